@@ -17,10 +17,21 @@ Other ways to deal the work (same kernels, same JSON line):
   --scaling strong     ONE 300-frame clip dealt frame-round-robin over the ranks (total work fixed)
   --streams S          BASELINE configs[3]: S independent 300-frame streams, stream s on rank s % N
 
-Prints ONE JSON line on rank 0.  Beside the contract keys it carries (N = 1 only, --no-extras to
-skip): `value_sustained` (the same step repeated for >= 0.5 s), `end_to_end` (PCIe-inclusive
-ntscsim_frames_host rates), `variant422` (the 8-bit YUV422P tool), `sizes` (1920x1080, 3840x2160)
-and `presets` (the default preset = BASELINE configs[0]'s workload on the GPU).
+Prints ONE JSON line on rank 0.  A plain run only sets up, warms up (the --sustain-seconds pre-roll, then
+the W steps), times the K steps and prints the contract keys (`value_sustained` = the pre-roll's own rate).
+Everything else the benchmark measures or checks runs only with --full: the kernel-time `roofline`, the
+CPU baselines (`cpu_baseline`), the re-computation of every rank's checksum and (N = 1 only, --no-extras
+to skip) the side legs of bench_side.py: `end_to_end` (PCIe-inclusive ntscsim_frames_host rates),
+`variant422` (the 8-bit YUV422P tool), `sizes` (1920x1080, 3840x2160) and `presets` (the default
+preset = BASELINE configs[0]'s workload on the GPU).  --full also writes the whole result to
+bench_extras.json.
+
+  --dump-outputs DIR   after the timed steps, write what the last timed step computed (this rank's
+                       destination clip(s)) to DIR as .npy: a fixed, seeded sample of its rows in
+                       float32 (dst_rows.npy, their flat frame * height + row indices in
+                       dst_row_ids.npy) and the byte sum of every destination frame in float64
+                       (dst_frame_sums.npy); < 64 MB in all.  The inputs depend on the arguments only,
+                       so two builds can be compared file for file.
 """
 import argparse
 import json
@@ -34,6 +45,8 @@ sys.path.insert(0, os.path.join(ROOT, "composite-video-simulator_amd"))
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_CLOCK_HZ = 2.4e9         # MI355X_MICROARCH.md: 256 CU x 4 SIMD-32 at 2.4 GHz
 N_SIMD = 256 * 4
+DUMP_ROW_BYTES = 48 << 20      # --dump-outputs: float32 row sample, all ranks together (plus small index / sum arrays)
+DUMP_SEED = 0x5EED
 
 
 from bench_side import (device_rate, device_stream_rate, emit, extras, make_bars_clip, time_steps,  # noqa: E402,F401
@@ -201,6 +214,31 @@ def valu_roofline(w, h, preset, fields_per_step, tm_ms, ms_per_step):
     return out, tj.get("k_decode_hbm_bytes_per_launch", None) and tj["k_decode_hbm_bytes_per_launch"] * scale
 
 
+def dump_outputs(torch, dirname, dsts, world, rank):
+    """--dump-outputs: the destination clip(s) [n, h, w, 4] uint8 of the last timed step as .npy files in
+    `dirname` -- a seeded sample of rows (all of them when they fit), their flat row ids, the byte sum of every
+    frame.  With N > 1 ranks every rank writes its own files (suffix _rank<r>), within a 1/N share of the budget."""
+    import numpy as np
+    if not dsts:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    _, h, w, c = dsts[0].shape
+    n_rows = [d.shape[0] * h for d in dsts]
+    total = sum(n_rows)
+    k = min(total, DUMP_ROW_BYTES // world // (w * c * 4))
+    ids = np.sort(np.random.default_rng(DUMP_SEED).choice(total, k, replace=False))
+    rows, sums, base = [], [], 0
+    for d, n in zip(dsts, n_rows):
+        sel = ids[(ids >= base) & (ids < base + n)] - base
+        rows.append(d.reshape(n, w, c)[torch.from_numpy(sel).to(d.device)].cpu().numpy())
+        sums.append(d.reshape(d.shape[0], -1).sum(dim=1, dtype=torch.int64).cpu().numpy())
+        base += n
+    tag = "_rank%d" % rank if world > 1 else ""
+    np.save(os.path.join(dirname, "dst_rows%s.npy" % tag), np.concatenate(rows).astype(np.float32))
+    np.save(os.path.join(dirname, "dst_row_ids%s.npy" % tag), ids.astype(np.float64))
+    np.save(os.path.join(dirname, "dst_frame_sums%s.npy" % tag), np.concatenate(sums).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -231,17 +269,28 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (and take the barrier / MAX / all-gather branches) even "
                          "with one rank: exercises the RCCL code path on a single GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure and check everything else: kernel-time roofline, CPU "
+                         "baselines, rank checksums, the side legs of bench_side.py; write bench_extras.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/*.npy")
     ap.add_argument("--cpu-fields", type=int, default=300,
-                    help="fields of the clip timed on the single-threaded CPU engines (0 = skip)")
+                    help="(--full) fields of the clip timed on the single-threaded CPU engines (0 = skip)")
     ap.add_argument("--cpu-mt-fields", type=int, default=8,
-                    help="fields per process of the all-cores CPU leg (0 = skip that leg)")
+                    help="(--full) fields per process of the all-cores CPU leg (0 = skip that leg)")
     ap.add_argument("--sustain-seconds", type=float, default=0.5,
                     help="before the W warm-up and K timed steps, repeat the same step for at least this long -> value_sustained")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip end_to_end / variant422 / sizes / presets (they run at N = 1 only)")
+                    help="(--full) skip end_to_end / variant422 / sizes / presets (they run at N = 1 only)")
     ap.add_argument("--cpu-worker", nargs=2, metavar=("A", "B"), default=None,
                     help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.tool == "to_composite":
+        # (that tool processes every field in place: what a step computes depends on how many steps ran before it,
+        # and the pre-roll's step count is timed, not fixed)
+        ap.error("--dump-outputs is not available with --tool to_composite")
     if args.cpu_worker:
         return cpu_worker(args)
     if args.tool == "to_composite":
@@ -359,12 +408,14 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, ctxs[(args.steps - 1) % nq][2], world, rank)
 
     # Kernel durations: hipEvents recorded on the launch stream around every kernel of the same
     # step, run right after the timed region on one context.  (Event records between kernels
     # serialise the in-flight streams, so they are kept out of the throughput measurement.)
     tm = {"calls": 0, "setup": 0.0, "encode": 0.0, "decode": 0.0}
-    if fields_per_step_local:
+    if args.full and fields_per_step_local:
         nprof = max(3, min(args.steps, 10))
         sm0, plans0, _, st0 = ctxs[0]
         sm0.set_profiling(True)
@@ -377,7 +428,7 @@ def main():
     def checksum(dsts):
         return int(sum(int(d.to(torch.int64).sum().item()) for d in dsts))
 
-    my_cs = checksum(ctxs[0][2]) if ctxs[0][2] else 0
+    my_cs = checksum(ctxs[0][2]) if args.full and ctxs[0][2] else 0
     allcs, verified = None, None
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -387,7 +438,7 @@ def main():
         cs = torch.tensor([my_cs, fields_per_step_local], dtype=torch.int64, device=red_dev)
         allg = [torch.zeros_like(cs) for _ in range(world)]
         dist.all_gather(allg, cs)
-        allcs = [int(c_[0].item()) for c_ in allg]
+        allcs = [int(c_[0].item()) for c_ in allg] if args.full else None
         fields_all = [int(c_[1].item()) for c_ in allg]
         if sustained is not None:
             ts = torch.tensor([sustained[1]], dtype=torch.float64, device=red_dev)
@@ -403,7 +454,7 @@ def main():
     out = None
     if rank == 0:
         # every rank's checksum, recomputed here on ONE GPU from that rank's share of the work
-        if dist is not None:
+        if dist is not None and args.full:
             exp = []
             for r in range(world):
                 if r == 0:
@@ -429,7 +480,7 @@ def main():
         achieved = alg_bytes_launch / (dec_ms * 1e-3) / 1e9 if dec_ms > 0 else 0.0
         ms_per_step = elapsed / args.steps * 1e3
         valu, traffic = (None, None)
-        if args.mode == "exact":
+        if args.full and args.mode == "exact":
             valu, traffic = valu_roofline(w, h, args.preset, launch_fields,
                                           {"decode": dec_ms, "encode": enc_ms, "setup": set_ms},
                                           ms_per_step * launch_fields / max(1, fields_per_step_local))
@@ -472,7 +523,7 @@ def main():
                              "measured without it (r01, r02) are ~4-6 % lower for that reason alone"},
                 "rank_checksums": allcs,
                 "rank_checksums_verified": verified,
-                "rank_checksums_note": None if dist is None else
+                "rank_checksums_note": None if allcs is None else
                     "sum of all bytes of each rank's destination clip(s); verified = rank 0 re-ran every "
                     "rank's share on its own GPU after the timed region and got the same sums",
                 "mode": "exact (bit-identical to the reference: fp64, no FMA contraction)"
@@ -480,7 +531,9 @@ def main():
                         ("fast32 (fp32 filters; <= 1 LSB per 8-bit channel vs the reference)" if args.mode == "fast32" else
                          "float (all-float pipeline; <= 1 LSB per 8-bit channel vs the reference)"),
             },
-            "roofline": {
+        }
+        if args.full:
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_decode" if args.mode != "float" else "k_decode_fp",
                 "achieved": achieved,
@@ -506,17 +559,16 @@ def main():
                 "kernel_timing": "hipEvents on the launch stream, %d steps on one context right "
                                  "after the timed region (un-shared launches; rocprofv3 "
                                  "--kernel-trace --stats of `--inflight 1` agrees, profiles/README.md)" % calls,
-            },
-        }
+            }
         if sustained is not None:
             out["value_sustained"] = total_fields_per_step * sustained[0] / sustained[1]
             out["sustained"] = {"steps": sustained[0], "seconds": sustained[1], "order": "sustained leg, then W warm-up steps, then the K timed steps"}
-        if world == 1 and not args.no_extras and args.mode == "exact" and args.streams == 0:
+        if args.full and world == 1 and not args.no_extras and args.mode == "exact" and args.streams == 0:
             try:
                 out.update(extras(torch, ntscsim, dev, local_rank, args))
             except Exception as e:      # never lose the headline line to an extra
                 out["extras_error"] = repr(e)
-        if world == 1 and args.cpu_fields > 0 and args.mode == "exact" and fields_per_step_local:
+        if args.full and world == 1 and args.cpu_fields > 0 and args.mode == "exact" and fields_per_step_local:
             import numpy as np
             dst = ctxs[0][2][0]
             ncpu = min(args.cpu_fields, len(clips[0][3]))
@@ -568,7 +620,7 @@ def main():
         dist.destroy_process_group()
     # (after the teardown: the contract object is the last thing this process writes to stdout)
     if out is not None:
-        emit(out)
+        emit(out, "bench_extras.json" if args.full else None)
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""bench_side.py -- the side benchmarks of bench.py (N = 1, rank 0, `--no-extras` skips them): the numbers README /
+"""bench_side.py -- the side benchmarks of bench.py (--full, N = 1, rank 0; `--no-extras` skips them): the numbers README /
 DESIGN quote BESIDE the contract's headline value -- PCIe-inclusive host-frame rates, the drop-in loops of host/*.cpp,
 the 8-bit YUV422P tool, the raw-composite decoder, other sizes and switch sets -- and the helpers they share with the
 headline (synthetic clips, device-resident contexts).  bench.py owns the contract line, the roofline and the CPU
@@ -567,9 +567,10 @@ def compact_line(out, extras_file):
     if pre:
         line["config"]["pre_roll_s"] = pre.get("seconds")
     rf = out.get("roofline") or {}
-    line["roofline"] = {k: rf[k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic",
-                                           "algorithmic_bytes_per_launch", "kernel_ms", "kernel_ms_all",
-                                           "path_achieved", "live_fields") if k in rf}
+    if rf:                                  # (--full only)
+        line["roofline"] = {k: rf[k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic",
+                                               "algorithmic_bytes_per_launch", "kernel_ms", "kernel_ms_all",
+                                               "path_achieved", "live_fields") if k in rf}
     if rf.get("traffic") is not None:
         line["roofline"]["traffic_source"] = "replayed:profiles/traffic.json"
     valu = rf.get("valu") or {}
@@ -608,7 +609,8 @@ def compact_line(out, extras_file):
     if side:
         side["unit"] = "frames/s"
         line["side"] = side
-    line["extras_file"] = extras_file
+    if extras_file:
+        line["extras_file"] = extras_file
     line = _r(line)
     # never lose the line to its own length: drop the optional parts, largest first
     for drop in ("presets", "sizes", None):
@@ -623,9 +625,10 @@ def compact_line(out, extras_file):
 
 def emit(out, name="bench_extras.json"):
     """Full dictionary -> bench_extras.json (and gpurun_out/ when present); contract object -> the last stdout line."""
-    paths = [os.path.join(ROOT, name)]
+    # name None (a plain run, without --full): no file, the contract object only
+    paths = [os.path.join(ROOT, name)] if name else []
     god = os.path.join(ROOT, "gpurun_out")
-    if os.path.isdir(god):
+    if name and os.path.isdir(god):
         paths.append(os.path.join(god, name))
     written = None
     for p in paths:

@@ -61,13 +61,15 @@ def main_to_composite(args):
         vstep(i)
     fence()
     elapsed = time.perf_counter() - t0
-    # kernel time: hipEvents around the kernels of un-shared launches on one context
-    sims[0].set_profiling(True)
-    for _ in range(5):
-        vstep(0)
-    torch.cuda.synchronize(dev)
-    tm = sims[0].timings_ms()
-    sims[0].set_profiling(False)
+    # kernel time (--full): hipEvents around the kernels of un-shared launches on one context
+    tm = {"calls": 0, "setup": 0.0, "decode": 0.0}
+    if args.full:
+        sims[0].set_profiling(True)
+        for _ in range(5):
+            vstep(0)
+        torch.cuda.synchronize(dev)
+        tm = sims[0].timings_ms()
+        sims[0].set_profiling(False)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -115,18 +117,19 @@ def main_to_composite(args):
                        "pre_roll": None if sustained is None else
                            {"steps": sustained[0], "seconds": sustained[1],
                             "note": "untimed steps of the same work before the W warm-up steps (= the value_sustained leg)"}},
-            "roofline": {"bound": "hbm", "kernel": "k422_fused", "achieved": alg / (k_ms * 1e-3) / 1e9 if k_ms else 0.0,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if k_ms else 0.0,
-                         "traffic": traffic, "algorithmic_bytes_per_launch": alg, "kernel_ms": k_ms,
-                         "kernel_ms_all": {"setup": set_ms, "process": k_ms}, "valu": valu,
-                         "kernel_forms": sims[0].last_kernels(),
-                         "note": "4*W*L algorithmic bytes per field; like the BGRA tool the kernel is bound by "
-                                 "dependent fp64 filter chains, not by HBM (DESIGN.md section 7)"},
         }
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "kernel": "k422_fused", "achieved": alg / (k_ms * 1e-3) / 1e9 if k_ms else 0.0,
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": (alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if k_ms else 0.0,
+                               "traffic": traffic, "algorithmic_bytes_per_launch": alg, "kernel_ms": k_ms,
+                               "kernel_ms_all": {"setup": set_ms, "process": k_ms}, "valu": valu,
+                               "kernel_forms": sims[0].last_kernels(),
+                               "note": "4*W*L algorithmic bytes per field; like the BGRA tool the kernel is bound by "
+                                       "dependent fp64 filter chains, not by HBM (DESIGN.md section 7)"}
         if sustained is not None:
             out["value_sustained"] = world * nf * sustained[0] / sustained[1]
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the switch-set families beside the -vhs one, measured the same way: 24 steps after one
             # per context, no pre-roll; which kernel form each took is recorded beside its rate
             import copy
@@ -161,7 +164,7 @@ def main_to_composite(args):
                 if ref and "value" in v_:
                     v_["frac_of_preset"] = v_["value"] / ref
             out["presets"] = legs
-        if args.cpu_fields > 0:
+        if args.full and args.cpu_fields > 0:
             p422 = ntscsim.make_params_to_composite(args.preset.split())
             ncpu = min(args.cpu_fields, nf)
             have_ref = L.have_tocomp_ref()
@@ -199,4 +202,4 @@ def main_to_composite(args):
     if dist is not None:
         dist.destroy_process_group()
     if rank == 0 and out is not None:
-        emit(out, "bench_extras_to_composite.json")
+        emit(out, "bench_extras_to_composite.json" if args.full else None)

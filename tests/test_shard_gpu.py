@@ -75,7 +75,7 @@ def test_hip_shards_equal_the_serial_run(world, tmp_path):
                          ids=["weak", "strong", "streams8"])
 def test_bench_multirank_branch_verifies_itself(extra):
     r = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "3",
-                    "--warmup", "1", "--frames", "12", "--cpu-fields", "0", "--sustain-seconds", "0"] + extra)
+                    "--warmup", "1", "--frames", "12", "--cpu-fields", "0", "--sustain-seconds", "0", "--full"] + extra)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

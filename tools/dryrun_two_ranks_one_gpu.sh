@@ -11,7 +11,7 @@ mkdir -p gpurun_out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 run() {
   timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $2 \
-      bench.py --gpus 2 --steps 10 --warmup 3 --no-extras --cpu-fields 0 --sustain-seconds 0 --dist-backend $1 2> /tmp/dryrun_$1.err | grep '^{' | tail -1
+      bench.py --full --gpus 2 --steps 10 --warmup 3 --no-extras --cpu-fields 0 --sustain-seconds 0 --dist-backend $1 2> /tmp/dryrun_$1.err | grep '^{' | tail -1
 }
 {
 echo "# two ranks on one GPU, backend $backend"

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/${1:-fp_probe}
 mkdir -p $OUT
 for v in ${2:-0 1}; do
   echo "== variant $v"
-  NTSCSIM_FP_VARIANT=$v python bench.py --mode float --no-extras --cpu-fields 0 2>/dev/null | tail -1 | python -c "
+  NTSCSIM_FP_VARIANT=$v python bench.py --full --mode float --no-extras --cpu-fields 0 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('value %.0f sustained %.0f ms/step %.4f kernels %s' % (d['value'], d.get('value_sustained',0), d['ms_per_step'], d['roofline']['kernel_ms_all']))"
 done

@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/${1:-kstats}; shift
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o ks -- python "$R/bench.py" --cpu-fields 0 "$@" > "$OUT/bench.log" 2>&1 < /dev/null
+timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o ks -- python "$R/bench.py" --full --cpu-fields 0 "$@" > "$OUT/bench.log" 2>&1 < /dev/null
 cd "$R"
 f=$(find "$OUT" -name "*kernel_stats.csv" | head -1)
 if [ -n "$f" ]; then cp "$f" "$OUT/kernel_stats.csv"; python - "$OUT/kernel_stats.csv" <<'PY'

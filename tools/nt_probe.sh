@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 for n in base nt_all2 nt_encld base nt_all2; do
   lib=$R/tools/bin/variants/lib_$n.so
   [ -f $lib ] || continue
-  v=$(NTSCSIM_LIB=$lib timeout 120 python bench.py --cpu-fields 0 --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); k=d['roofline']['kernel_ms_all']; print('value %.0f sustained %.0f  enc %.4f dec %.4f ms' % (d['value'], d['value_sustained'], k['encode'], k['decode']))")
+  v=$(NTSCSIM_LIB=$lib timeout 120 python bench.py --full --cpu-fields 0 --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); k=d['roofline']['kernel_ms_all']; print('value %.0f sustained %.0f  enc %.4f dec %.4f ms' % (d['value'], d['value_sustained'], k['encode'], k['decode']))")
   echo "$n: $v"
 done
 cd /tmp

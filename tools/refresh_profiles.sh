@@ -2,25 +2,27 @@
 # How profiles/ is produced (two GPU calls + one local step); TAG = r02, r03, ...
 #
 # 1. GPU box:   bash tools/refresh_profiles.sh gpu r02        (counters, kernel stats, probes, bench line)
+#               RESULTS_DIR = the results directory the probes below write to (the bench lines go there too)
 # 2. locally:   bash tools/refresh_profiles.sh local r02      (ISA census + assemble profiles/)
 # 3. GPU box again for the bench line once profiles/traffic.json has changed (bench.py reads it for
 #    roofline.traffic / roofline.valu), then step 2 again.
 set -u
 mode=${1:-local}; tag=${2:-r02}
 if [ "$mode" = gpu ]; then
+  res=${RESULTS_DIR:?set RESULTS_DIR to the results directory of this run}
   timeout 700 bash tools/pmc.sh pmc_$tag > /dev/null 2>&1
   timeout 250 tools/kstats.sh ks_${tag}_if1 --inflight 1 --steps 20 --no-extras --sustain-seconds 0 > /dev/null
   timeout 250 tools/kstats.sh ks_${tag}_default --no-extras --sustain-seconds 0 > /dev/null
   timeout 120 tools/bin/valu_rate_probe > gpurun_out/valu_rates_$tag.txt 2>&1
   timeout 120 tools/bin/chain_probe > gpurun_out/chain_probe_$tag.txt 2>&1
-  timeout 900 python bench.py > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err
-  timeout 200 python bench.py --mode fast32 --cpu-fields 0 --no-extras > gpurun_out/bench_${tag}_fast32.json 2>> gpurun_out/bench_$tag.err
-  # the command the driver runs at round end, exactly (its own K / W, every side leg): the contract line and what it left in
-  # bench_extras.json
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_${tag}_driver_cmd.json 2>> gpurun_out/bench_$tag.err
+  timeout 900 python bench.py --full > "$res/bench_$tag.json" 2> "$res/bench_$tag.err"
+  timeout 200 python bench.py --full --mode fast32 --cpu-fields 0 --no-extras > "$res/bench_${tag}_fast32.json" 2>> "$res/bench_$tag.err"
+  # the command the driver runs at round end (its own K / W) with --full (every side leg): the contract line and what it
+  # left in bench_extras.json
+  timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$res/bench_${tag}_driver_cmd.json" 2>> "$res/bench_$tag.err"
   cp bench_extras.json gpurun_out/bench_extras_$tag.json 2> /dev/null
   # NTSCSIM_MODE_FLOAT (round 6): bench line, kernel stats, error against the oracle, stall counters of its forms, HBM bytes
-  timeout 200 python bench.py --mode float --cpu-fields 0 --no-extras > gpurun_out/bench_${tag}_float.json 2>> gpurun_out/bench_$tag.err
+  timeout 200 python bench.py --full --mode float --cpu-fields 0 --no-extras > "$res/bench_${tag}_float.json" 2>> "$res/bench_$tag.err"
   timeout 250 tools/kstats.sh ks_${tag}_float --mode float --inflight 1 --steps 20 --no-extras --sustain-seconds 0 > /dev/null
   timeout 600 python tools/float_err.py --mode float > gpurun_out/float_err_$tag.txt 2>&1
   timeout 400 bash tools/fp_probe.sh fp_$tag "10 0" "10 0" > gpurun_out/float_pmc_$tag.txt 2>&1
@@ -34,7 +36,7 @@ if [ "$mode" = gpu ]; then
   timeout 300 bash tools/sync422_trace.sh > /dev/null 2>&1          # -> gpurun_out/sync422_timeline.txt
   timeout 500 bash tools/pmc422.sh pmc422_$tag > /dev/null 2>&1
   timeout 250 tools/kstats.sh ks_${tag}_tocomp --tool to_composite --inflight 1 --steps 20 --sustain-seconds 0 > /dev/null
-  timeout 600 python bench.py --tool to_composite --cpu-fields 200 > gpurun_out/bench_${tag}_tocomp.json 2>> gpurun_out/bench_$tag.err
+  timeout 600 python bench.py --full --tool to_composite --cpu-fields 200 > "$res/bench_${tag}_tocomp.json" 2>> "$res/bench_$tag.err"
   ( export TMPDIR=/tmp; R=$PWD; O=$R/gpurun_out/ks_${tag}_raw28; mkdir -p $O; cd /tmp;
     timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o ks -- python $R/tools/raw28_probe.py > $O/probe.log 2>&1 < /dev/null;
     f=$(find $O -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv )

@@ -11,10 +11,10 @@ for n in 1 2 4 8; do
   [ "$n" -le "$max" ] || break
   port=$((29700 + n))
   if [ "$n" -eq 1 ]; then
-    line=$(python bench.py --gpus 1 --no-extras --cpu-fields 0 --force-dist "$@" 2> /tmp/run_multi_gpu_$n.err | grep '^{' | tail -1)
+    line=$(python bench.py --full --gpus 1 --no-extras --cpu-fields 0 --force-dist "$@" 2> /tmp/run_multi_gpu_$n.err | grep '^{' | tail -1)
   else
     line=$(python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port "$port" \
-           bench.py --gpus "$n" --no-extras --cpu-fields 0 "$@" 2> /tmp/run_multi_gpu_$n.err | grep '^{' | tail -1)
+           bench.py --full --gpus "$n" --no-extras --cpu-fields 0 "$@" 2> /tmp/run_multi_gpu_$n.err | grep '^{' | tail -1)
   fi
   if [ -z "$line" ]; then echo "N=$n FAILED (see /tmp/run_multi_gpu_$n.err)"; tail -3 /tmp/run_multi_gpu_$n.err; continue; fi
   base=$(python - "$n" "$base" "$line" <<'PY'

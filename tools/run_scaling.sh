@@ -5,7 +5,7 @@
 for n in "$@"; do
   lib=$(pwd)/tools/bin/variants/lib_$n.so
   for fr in 134 269 404; do
-    NTSCSIM_LIB=$lib timeout 120 python bench.py --cpu-fields 0 --inflight 1 --steps 20 --frames $fr > /tmp/s.json 2>/dev/null
+    NTSCSIM_LIB=$lib timeout 120 python bench.py --full --cpu-fields 0 --inflight 1 --steps 20 --frames $fr > /tmp/s.json 2>/dev/null
     python - "$n" $fr <<'PY'
 import json, sys
 d = json.load(open("/tmp/s.json")); k = d["roofline"]["kernel_ms_all"]; n = 2 * int(sys.argv[2])

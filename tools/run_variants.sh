@@ -8,7 +8,7 @@ names="$@"
 for n in $names; do
   lib=$(pwd)/tools/bin/variants/lib_$n.so
   for q in 1 3; do
-    NTSCSIM_LIB=$lib timeout 120 python bench.py --cpu-fields 0 --inflight $q --steps 30 --warmup 5 > "$out/$n.if$q.json" 2> "$out/$n.if$q.err"
+    NTSCSIM_LIB=$lib timeout 120 python bench.py --full --cpu-fields 0 --inflight $q --steps 30 --warmup 5 > "$out/$n.if$q.json" 2> "$out/$n.if$q.err"
   done
   python - "$out" "$n" <<'PY'
 import json, sys
