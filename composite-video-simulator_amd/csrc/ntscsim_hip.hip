@@ -26,6 +26,7 @@
 #include "ntsc422_fused.hip"
 #include "ntsc_scale.hip"
 #include "ntsc_float.hpp"       // NTSCSIM_MODE_FLOAT: its kernels are a translation unit of their own
+#include "ntsc_blend.hpp"       // the frameblend stage (ntscsim_blend_*): likewise, csrc/ntsc_blend.hip
 
 using namespace ntscsim;
 
@@ -217,7 +218,12 @@ struct ntscsim_ctx {
     bool latency_form = false;
     bool latency_pref = false;       // ntscsim_set_launch_form(): the device-pointer entry points' short launches take it too
     unsigned *pipe_fault = nullptr;  // pinned word the role kernels raise when a hand-off timed out (ntsc_pipe.hip); checked behind launches
+    ntscsim::BlendState *blend = nullptr;   // ntscsim_blend_bind(): state of the frameblend stage (csrc/ntsc_blend.hip)
 };
+ntscsim::CtxBlendView ntscsim::ctx_blend_view(ntscsim_ctx *c)
+{
+    return CtxBlendView{c->device, c->stream, &c->err, &c->kernels, &c->blend};
+}
 static void declared_pins_destroy(ntscsim_ctx *c);
 static uint8_t *pinned_device_ptr(ntscsim_ctx *c, const void *p, size_t span);      // ntscsim_submit.hip
 static void submit_engine_destroy(ntscsim_ctx *c);
@@ -465,6 +471,7 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     submit_engine_destroy(c);
     host422_engine_destroy(c);
     declared_pins_destroy(c);
+    if (c->blend) { ntscsim::blend_state_destroy(c->blend); c->blend = nullptr; }
     for (Geometry *e : c->geoms) {
         e->lskip.release(); e->pskip.release(); e->jrow.release(); e->sstart.release(); e->jwarm.release();
         delete e;

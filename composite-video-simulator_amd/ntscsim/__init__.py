@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -391,6 +391,131 @@ class FieldSimulator:
             self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size)
         self._chk(rc, "ntscsim_debug_read_composite")
         return a
+
+
+def blend_frame_times(params, n_frames, rate_num, rate_den=1):
+    """Times, in output periods, of the frames of a constant-rate clip: pts = frame number, time base =
+    rate_den / rate_num (ntscsim_blend_frame_time, frameblend.cpp:100-110)."""
+    L = lib()
+    return [float(L.ntscsim_blend_frame_time(k, int(rate_den), int(rate_num), C.byref(params))) for k in range(n_frames)]
+
+
+def blend_plan(params, times, first=0, last=None):
+    """The planner (ntscsim_blend_plan_*, frameblend.cpp:929-1028) over a whole clip, with the tool's read-ahead of
+    30 periods (:910): a list, one entry per output period in [first, last), of (ids, weight16) -- ids are indices
+    into `times`.  last = None: the tool's own end of the clip (ntscsim_blend_clip_periods).  Host only: no GPU."""
+    L = lib()
+    times = [float(t) for t in times]
+    if last is None:
+        last = int(L.ntscsim_blend_clip_periods(times[-1]))
+    h = C.c_void_p()
+    rc = L.ntscsim_blend_plan_create(C.byref(params), C.byref(h))
+    if rc != _capi.OK:
+        raise NtscsimError(rc, "ntscsim_blend_plan_create")
+    out = []
+    try:
+        cap = 64
+        ids, w16 = (C.c_int64 * cap)(), (C.c_uint32 * cap)()
+        n = C.c_int(0)
+        pushed = 1
+        L.ntscsim_blend_plan_push(h, times[0])
+        for current in range(int(last)):
+            while pushed < len(times) and times[pushed - 1] < current + 30:
+                L.ntscsim_blend_plan_push(h, times[pushed])
+                pushed += 1
+            rc = L.ntscsim_blend_plan_next(h, current, ids, w16, cap, C.byref(n), None)
+            if rc == _capi.E_SIZE:
+                cap = n.value
+                ids, w16 = (C.c_int64 * cap)(), (C.c_uint32 * cap)()
+                rc = L.ntscsim_blend_plan_next(h, current, ids, w16, cap, C.byref(n), None)
+            if rc != _capi.OK:
+                raise NtscsimError(rc, "ntscsim_blend_plan_next(%d)" % current)
+            if current >= first:
+                out.append(([int(ids[k]) for k in range(n.value)], [int(w16[k]) for k in range(n.value)]))
+    finally:
+        L.ntscsim_blend_plan_destroy(h)
+    return out
+
+
+class FrameBlender:
+    """The frameblend stage (ntscsim_blend_*): resamples a clip to the output rate by blending the source frames
+    that overlap each output period.  `flags` are frameblend's switches, e.g. ("-gamma", "ntsc").  sim: share the
+    context of a FieldSimulator (the outputs can then be handed to sim.fields() on the same stream); otherwise a
+    context of its own is created.  torch is used only for device memory and streams."""
+
+    def __init__(self, flags=(), device=0, params=None, sim=None):
+        self.params = params if params is not None else _capi.make_blend_params(flags)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        self.sim._chk(self._lib.ntscsim_blend_bind(self.sim._h, C.byref(self.params)), "ntscsim_blend_bind")
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    def frame_times(self, n_frames, rate_num, rate_den=1):
+        return blend_frame_times(self.params, n_frames, rate_num, rate_den)
+
+    def plan(self, times, first=0, last=None):
+        return blend_plan(self.params, times, first, last)
+
+    def n_out(self, times):
+        """Output periods the tool renders for a clip with these frame times (frameblend.cpp:924-927)."""
+        return int(self._lib.ntscsim_blend_clip_periods(float(times[-1])))
+
+    @staticmethod
+    def _descs(jobs, ptr, linesize):
+        """jobs: list of (dst, [(src, weight16), ...]), frames [H, W, 4] uint8 with contiguous pixels."""
+        arr = (_capi.BlendDesc * len(jobs))()
+        keep = []
+        for d, (dst, taps) in zip(arr, jobs):
+            h, w = dst.shape[0], dst.shape[1]
+            t = (_capi.BlendTap * max(1, len(taps)))()
+            for k, (src, w16) in enumerate(taps):
+                assert tuple(src.shape) == (h, w, 4)
+                t[k].src_dev, t[k].src_linesize, t[k].weight16 = ptr(src), linesize(src), int(w16)
+            keep.append(t)
+            d.dst_dev, d.dst_linesize, d.width, d.height, d.n_taps, d.taps = ptr(dst), linesize(dst), w, h, len(taps), t
+        return arr, keep
+
+    def blend_frames(self, jobs, stream=None):
+        """ntscsim_blend_frames_device: jobs = [(dst, [(src, weight16), ...]), ...] of torch uint8 CUDA tensors
+        [H, W, 4] (any row stride).  Enqueues; does not synchronise."""
+        arr, keep = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        rc = self._lib.ntscsim_blend_frames_device(self.sim._h, arr, len(jobs), C.c_void_p(stream))
+        self.sim._chk(rc, "ntscsim_blend_frames_device")
+
+    def blend_frames_host(self, jobs):
+        """ntscsim_blend_frames_host: the same on numpy uint8 arrays [H, W, 4].  Synchronous."""
+        arr, keep = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self.sim._chk(self._lib.ntscsim_blend_frames_host(self.sim._h, arr, len(jobs)), "ntscsim_blend_frames_host")
+
+    def blend(self, src, times, out, first=0, last=None, stream=None):
+        """ntscsim_blend_clip_device: src torch uint8 CUDA [N, H, W, 4] with frame times `times` (output periods),
+        out [last - first, H, W, 4]; output period k lands in out[k - first].  Enqueues; does not synchronise."""
+        n, h, w = src.shape[0], src.shape[1], src.shape[2]
+        if last is None:
+            last = first + out.shape[0]
+        assert src.is_cuda and out.is_cuda and len(times) == n and out.shape[0] >= last - first
+        assert tuple(out.shape[1:]) == (h, w, 4) and src.stride(2) == 4 and out.stride(2) == 4
+        sp = (C.c_void_p * n)(*[src.data_ptr() + j * src.stride(0) for j in range(n)])
+        dp = (C.c_void_p * max(1, last - first))(*[out.data_ptr() + k * out.stride(0) for k in range(last - first)])
+        tt = (C.c_double * n)(*[float(t) for t in times])
+        if stream is None:
+            stream = self.sim._torch_stream()
+        rc = self._lib.ntscsim_blend_clip_device(self.sim._h, sp, src.stride(1), tt, n, dp, out.stride(1), w, h,
+                                                 int(first), int(last), C.c_void_p(stream))
+        self.sim._chk(rc, "ntscsim_blend_clip_device")
+
+    def last_kernels(self):
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
 
 
 class Pool:

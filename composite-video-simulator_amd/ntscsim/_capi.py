@@ -45,6 +45,10 @@ EXPORTS = (
     "ntscsim_field422", "ntscsim_submit422", "ntscsim_submit422_configure", "ntscsim_submit422_stats",
     "ntscsim_pool_create", "ntscsim_pool_destroy", "ntscsim_pool_size", "ntscsim_pool_ctx", "ntscsim_pool_set_block",
     "ntscsim_pool_get_rng_pos", "ntscsim_pool_set_rng_pos", "ntscsim_pool_last_error", "ntscsim_pool_frames_host",
+    "ntscsim_blend_params_init", "ntscsim_blend_parse_argv", "ntscsim_blend_frame_time",
+    "ntscsim_blend_plan_create", "ntscsim_blend_plan_push", "ntscsim_blend_plan_next", "ntscsim_blend_plan_reset",
+    "ntscsim_blend_plan_destroy", "ntscsim_blend_clip_periods", "ntscsim_blend_tables", "ntscsim_blend_bind",
+    "ntscsim_blend_frames_device", "ntscsim_blend_clip_device", "ntscsim_blend_frames_host",
 )
 
 
@@ -210,6 +214,29 @@ class HostSource(C.Structure):
         ("plane_offset", C.c_size_t * 3),
         ("frame_bytes", C.c_size_t),
     ]
+
+
+class BlendParams(C.Structure):
+    """struct ntscsim_blend_params -- keep in lock-step with include/ntscsim.h."""
+    _fields_ = [("struct_size", C.c_uint32), ("rate_num", C.c_int32), ("rate_den", C.c_int32),
+                ("output_width", C.c_int32), ("output_height", C.c_int32), ("squelch_near_match", C.c_int32),
+                ("fullframealt", C.c_int32), ("framealt", C.c_int32), ("gamma_correction", C.c_double),
+                ("underscan", C.c_int32), ("use_422_colorspace", C.c_int32), ("n_inputs", C.c_int32), ("_pad", C.c_int32),
+                ("input_path", C.c_char_p), ("output_path", C.c_char_p)]
+
+
+class BlendTap(C.Structure):
+    """struct ntscsim_blend_tap"""
+    _fields_ = [("src_dev", C.c_void_p), ("src_linesize", C.c_int32), ("weight16", C.c_uint32)]
+
+
+class BlendDesc(C.Structure):
+    """struct ntscsim_blend_desc"""
+    _fields_ = [("dst_dev", C.c_void_p), ("dst_linesize", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("n_taps", C.c_int32), ("taps", C.POINTER(BlendTap))]
+
+
+BLEND_FAST_TAPS = 4
 
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
@@ -407,6 +434,37 @@ def lib():
     L.ntscsim_pool_frames_host.argtypes = [C.c_void_p, _u8p, C.c_size_t, C.c_int, C.c_int, _u8p, C.c_size_t, C.c_int,
                                            C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int]
     L.ntscsim_pool_frames_host.restype = C.c_int
+    L.ntscsim_blend_params_init.argtypes = [C.POINTER(BlendParams)]
+    L.ntscsim_blend_params_init.restype = None
+    L.ntscsim_blend_parse_argv.argtypes = [C.POINTER(BlendParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ntscsim_blend_parse_argv.restype = C.c_int
+    L.ntscsim_blend_frame_time.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(BlendParams)]
+    L.ntscsim_blend_frame_time.restype = C.c_double
+    L.ntscsim_blend_plan_create.argtypes = [C.POINTER(BlendParams), C.POINTER(C.c_void_p)]
+    L.ntscsim_blend_plan_create.restype = C.c_int
+    L.ntscsim_blend_plan_push.argtypes = [C.c_void_p, C.c_double]
+    L.ntscsim_blend_plan_push.restype = C.c_int64
+    L.ntscsim_blend_plan_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.ntscsim_blend_plan_next.restype = C.c_int
+    L.ntscsim_blend_plan_reset.argtypes = [C.c_void_p]
+    L.ntscsim_blend_plan_reset.restype = None
+    L.ntscsim_blend_plan_destroy.argtypes = [C.c_void_p]
+    L.ntscsim_blend_plan_destroy.restype = None
+    L.ntscsim_blend_clip_periods.argtypes = [C.c_double]
+    L.ntscsim_blend_clip_periods.restype = C.c_int64
+    L.ntscsim_blend_tables.argtypes = [C.c_double, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]
+    L.ntscsim_blend_tables.restype = C.c_int
+    L.ntscsim_blend_bind.argtypes = [C.c_void_p, C.POINTER(BlendParams)]
+    L.ntscsim_blend_bind.restype = C.c_int
+    L.ntscsim_blend_frames_device.argtypes = [C.c_void_p, C.POINTER(BlendDesc), C.c_int, C.c_void_p]
+    L.ntscsim_blend_frames_device.restype = C.c_int
+    L.ntscsim_blend_clip_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                            C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                            C.c_void_p]
+    L.ntscsim_blend_clip_device.restype = C.c_int
+    L.ntscsim_blend_frames_host.argtypes = [C.c_void_p, C.POINTER(BlendDesc), C.c_int]
+    L.ntscsim_blend_frames_host.restype = C.c_int
     _lib = L
     return L
 
@@ -463,3 +521,18 @@ def make_raw28_opts(flags=()):
     if rc != OK:
         raise NtscsimError(rc, "raw28 parse_argv(%r)" % (list(flags),))
     return o
+
+
+def make_blend_params(flags=(), require_io=False):
+    """ntscsim_blend_params from frameblend's switches (frameblend.cpp parse_argv :512).  The returned struct keeps
+    the argv strings alive (input_path / output_path point into them)."""
+    L = lib()
+    p = BlendParams()
+    L.ntscsim_blend_params_init(C.byref(p))
+    argv = [b"frameblend"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    rc = L.ntscsim_blend_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
+    if rc != OK:
+        raise NtscsimError(rc, "blend parse_argv(%r)" % (list(flags),))
+    p._argv = arr
+    return p

@@ -821,6 +821,120 @@ void ntscsim_raw28_debug_pick_chunk(double scanline_samples, double target_sampl
 /* Debug tap: the front end's hsync_dc_raw of every sample of the last call, to host memory */
 int  ntscsim_raw28_debug_read_front(ntscsim_raw28 *dec, uint8_t *hsync_dc_raw, size_t n);
 
+/* ---- frameblend: the frame-rate converter in front of the simulator (frameblend.cpp) ---------------
+ * The tool resamples a clip to the output rate: every output period `current` (one tick of
+ * output_field_rate) is the blend of the source frames that overlap [current, current + 1), weighted by
+ * the overlap, optionally in linear light through a gamma table (main() :929-1081).  Mapping:
+ *
+ *   globals :44-57 + preset_NTSC() :491-494 + parse_argv() :512-634 | ntscsim_blend_params, _init(), _parse_argv()
+ *   InputFile::video_frame_rgb_to_output_f() :100-110               | ntscsim_blend_frame_time()
+ *   the weight scan, squelch and weight16 :929-1028, erase :1107-1120 | ntscsim_blend_plan_*()   (host, no GPU)
+ *   gamma16_do_init() :724-732                                      | ntscsim_blend_tables()    (host libm)
+ *   the pixel loops :1032-1081                                      | ntscsim_blend_frames_device() / _clip_device() / _frames_host()
+ *
+ * Decoding, scaling (-underscan, sws_scale) and encoding stay with the caller; the
+ * switches that steer them are parsed and recorded.  Output frames are BGRA with alpha 0xFF (:1051), stay in
+ * device memory and can be handed to ntscsim_fields_device() as sources.
+ */
+typedef struct ntscsim_blend_params {
+    uint32_t struct_size;            /* = sizeof(ntscsim_blend_params)                                   */
+    int32_t  rate_num, rate_den;     /* output_field_rate :54 / preset_NTSC() :491-494  60000 / 1001     */
+    int32_t  output_width;           /* :55  -1 = size of the input (-width, >= 32)                      */
+    int32_t  output_height;          /* :56  -1                                                          */
+    int32_t  squelch_near_match;     /* squelch_frameblend_near_match :44  false (-sqnr)                 */
+    int32_t  fullframealt;           /* :46  false (-ffa)                                                */
+    int32_t  framealt;               /* :47  1 (-fa, clamped 1..8 :548-550)                              */
+    double   gamma_correction;       /* :49  -1; the gamma path runs only when > 1 (:1032)               */
+    /* recorded for the media I/O layer, not acted on here */
+    int32_t  underscan;              /* :51  0 (-underscan, clamped 0..99)                               */
+    int32_t  use_422_colorspace;     /* :53  false (-422 / -420)                                         */
+    int32_t  n_inputs;               /* number of -i switches seen (:561-565)                            */
+    int32_t  _pad;
+    const char *input_path;          /* the last -i                                                      */
+    const char *output_path;         /* -o :595-599                                                      */
+} ntscsim_blend_params;
+
+void ntscsim_blend_params_init(ntscsim_blend_params *p);
+/* Mirror of parse_argv() :512-634: same switch names (any number of leading '-'), clamps and the -or forms
+ * (:566-594: strtof, optional :d /d \d, "< 5 fps" floor, a bare number is stored x10000 over 10000).
+ * argv[0] is the program name.  require_io != 0 applies the "No output file / No input files" checks
+ * (:624-631).  Returns NTSCSIM_OK, NTSCSIM_E_HELP (-h / -help) or NTSCSIM_E_FLAG (the tool's "return 1"). */
+int  ntscsim_blend_parse_argv(ntscsim_blend_params *p, int argc, const char *const *argv, int require_io);
+/* :100-110: pts as a double, times tb_num * rate_num, then divided by tb_den * rate_den (both products in
+ * signed 64-bit integers; two roundings, in that order). */
+double ntscsim_blend_frame_time(int64_t pts, int32_t tb_num, int32_t tb_den, const ntscsim_blend_params *p);
+
+/* The planner: which source frames make output period `current`, with which 16.16 weights (:929-1028).
+ * It is stateful like the tool's two vectors: ntscsim_blend_plan_push() appends a frame (its time from
+ * ntscsim_blend_frame_time()) and returns its STABLE id, counted from 0 at the start of the clip;
+ * ntscsim_blend_plan_next() must be called once per output period, in order (the tool's `current++`).  It
+ * reproduces the erase of the first `cutoff` frames once cutoff reaches 32 (:1107-1120) -- which renumbers
+ * the tool's indices and shifts the phase of the -fa scan (:937) -- internally: ids stay stable, and
+ * *release_below (may be NULL) is the lowest id a later call can still name, so the caller may free or
+ * reuse every source frame below it.  *n receives the tap count (0: the tool writes a black frame); with
+ * more than `cap` taps the call returns NTSCSIM_E_SIZE, *n is the count needed and the state is unchanged.
+ * Taps whose weight rounded to 0 are listed (they add nothing).  Plain double / integer arithmetic, no GPU. */
+typedef struct ntscsim_blend_plan ntscsim_blend_plan;
+int     ntscsim_blend_plan_create(const ntscsim_blend_params *p, ntscsim_blend_plan **out);
+int64_t ntscsim_blend_plan_push(ntscsim_blend_plan *plan, double frame_t);
+int     ntscsim_blend_plan_next(ntscsim_blend_plan *plan, int64_t current, int64_t *ids, uint32_t *weight16,
+                                int cap, int *n, int64_t *release_below);
+void    ntscsim_blend_plan_reset(ntscsim_blend_plan *plan);
+void    ntscsim_blend_plan_destroy(ntscsim_blend_plan *plan);
+/* Number of output periods the tool renders for a clip whose LAST frame has time `last_frame_t`: its loop
+ * stops at the first current > ceil(last_frame_t) once the input is exhausted (:924-927). */
+int64_t ntscsim_blend_clip_periods(double last_frame_t);
+
+/* gamma16_do_init() :724-732 for gamma_correction = gamma: dec[i] = (unsigned long)(pow(i / 255.0, gamma) * 8192),
+ * enc[i] = (unsigned long)(pow(i / 8192.0, 1.0 / gamma) * 255), host libm.  NTSCSIM_E_PARAM unless gamma > 0. */
+int  ntscsim_blend_tables(double gamma, uint16_t dec[256], uint8_t enc[8193]);
+
+/* Snapshot the blend parameters on a ctx (any ntscsim_params it was created with) and upload the gamma
+ * tables when gamma_correction > 1.  Waits for blend work in flight on the ctx. */
+int  ntscsim_blend_bind(ntscsim_ctx *ctx, const ntscsim_blend_params *p);
+
+typedef struct ntscsim_blend_tap {
+    const void *src_dev;             /* device pointer, BGRA frame of the descriptor's width x height    */
+    int32_t     src_linesize;        /* bytes, >= 4*width, multiple of 4                                 */
+    uint32_t    weight16;            /* :1027-1028                                                       */
+} ntscsim_blend_tap;
+typedef struct ntscsim_blend_desc {
+    void       *dst_dev;             /* device pointer, BGRA frame; bytes of a row behind 4*width are not touched */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                 */
+    int32_t     width, height;
+    int32_t     n_taps;              /* 0: black frame, alpha 0xFF                                        */
+    const ntscsim_blend_tap *taps;   /* host memory, n_taps entries                                      */
+} ntscsim_blend_desc;
+#define NTSCSIM_BLEND_FAST_TAPS 4
+/*
+ * The pixel loops :1032-1081 for `n` output frames, one launch: per channel
+ *   gamma_correction > 1:  out = enc[min(8192, (sum_k dec[src_k] * weight16_k) >> 16)]
+ *   otherwise:             out = min(255, (sum_k src_k * weight16_k) >> 16)
+ * alpha 0xFF.  All frame pointers are DEVICE pointers; `descs` and the tap lists are host memory and are
+ * consumed by the call.  Enqueued on hip_stream (NULL: the ctx's own stream), returns without synchronising.
+ * A call whose descriptors all have at most NTSCSIM_BLEND_FAST_TAPS taps runs k_blend_fast (taps in the
+ * record), any other k_blend_general (tap lists in device memory); the sums are 32-bit while
+ * 8192 * sum(weight16) < 2^32 (255 * sum without gamma) holds for every descriptor and 64-bit otherwise.  Frames whose
+ * pointers and linesizes are all multiples of 16 move as 16-byte vectors; any other frame, and the last
+ * width % 4 pixels of a row, as dwords.  Same bytes either way.  sum(weight16) >= 2^38 is refused
+ * (NTSCSIM_E_ARG; the tool's own clamp255(int) is undefined from 2^39); a destination must not be a source
+ * of the same call.  Requires ntscsim_blend_bind().
+ */
+int  ntscsim_blend_frames_device(ntscsim_ctx *ctx, const ntscsim_blend_desc *descs, int n, void *hip_stream);
+/*
+ * A clip resident in device memory: n_src BGRA frames (src_dev[j], rows of src_linesize bytes, time
+ * frame_t[j]) -> output periods [first, last), period k into dst_dev[k - first].  Runs the planner on the
+ * host from period 0 with the tool's read-ahead (:910: frames are appended while the newest is less than 30
+ * periods ahead) and enqueues the launches on hip_stream; asynchronous like ntscsim_blend_frames_device().
+ */
+int  ntscsim_blend_clip_device(ntscsim_ctx *ctx, const void *const *src_dev, int src_linesize,
+                               const double *frame_t, int n_src, void *const *dst_dev, int dst_linesize,
+                               int width, int height, int64_t first, int64_t last, void *hip_stream);
+/* ntscsim_blend_frames_device() on HOST frames: every pointer of descs / taps is host memory.  Each distinct
+ * source frame (pointer + linesize) is uploaded once however many outputs it feeds; uploads, the launch and
+ * the downloads go through pinned staging of the ctx.  Synchronous.  Same bytes as the device call. */
+int  ntscsim_blend_frames_host(ntscsim_ctx *ctx, const ntscsim_blend_desc *descs, int n);
+
 #ifdef __cplusplus
 }
 #endif
