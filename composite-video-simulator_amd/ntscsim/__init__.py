@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -510,6 +510,112 @@ class FrameBlender:
         rc = self._lib.ntscsim_blend_clip_device(self.sim._h, sp, src.stride(1), tt, n, dp, out.stride(1), w, h,
                                                  int(first), int(last), C.c_void_p(stream))
         self.sim._chk(rc, "ntscsim_blend_clip_device")
+
+    def last_kernels(self):
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
+
+
+class ColorKeyer:
+    """The colorkey stage (ntscsim_key_*): keys layers over a destination that is never cleared, as ffmpeg_colorkey
+    does.  `argv` are the tool's switches, e.g. ("-d", "2", "-i", "bg", "-i", "fg", "-color", "0x00FF00", "-threshhold",
+    "96"): every -i opens a layer (the name is only recorded) and the per-layer switches behind it apply to it.
+    width / height: the frame size (the tool has no -height).  sim: share the context of a FieldSimulator (its outputs
+    can then be keyed on the same stream without leaving device memory); otherwise a context of its own is created.
+    torch is used only for device memory and streams."""
+
+    def __init__(self, argv=(), width=None, height=None, device=0, params=None, sim=None):
+        self.params = params if params is not None else _capi.make_key_params(argv, width=width, height=height)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        self.sim._chk(self._lib.ntscsim_key_bind(self.sim._h, C.byref(self.params)), "ntscsim_key_bind")
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    @property
+    def n_layers(self):
+        return int(self.params.n_layers)
+
+    @property
+    def delay(self):
+        return int(self.params.delay)
+
+    def rand_advance(self, pos, present=None):
+        """ntscsim_key_rand_advance: the position of the rand() stream behind one output frame that starts at `pos`;
+        present[l] false marks layer l as absent in that frame (default: all present)."""
+        v = C.c_uint64(int(pos))
+        pm = None
+        if present is not None:
+            assert len(present) == self.n_layers
+            pm = (C.c_uint8 * max(1, self.n_layers))(*[1 if x else 0 for x in present])
+        rc = self._lib.ntscsim_key_rand_advance(C.byref(self.params), pm, C.byref(v))
+        if rc != _capi.OK:
+            raise NtscsimError(rc, "ntscsim_key_rand_advance")
+        return int(v.value)
+
+    def _descs(self, jobs, ptr, linesize):
+        """jobs: list of (dst, [src or None per layer], rand_pos), frames [H, W, 4] uint8 with contiguous pixels."""
+        arr = (_capi.KeyDesc * max(1, len(jobs)))()
+        keep = []
+        for d, (dst, srcs, pos) in zip(arr, jobs):
+            h, w = dst.shape[0], dst.shape[1]
+            t = (_capi.KeySrc * max(1, len(srcs)))()
+            for k, src in enumerate(srcs):
+                if src is not None:
+                    assert tuple(src.shape) == (h, w, 4)
+                    t[k].src_dev, t[k].src_linesize = ptr(src), linesize(src)
+            keep.append(t)
+            d.dst_dev, d.dst_linesize, d.width, d.height, d.n_layers, d.layers = ptr(dst), linesize(dst), w, h, len(srcs), t
+            d.rand_pos = int(pos)
+        return arr, keep
+
+    def key_frames(self, jobs, stream=None):
+        """ntscsim_key_frames_device: jobs = [(dst, [src or None per layer], rand_pos), ...] of torch uint8 CUDA tensors
+        [H, W, 4] (any row stride); dst is keyed in place.  Enqueues; does not synchronise."""
+        arr, keep = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        rc = self._lib.ntscsim_key_frames_device(self.sim._h, arr, len(jobs), C.c_void_p(stream))
+        self.sim._chk(rc, "ntscsim_key_frames_device")
+
+    def key_frames_host(self, jobs):
+        """ntscsim_key_frames_host: the same on numpy uint8 arrays [H, W, 4].  Synchronous."""
+        arr, keep = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self.sim._chk(self._lib.ntscsim_key_frames_host(self.sim._h, arr, len(jobs)), "ntscsim_key_frames_host")
+
+    def key_clip(self, ring, layers, out, ring_index=0, rand_pos=0, stream=None):
+        """ntscsim_key_clip_device: ring = list of `delay` torch uint8 CUDA frames [H, W, 4] (the destination ring, kept
+        between calls), layers = per layer a list of T frames (None: absent in that frame), out = list of T frames.
+        Frames of one list share a row stride.  Returns (ring_index, rand_pos) behind the last frame, to be handed to
+        the next call.  Enqueues; does not synchronise."""
+        T, nl = len(out), self.n_layers
+        assert len(ring) == self.delay and len(layers) == nl and all(len(lay) == T for lay in layers)
+        rp = (C.c_void_p * max(1, len(ring)))(*[r.data_ptr() for r in ring])
+        sp = (C.c_void_p * max(1, nl * T))(*[(f.data_ptr() if f is not None else None) for lay in layers for f in lay])
+        ls = (C.c_int32 * max(1, nl))()
+        for k, lay in enumerate(layers):
+            strides = set(f.stride(0) for f in lay if f is not None)
+            assert len(strides) <= 1
+            ls[k] = strides.pop() if strides else 4 * int(self.params.width)
+        op = (C.c_void_p * max(1, T))(*[o.data_ptr() for o in out])
+        ri, pos = C.c_int32(int(ring_index)), C.c_uint64(int(rand_pos))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        rc = self._lib.ntscsim_key_clip_device(self.sim._h, rp, ring[0].stride(0) if len(ring) else 0, C.byref(ri), sp, ls, op,
+                                               out[0].stride(0) if T else 4 * int(self.params.width), T, C.byref(pos),
+                                               C.c_void_p(stream))
+        self.sim._chk(rc, "ntscsim_key_clip_device")
+        return int(ri.value), int(pos.value)
+
+    def debug_set_bits_limit(self, nbytes):
+        """ntscsim_key_debug_set_bits_limit: bound on the hit bits of one launch (0: the default)."""
+        self.sim._chk(self._lib.ntscsim_key_debug_set_bits_limit(self.sim._h, int(nbytes)), "ntscsim_key_debug_set_bits_limit")
 
     def last_kernels(self):
         return self.sim.last_kernels()

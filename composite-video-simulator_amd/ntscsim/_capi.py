@@ -49,6 +49,9 @@ EXPORTS = (
     "ntscsim_blend_plan_create", "ntscsim_blend_plan_push", "ntscsim_blend_plan_next", "ntscsim_blend_plan_reset",
     "ntscsim_blend_plan_destroy", "ntscsim_blend_clip_periods", "ntscsim_blend_tables", "ntscsim_blend_bind",
     "ntscsim_blend_frames_device", "ntscsim_blend_clip_device", "ntscsim_blend_frames_host",
+    "ntscsim_key_params_init", "ntscsim_key_params_free", "ntscsim_key_params_add_layer", "ntscsim_key_parse_argv",
+    "ntscsim_key_rand_advance", "ntscsim_key_bind", "ntscsim_key_frames_device", "ntscsim_key_clip_device",
+    "ntscsim_key_frames_host", "ntscsim_key_debug_lane_state", "ntscsim_key_debug_set_bits_limit",
 )
 
 
@@ -237,6 +240,40 @@ class BlendDesc(C.Structure):
 
 
 BLEND_FAST_TAPS = 4
+
+
+class KeyLayer(C.Structure):
+    """struct ntscsim_key_layer -- keep in lock-step with include/ntscsim.h."""
+    _fields_ = [("color", C.c_uint32), ("threshhold", C.c_int32), ("fade", C.c_uint32), ("xdivr", C.c_uint32),
+                ("invert", C.c_int32), ("noisekey", C.c_uint32), ("path", C.c_char_p)]
+
+
+class KeyParams(C.Structure):
+    """struct ntscsim_key_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("tv_standard", C.c_int32),
+                ("delay", C.c_int32), ("use_422_colorspace", C.c_int32), ("n_layers", C.c_int32), ("layers_cap", C.c_int32),
+                ("layers", C.POINTER(KeyLayer)), ("output_path", C.c_char_p)]
+
+    def __del__(self):                      # the layer list is a heap block of the library's
+        try:
+            if _lib is not None and self.layers:
+                _lib.ntscsim_key_params_free(C.byref(self))
+        except Exception:
+            pass
+
+
+class KeySrc(C.Structure):
+    """struct ntscsim_key_src"""
+    _fields_ = [("src_dev", C.c_void_p), ("src_linesize", C.c_int32), ("_pad", C.c_int32)]
+
+
+class KeyDesc(C.Structure):
+    """struct ntscsim_key_desc"""
+    _fields_ = [("dst_dev", C.c_void_p), ("dst_linesize", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("n_layers", C.c_int32), ("layers", C.POINTER(KeySrc)), ("rand_pos", C.c_uint64)]
+
+
+KEY_FAST_LAYERS = 4
 
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
@@ -465,6 +502,30 @@ def lib():
     L.ntscsim_blend_clip_device.restype = C.c_int
     L.ntscsim_blend_frames_host.argtypes = [C.c_void_p, C.POINTER(BlendDesc), C.c_int]
     L.ntscsim_blend_frames_host.restype = C.c_int
+    L.ntscsim_key_params_init.argtypes = [C.POINTER(KeyParams)]
+    L.ntscsim_key_params_init.restype = None
+    L.ntscsim_key_params_free.argtypes = [C.POINTER(KeyParams)]
+    L.ntscsim_key_params_free.restype = None
+    L.ntscsim_key_params_add_layer.argtypes = [C.POINTER(KeyParams), C.c_char_p]
+    L.ntscsim_key_params_add_layer.restype = C.c_int
+    L.ntscsim_key_parse_argv.argtypes = [C.POINTER(KeyParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ntscsim_key_parse_argv.restype = C.c_int
+    L.ntscsim_key_rand_advance.argtypes = [C.POINTER(KeyParams), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
+    L.ntscsim_key_rand_advance.restype = C.c_int
+    L.ntscsim_key_bind.argtypes = [C.c_void_p, C.POINTER(KeyParams)]
+    L.ntscsim_key_bind.restype = C.c_int
+    L.ntscsim_key_frames_device.argtypes = [C.c_void_p, C.POINTER(KeyDesc), C.c_int, C.c_void_p]
+    L.ntscsim_key_frames_device.restype = C.c_int
+    L.ntscsim_key_clip_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int,
+                                          C.c_int, C.POINTER(C.c_uint64), C.c_void_p]
+    L.ntscsim_key_clip_device.restype = C.c_int
+    L.ntscsim_key_frames_host.argtypes = [C.c_void_p, C.POINTER(KeyDesc), C.c_int]
+    L.ntscsim_key_frames_host.restype = C.c_int
+    L.ntscsim_key_debug_lane_state.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.ntscsim_key_debug_lane_state.restype = C.c_int
+    L.ntscsim_key_debug_set_bits_limit.argtypes = [C.c_void_p, C.c_size_t]
+    L.ntscsim_key_debug_set_bits_limit.restype = C.c_int
     _lib = L
     return L
 
@@ -535,4 +596,24 @@ def make_blend_params(flags=(), require_io=False):
     if rc != OK:
         raise NtscsimError(rc, "blend parse_argv(%r)" % (list(flags),))
     p._argv = arr
+    return p
+
+
+def make_key_params(flags=(), require_io=False, width=None, height=None):
+    """ntscsim_key_params from ffmpeg_colorkey's switches (ffmpeg_colorkey.cpp parse_argv :629).  width / height
+    override the frame size after parsing (the tool has no -height).  The returned struct keeps the argv strings
+    alive (the layers' paths and output_path point into them) and frees its layer list when it is collected."""
+    L = lib()
+    p = KeyParams()
+    L.ntscsim_key_params_init(C.byref(p))
+    argv = [b"ffmpeg_colorkey"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    p._argv = arr
+    rc = L.ntscsim_key_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
+    if rc != OK:
+        raise NtscsimError(rc, "key parse_argv(%r)" % (list(flags),))
+    if width is not None:
+        p.width = int(width)
+    if height is not None:
+        p.height = int(height)
     return p

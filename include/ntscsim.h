@@ -935,6 +935,134 @@ int  ntscsim_blend_clip_device(ntscsim_ctx *ctx, const void *const *src_dev, int
  * the downloads go through pinned staging of the ctx.  Synchronous.  Same bytes as the device call. */
 int  ntscsim_blend_frames_host(ntscsim_ctx *ctx, const ntscsim_blend_desc *descs, int n);
 
+/* ---- colorkey: the retro colour keyer behind the simulator (ffmpeg_colorkey.cpp) --------------------
+ * The tool keys its inputs, in order, over a destination frame that is never cleared: a source pixel is
+ * copied when its RGB distance to the key colour passes the threshold, the distance is sampled every
+ * -xd pixels, -noise lets keyed-out pixels through at random (three rand() per pixel from the unseeded
+ * stream) and -f fades what is already there.  The destinations form a ring of -d frames, so output
+ * frame t is keyed onto output frame t - d ("hall of mirrors").  Mapping:
+ *
+ *   InputFile :68, :517-527 + new_input_file() :571-589               | ntscsim_key_layer, ntscsim_key_params_add_layer()
+ *   globals :44-63 + preset_NTSC / _PAL :597-613 + parse_argv() :629-739 | ntscsim_key_params, _init(), _parse_argv()
+ *   the rand() calls of composite_layer() :837-842, :860-861           | ntscsim_key_rand_advance()  (host, no GPU)
+ *   composite_layer() :844-885, all layers of a frame :1119-1146       | ntscsim_key_frames_device() / _frames_host()
+ *   the frame loop over the ring :997-1019, :1118-1171                 | ntscsim_key_clip_device()
+ *
+ * Decoding, scaling (sws_scale), encoding and the audio pass-through stay with the caller.
+ * Frames are BGRA in device memory; the simulator's outputs can be handed over as layers without a copy.
+ */
+typedef struct ntscsim_key_layer {
+    uint32_t color;                  /* :517  0 (black)      -color, 0xRRGGBB; the high byte is ignored (:854-856) */
+    int32_t  threshhold;             /* :518  0              -threshhold (the tool's spelling), compared signed     */
+    uint32_t fade;                   /* :519  0              -f; the factor 256 - fade is unsigned: > 256 wraps     */
+    uint32_t xdivr;                  /* :520  1              -xd; 0 behaves as 1 (:883)                              */
+    int32_t  invert;                 /* :521  false          -inv                                                    */
+    uint32_t noisekey;               /* :527  0              -noise; > 0 draws 3 rand() per pixel                    */
+    const char *path;                /* :516  the -i that opened the layer (points into argv), may be NULL            */
+} ntscsim_key_layer;
+
+typedef struct ntscsim_key_params {
+    uint32_t struct_size;            /* = sizeof(ntscsim_key_params)                                      */
+    int32_t  width, height;          /* :46-47  720 x 480 (preset_NTSC), 720 x 576 (-tvstd pal), -width   */
+    int32_t  tv_standard;            /* 0 NTSC, 1 PAL (-tvstd)                                             */
+    int32_t  delay;                  /* :62  1 (-d, 1..256): frames in the destination ring                */
+    int32_t  use_422_colorspace;     /* :44  false (-422 / -420); recorded, not acted on                   */
+    int32_t  n_layers;               /* inputs so far, in layering order; no upper limit                   */
+    int32_t  layers_cap;             /* allocated entries of `layers`                                      */
+    ntscsim_key_layer *layers;       /* heap block owned by the struct: ntscsim_key_params_free()          */
+    const char *output_path;         /* -o :693-697                                                        */
+} ntscsim_key_params;
+
+void ntscsim_key_params_init(ntscsim_key_params *p);
+/* Releases the layer list (the struct itself is the caller's). */
+void ntscsim_key_params_free(ntscsim_key_params *p);
+/* new_input_file() :571-589: appends a layer that copies the settings of the previous one (defaults :68 for the
+ * first).  Returns its index, or NTSCSIM_E_ARG / NTSCSIM_E_NOMEM. */
+int  ntscsim_key_params_add_layer(ntscsim_key_params *p, const char *path);
+/* Mirror of parse_argv() :629-739: same switch names (any number of leading '-'), every value through strtoul
+ * with base 0 and the tool's casts.  argv[0] is the program name.  A per-layer switch (-f -xd -noise -inv
+ * -threshhold -color) before the first -i makes the tool throw (current_input_file() :562-569): NTSCSIM_E_ARG.
+ * require_io != 0 applies the "No output file / No input files" checks (:729-736).  Otherwise NTSCSIM_OK,
+ * NTSCSIM_E_HELP (-h / -help) or NTSCSIM_E_FLAG (the tool's "return 1"; -d outside 1..256, -width < 32). */
+int  ntscsim_key_parse_argv(ntscsim_key_params *p, int argc, const char *const *argv, int require_io);
+/*
+ * The tool's rand() stream is one serial stream; position n is the state after n calls (ntscsim_rng_draw).
+ * One output frame visits the layers in list order; a layer that is present and has noisekey > 0 consumes
+ * exactly 3 * width * height draws, in raster order, at every pixel whatever its xdivr; an absent layer (no
+ * source frame, the early return :837-842) or a layer with noisekey == 0 consumes none.  This advances *pos
+ * over one frame: present[l] != 0 marks layer l as present, present == NULL means all of them.  Call it once
+ * per frame to chain the positions handed to ntscsim_key_frames_device().
+ */
+int  ntscsim_key_rand_advance(const ntscsim_key_params *p, const uint8_t *present, uint64_t *pos);
+
+/* Snapshot the key parameters and the layer list on a ctx (any ntscsim_params it was created with).  Waits for
+ * key work in flight on the ctx.  NTSCSIM_E_PARAM for delay outside 1..256, NTSCSIM_E_SIZE for a frame size
+ * below 1 x 1, above 65536 in either direction or of 2^31 pixels and more. */
+int  ntscsim_key_bind(ntscsim_ctx *ctx, const ntscsim_key_params *p);
+
+typedef struct ntscsim_key_src {
+    const void *src_dev;             /* device pointer, BGRA frame; NULL: the layer is absent in this frame */
+    int32_t     src_linesize;        /* bytes, >= 4*width, multiple of 4                                    */
+    int32_t     _pad;
+} ntscsim_key_src;
+typedef struct ntscsim_key_desc {
+    void       *dst_dev;             /* device pointer, BGRA frame, read and written in place; bytes of a row behind 4*width are not touched */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                    */
+    int32_t     width, height;       /* must be the bound params'                                           */
+    int32_t     n_layers;            /* must be the bound params'                                           */
+    const ntscsim_key_src *layers;   /* host memory, n_layers entries, list order                           */
+    uint64_t    rand_pos;            /* position of the frame's first draw                                  */
+} ntscsim_key_desc;
+#define NTSCSIM_KEY_FAST_LAYERS 4
+/*
+ * composite_layer() :844-885 for every layer of `n` output frames.  Per pixel and layer, in uint32_t / int
+ * arithmetic as the tool has it: the distance d = |dR| + |dG| + |dB| to the key colour is taken from the source
+ * pixel where the counter xdivc is 0 (the start of a row and every xdivr pixels) and held between; a noise hit
+ * ((r1 * r2 * r3) % 20001 < noisekey on three consecutive draws) sets d = 0xFFFF, which is held likewise; the
+ * destination is faded when fade != 0; then all four bytes of the source pixel are copied when d >= threshhold
+ * (d < threshhold with invert).  All frame pointers are DEVICE pointers; `descs` and the layer lists are host
+ * memory and are consumed by the call.  Enqueued on hip_stream (NULL: the ctx's own stream), returns without
+ * synchronising.  Descriptors take effect in order: a later one that names a destination (or reads a frame) an
+ * earlier one wrote sees the earlier result.
+ * Kernels: k_key_fast<NOISE> (up to NTSCSIM_KEY_FAST_LAYERS layers, in the record) or k_key_general<NOISE> (layer
+ * list in device memory); NOISE only when a present layer has noisekey > 0, and then k_key_draw runs in front and
+ * leaves one hit bit per pixel.  Frames whose pointers and linesizes are all multiples of 16 move as 16-byte
+ * vectors; any other frame, and the last width % 4 pixels of a row, as dwords.  Same bytes either way.
+ * NTSCSIM_E_SIZE: a size other than the bound params', a linesize below 4*width or not a multiple of 4.
+ * NTSCSIM_E_ARG: a source that overlaps the destination of its descriptor, a NULL destination, no
+ * ntscsim_key_bind() before.
+ */
+int  ntscsim_key_frames_device(ntscsim_ctx *ctx, const ntscsim_key_desc *descs, int n, void *hip_stream);
+/*
+ * The tool's frame loop :1118-1171 for T output frames of a clip resident in device memory.  ring_dev[0..delay)
+ * are the destination frames (the tool zeroes them once, :1013-1016; the caller does that before the first
+ * call), *ring_index the slot of the first frame (the tool starts at 0).  Frame t takes layer l from
+ * src_dev[l * T + t] (NULL: absent), rows of src_linesize[l] bytes, is keyed onto ring slot
+ * (*ring_index + t) % delay and delivered to out_dev[t].  *rand_pos is the position of the first draw.  After
+ * the call the ring holds what the tool's ring holds, and *ring_index and *rand_pos are those of frame T: a
+ * following call continues the clip.  One launch of k_key_clip_fast<NOISE, layers> (1 to 4 layers) / k_key_clip_general<NOISE> walks the
+ * min(delay, T) independent chains through all of their frames with the destination pixel in registers: it is
+ * read from the ring once, written to out_dev[t] at every step and to the ring at the end; the fast form keeps the source
+ * loads of a chain's next two frames in flight.  Asynchronous like
+ * ntscsim_key_frames_device(); ring, sources and outputs must not overlap each other (NTSCSIM_E_ARG).
+ */
+int  ntscsim_key_clip_device(ntscsim_ctx *ctx, void *const *ring_dev, int ring_linesize, int32_t *ring_index,
+                             const void *const *src_dev, const int32_t *src_linesize, void *const *out_dev,
+                             int out_linesize, int T, uint64_t *rand_pos, void *hip_stream);
+/* ntscsim_key_frames_device() on HOST frames: every pointer of descs / layers is host memory.  Each distinct
+ * frame (pointer + linesize) is uploaded once, destinations are downloaded after the last descriptor; all of it
+ * goes through pinned staging of the ctx.  Synchronous.  Same bytes as the device call.  A destination must be disjoint
+ * from every other frame of the call that is not the very same (pointer, linesize): NTSCSIM_E_ARG otherwise. */
+int  ntscsim_key_frames_host(ntscsim_ctx *ctx, const ntscsim_key_desc *descs, int n);
+/* Debug tap: the bound on the hit bits of one launch, in bytes (default 128 MiB; 0 restores it).  A clip or frames call
+ * whose noisy layers need more is cut into several launches of at least one frame each -- same bytes; the tests set a
+ * small bound to reach that path with small frames.  Requires ntscsim_key_bind(); kept across later binds. */
+int  ntscsim_key_debug_set_bits_limit(ntscsim_ctx *ctx, size_t bytes);
+/* Debug tap (host only, no GPU): the 31-word rand() window from which lane `lane` of k_key_draw starts for a
+ * layer whose first draw is at job_pos, computed as the launcher computes it (per-lane polynomial applied to
+ * the layer's window).  It must equal the window at job_pos + 768 * lane. */
+int  ntscsim_key_debug_lane_state(int width, int height, uint64_t job_pos, uint32_t lane, uint32_t out[31]);
+
 #ifdef __cplusplus
 }
 #endif
