@@ -28,6 +28,7 @@
 #include "ntsc_float.hpp"       // NTSCSIM_MODE_FLOAT: its kernels are a translation unit of their own
 #include "ntsc_blend.hpp"       // the frameblend stage (ntscsim_blend_*): likewise, csrc/ntsc_blend.hip
 #include "ntsc_key.hpp"         // the colorkey stage (ntscsim_key_*): likewise, csrc/ntsc_key.hip
+#include "ntsc_avg.hpp"         // the average_delay stage (ntscsim_avg_*): likewise, csrc/ntsc_avg.hip
 
 using namespace ntscsim;
 
@@ -221,6 +222,7 @@ struct ntscsim_ctx {
     unsigned *pipe_fault = nullptr;  // pinned word the role kernels raise when a hand-off timed out (ntsc_pipe.hip); checked behind launches
     ntscsim::BlendState *blend = nullptr;   // ntscsim_blend_bind(): state of the frameblend stage (csrc/ntsc_blend.hip)
     ntscsim::KeyState *key = nullptr;       // ntscsim_key_bind(): state of the colorkey stage (csrc/ntsc_key.hip)
+    ntscsim::AvgState *avg = nullptr;       // ntscsim_avg_bind(): state of the average_delay stage (csrc/ntsc_avg.hip)
 };
 ntscsim::CtxBlendView ntscsim::ctx_blend_view(ntscsim_ctx *c)
 {
@@ -229,6 +231,10 @@ ntscsim::CtxBlendView ntscsim::ctx_blend_view(ntscsim_ctx *c)
 ntscsim::CtxKeyView ntscsim::ctx_key_view(ntscsim_ctx *c)
 {
     return CtxKeyView{c->device, c->stream, &c->err, &c->kernels, &c->key};
+}
+ntscsim::CtxAvgView ntscsim::ctx_avg_view(ntscsim_ctx *c)
+{
+    return CtxAvgView{c->device, c->stream, &c->err, &c->kernels, &c->avg};
 }
 static void declared_pins_destroy(ntscsim_ctx *c);
 static uint8_t *pinned_device_ptr(ntscsim_ctx *c, const void *p, size_t span);      // ntscsim_submit.hip
@@ -479,6 +485,7 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     declared_pins_destroy(c);
     if (c->blend) { ntscsim::blend_state_destroy(c->blend); c->blend = nullptr; }
     if (c->key) { ntscsim::key_state_destroy(c->key); c->key = nullptr; }
+    if (c->avg) { ntscsim::avg_state_destroy(c->avg); c->avg = nullptr; }
     for (Geometry *e : c->geoms) {
         e->lskip.release(); e->pskip.release(); e->jrow.release(); e->sstart.release(); e->jwarm.release();
         delete e;

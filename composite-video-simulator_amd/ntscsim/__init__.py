@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -616,6 +616,95 @@ class ColorKeyer:
     def debug_set_bits_limit(self, nbytes):
         """ntscsim_key_debug_set_bits_limit: bound on the hit bits of one launch (0: the default)."""
         self.sim._chk(self._lib.ntscsim_key_debug_set_bits_limit(self.sim._h, int(nbytes)), "ntscsim_key_debug_set_bits_limit")
+
+    def last_kernels(self):
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
+
+
+class FrameAverager:
+    """The average_delay stage (ntscsim_avg_*): averages layers into a destination that is never cleared, as
+    ffmpeg_average_delay does.  `argv` are the tool's switches, e.g. ("-d", "2", "-i", "a", "-n", "64"): every -i opens a
+    layer (the name is only recorded) and -n behind it sets its level (256 = all new, 0 = all old).  width / height:
+    the frame size (the tool has no -height).  sim: share the context of a FieldSimulator (its outputs can then be
+    averaged on the same stream without leaving device memory); otherwise a context of its own is created.  torch is
+    used only for device memory and streams."""
+
+    def __init__(self, argv=(), width=None, height=None, device=0, params=None, sim=None):
+        self.params = params if params is not None else _capi.make_avg_params(argv, width=width, height=height)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        self.sim._chk(self._lib.ntscsim_avg_bind(self.sim._h, C.byref(self.params)), "ntscsim_avg_bind")
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    @property
+    def n_layers(self):
+        return int(self.params.n_layers)
+
+    @property
+    def delay(self):
+        return int(self.params.delay)
+
+    def _descs(self, jobs, ptr, linesize):
+        """jobs: list of (dst, [src or None per layer], field), frames [H, W, 4] uint8 with contiguous pixels."""
+        arr = (_capi.AvgDesc * max(1, len(jobs)))()
+        keep = []
+        for d, (dst, srcs, field) in zip(arr, jobs):
+            h, w = dst.shape[0], dst.shape[1]
+            t = (_capi.AvgSrc * max(1, len(srcs)))()
+            for k, src in enumerate(srcs):
+                if src is not None:
+                    assert tuple(src.shape) == (h, w, 4)
+                    t[k].src_dev, t[k].src_linesize = ptr(src), linesize(src)
+            keep.append(t)
+            d.dst_dev, d.dst_linesize, d.width, d.height, d.n_layers, d.layers = ptr(dst), linesize(dst), w, h, len(srcs), t
+            d.field = int(field)
+        return arr, keep
+
+    def average_frames(self, jobs, stream=None):
+        """ntscsim_avg_frames_device: jobs = [(dst, [src or None per layer], field), ...] of torch uint8 CUDA tensors
+        [H, W, 4] (any row stride); dst is averaged in place.  Enqueues; does not synchronise."""
+        arr, keep = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        rc = self._lib.ntscsim_avg_frames_device(self.sim._h, arr, len(jobs), C.c_void_p(stream))
+        self.sim._chk(rc, "ntscsim_avg_frames_device")
+
+    def average_frames_host(self, jobs):
+        """ntscsim_avg_frames_host: the same on numpy uint8 arrays [H, W, 4].  Synchronous."""
+        arr, keep = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self.sim._chk(self._lib.ntscsim_avg_frames_host(self.sim._h, arr, len(jobs)), "ntscsim_avg_frames_host")
+
+    def average_clip(self, ring, layers, out, ring_index=0, field=0, stream=None):
+        """ntscsim_avg_clip_device: ring = list of `delay` torch uint8 CUDA frames [H, W, 4] (the destination ring, kept
+        between calls), layers = per layer a list of T frames (None: absent in that frame), out = list of T frames.
+        Frames of one list share a row stride.  Returns (ring_index, field) behind the last frame, to be handed to the
+        next call.  Enqueues; does not synchronise."""
+        T, nl = len(out), self.n_layers
+        assert len(ring) == self.delay and len(layers) == nl and all(len(lay) == T for lay in layers)
+        rp = (C.c_void_p * max(1, len(ring)))(*[r.data_ptr() for r in ring])
+        sp = (C.c_void_p * max(1, nl * T))(*[(f.data_ptr() if f is not None else None) for lay in layers for f in lay])
+        ls = (C.c_int32 * max(1, nl))()
+        for k, lay in enumerate(layers):
+            strides = set(f.stride(0) for f in lay if f is not None)
+            assert len(strides) <= 1
+            ls[k] = strides.pop() if strides else 4 * int(self.params.width)
+        op = (C.c_void_p * max(1, T))(*[o.data_ptr() for o in out])
+        ri, fld = C.c_int32(int(ring_index)), C.c_uint64(int(field))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        rc = self._lib.ntscsim_avg_clip_device(self.sim._h, rp, ring[0].stride(0) if len(ring) else 0, C.byref(ri), sp, ls, op,
+                                               out[0].stride(0) if T else 4 * int(self.params.width), T, C.byref(fld),
+                                               C.c_void_p(stream))
+        self.sim._chk(rc, "ntscsim_avg_clip_device")
+        return int(ri.value), int(fld.value)
 
     def last_kernels(self):
         return self.sim.last_kernels()

@@ -52,6 +52,8 @@ EXPORTS = (
     "ntscsim_key_params_init", "ntscsim_key_params_free", "ntscsim_key_params_add_layer", "ntscsim_key_parse_argv",
     "ntscsim_key_rand_advance", "ntscsim_key_bind", "ntscsim_key_frames_device", "ntscsim_key_clip_device",
     "ntscsim_key_frames_host", "ntscsim_key_debug_lane_state", "ntscsim_key_debug_set_bits_limit",
+    "ntscsim_avg_params_init", "ntscsim_avg_params_free", "ntscsim_avg_params_add_layer", "ntscsim_avg_parse_argv",
+    "ntscsim_avg_bind", "ntscsim_avg_frames_device", "ntscsim_avg_clip_device", "ntscsim_avg_frames_host",
 )
 
 
@@ -274,6 +276,39 @@ class KeyDesc(C.Structure):
 
 
 KEY_FAST_LAYERS = 4
+
+
+class AvgLayer(C.Structure):
+    """struct ntscsim_avg_layer -- keep in lock-step with include/ntscsim.h."""
+    _fields_ = [("newlevel", C.c_int32), ("path", C.c_char_p)]
+
+
+class AvgParams(C.Structure):
+    """struct ntscsim_avg_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("tv_standard", C.c_int32),
+                ("delay", C.c_int32), ("use_422_colorspace", C.c_int32), ("n_layers", C.c_int32), ("layers_cap", C.c_int32),
+                ("layers", C.POINTER(AvgLayer)), ("output_path", C.c_char_p)]
+
+    def __del__(self):                      # the layer list is a heap block of the library's
+        try:
+            if _lib is not None and self.layers:
+                _lib.ntscsim_avg_params_free(C.byref(self))
+        except Exception:
+            pass
+
+
+class AvgSrc(C.Structure):
+    """struct ntscsim_avg_src"""
+    _fields_ = [("src_dev", C.c_void_p), ("src_linesize", C.c_int32), ("_pad", C.c_int32)]
+
+
+class AvgDesc(C.Structure):
+    """struct ntscsim_avg_desc"""
+    _fields_ = [("dst_dev", C.c_void_p), ("dst_linesize", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("n_layers", C.c_int32), ("layers", C.POINTER(AvgSrc)), ("field", C.c_uint64)]
+
+
+AVG_FAST_LAYERS = 4
 
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
@@ -526,6 +561,24 @@ def lib():
     L.ntscsim_key_debug_lane_state.restype = C.c_int
     L.ntscsim_key_debug_set_bits_limit.argtypes = [C.c_void_p, C.c_size_t]
     L.ntscsim_key_debug_set_bits_limit.restype = C.c_int
+    L.ntscsim_avg_params_init.argtypes = [C.POINTER(AvgParams)]
+    L.ntscsim_avg_params_init.restype = None
+    L.ntscsim_avg_params_free.argtypes = [C.POINTER(AvgParams)]
+    L.ntscsim_avg_params_free.restype = None
+    L.ntscsim_avg_params_add_layer.argtypes = [C.POINTER(AvgParams), C.c_char_p]
+    L.ntscsim_avg_params_add_layer.restype = C.c_int
+    L.ntscsim_avg_parse_argv.argtypes = [C.POINTER(AvgParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ntscsim_avg_parse_argv.restype = C.c_int
+    L.ntscsim_avg_bind.argtypes = [C.c_void_p, C.POINTER(AvgParams)]
+    L.ntscsim_avg_bind.restype = C.c_int
+    L.ntscsim_avg_frames_device.argtypes = [C.c_void_p, C.POINTER(AvgDesc), C.c_int, C.c_void_p]
+    L.ntscsim_avg_frames_device.restype = C.c_int
+    L.ntscsim_avg_clip_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int,
+                                          C.c_int, C.POINTER(C.c_uint64), C.c_void_p]
+    L.ntscsim_avg_clip_device.restype = C.c_int
+    L.ntscsim_avg_frames_host.argtypes = [C.c_void_p, C.POINTER(AvgDesc), C.c_int]
+    L.ntscsim_avg_frames_host.restype = C.c_int
     _lib = L
     return L
 
@@ -612,6 +665,26 @@ def make_key_params(flags=(), require_io=False, width=None, height=None):
     rc = L.ntscsim_key_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
     if rc != OK:
         raise NtscsimError(rc, "key parse_argv(%r)" % (list(flags),))
+    if width is not None:
+        p.width = int(width)
+    if height is not None:
+        p.height = int(height)
+    return p
+
+
+def make_avg_params(flags=(), require_io=False, width=None, height=None):
+    """ntscsim_avg_params from ffmpeg_average_delay's switches (ffmpeg_average_delay.cpp parse_argv :623).  width /
+    height override the frame size after parsing (the tool has no -height).  The returned struct keeps the argv strings
+    alive (the layers' paths and output_path point into them) and frees its layer list when it is collected."""
+    L = lib()
+    p = AvgParams()
+    L.ntscsim_avg_params_init(C.byref(p))
+    argv = [b"ffmpeg_average_delay"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    p._argv = arr
+    rc = L.ntscsim_avg_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
+    if rc != OK:
+        raise NtscsimError(rc, "avg parse_argv(%r)" % (list(flags),))
     if width is not None:
         p.width = int(width)
     if height is not None:

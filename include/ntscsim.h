@@ -1063,6 +1063,112 @@ int  ntscsim_key_debug_set_bits_limit(ntscsim_ctx *ctx, size_t bytes);
  * the layer's window).  It must equal the window at job_pos + 768 * lane. */
 int  ntscsim_key_debug_lane_state(int width, int height, uint64_t job_pos, uint32_t lane, uint32_t out[31]);
 
+/* ---- average_delay: the frame-averaging delay line behind the simulator (ffmpeg_average_delay.cpp) ----
+ * The tool averages its inputs, in order, into a destination frame that is never cleared: every channel of
+ * a pixel becomes (source * newlevel + destination * (256 - newlevel) + dither) >> 8, with a 2 x 2 ordered
+ * dither that moves with the frame number.  The destinations form a ring of -d frames, so output frame t
+ * is an average of the new frame and output frame t - d (camera-tube lag, feedback trails).  Mapping:
+ *
+ *   InputFile :71-96 + new_input_file() :571-589                       | ntscsim_avg_layer, ntscsim_avg_params_add_layer()
+ *   globals :44-68 + preset_NTSC / _PAL :597-613 + parse_argv() :623-708 | ntscsim_avg_params, _init(), _parse_argv()
+ *   composite_layer() :801-837, all layers of a frame                   | ntscsim_avg_frames_device() / _frames_host()
+ *   the frame loop over the ring :948-970, :1069-1122                   | ntscsim_avg_clip_device()
+ *
+ * Decoding, scaling (sws_scale), encoding and the audio pass-through stay with the caller.
+ * Frames are BGRA in device memory; the simulator's outputs can be handed over as layers without a copy.
+ */
+typedef struct ntscsim_avg_layer {
+    int32_t  newlevel;               /* :73  128             -n ("256=100% 0=0%"); an int, any value: see below   */
+    const char *path;                /* the -i that opened the layer (points into argv), may be NULL                */
+} ntscsim_avg_layer;
+
+typedef struct ntscsim_avg_params {
+    uint32_t struct_size;            /* = sizeof(ntscsim_avg_params)                                      */
+    int32_t  width, height;          /* 720 x 480 (preset_NTSC), 720 x 576 (-tvstd pal), -width           */
+    int32_t  tv_standard;            /* 0 NTSC, 1 PAL (-tvstd)                                             */
+    int32_t  delay;                  /* :67  1 (-d, 1..256): frames in the destination ring                */
+    int32_t  use_422_colorspace;     /* false (-422 / -420); recorded, not acted on                        */
+    int32_t  n_layers;               /* inputs so far, in layering order; no upper limit                   */
+    int32_t  layers_cap;             /* allocated entries of `layers`                                      */
+    ntscsim_avg_layer *layers;       /* heap block owned by the struct: ntscsim_avg_params_free()          */
+    const char *output_path;         /* -o :662-666                                                        */
+} ntscsim_avg_params;
+
+void ntscsim_avg_params_init(ntscsim_avg_params *p);
+/* Releases the layer list (the struct itself is the caller's). */
+void ntscsim_avg_params_free(ntscsim_avg_params *p);
+/* new_input_file() :571-589: appends a layer that copies the newlevel of the previous one (128, :73, for the
+ * first).  Returns its index, or NTSCSIM_E_ARG / NTSCSIM_E_NOMEM. */
+int  ntscsim_avg_params_add_layer(ntscsim_avg_params *p, const char *path);
+/* Mirror of parse_argv() :623-708: -i -o -d -n -width -422 -420 -tvstd pal|ntsc, -h / -help (any number of
+ * leading '-'), every value through strtoul with base 0 and the tool's casts: -n becomes an int (so "-1" is -1
+ * and "0x100" is 256).  argv[0] is the program name.  -n before the first -i makes the tool throw
+ * (current_input_file() :562-569): NTSCSIM_E_ARG.  require_io != 0 applies the "No output file / No input
+ * files" checks (:698-705).  Otherwise NTSCSIM_OK, NTSCSIM_E_HELP (-h / -help) or NTSCSIM_E_FLAG (the tool's
+ * "return 1"; -d outside 1..256, -width < 32). */
+int  ntscsim_avg_parse_argv(ntscsim_avg_params *p, int argc, const char *const *argv, int require_io);
+
+/* Snapshot the parameters and the layer list on a ctx (any ntscsim_params it was created with).  Waits for
+ * average work in flight on the ctx.  NTSCSIM_E_PARAM for delay outside 1..256, NTSCSIM_E_SIZE for a frame size
+ * below 1 x 1, above 65536 in either direction or of 2^31 pixels and more. */
+int  ntscsim_avg_bind(ntscsim_ctx *ctx, const ntscsim_avg_params *p);
+
+typedef struct ntscsim_avg_src {
+    const void *src_dev;             /* device pointer, BGRA frame; NULL: the layer is absent in this frame (:808) */
+    int32_t     src_linesize;        /* bytes, >= 4*width, multiple of 4                                    */
+    int32_t     _pad;
+} ntscsim_avg_src;
+typedef struct ntscsim_avg_desc {
+    void       *dst_dev;             /* device pointer, BGRA frame, read and written in place; bytes of a row behind 4*width are not touched */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                    */
+    int32_t     width, height;       /* must be the bound params' (the tool skips a layer of another size, :812-813) */
+    int32_t     n_layers;            /* must be the bound params'                                           */
+    const ntscsim_avg_src *layers;   /* host memory, n_layers entries, list order                           */
+    uint64_t    field;               /* the `field` argument of composite_layer(): the tool's frame counter `current` */
+} ntscsim_avg_desc;
+#define NTSCSIM_AVG_FAST_LAYERS 4
+/*
+ * composite_layer() :801-837 for every layer of `n` output frames.  Per pixel (x, y) and present layer, in
+ * unsigned 32-bit arithmetic as the tool has it, with n = (uint32_t)newlevel, s / d the source / destination
+ * pixel and dither = ((((x ^ y) + field / delay) & 3) * 255) / 3:
+ *     c' = (s_c * n + d_c * (256 - n) + dither) >> 8   for c = R, G, B;     d = (R' << 16) + (G' << 8) + B'
+ * For newlevel in 0..256 every channel stays below 256 and the top byte becomes 0; for any other value the
+ * factors wrap modulo 2^32, the channels carry into each other and into the top byte, and those are the bytes
+ * returned.  An absent layer leaves the destination untouched, top byte included.  All layers of a frame share
+ * its dither.  All frame pointers are DEVICE pointers; `descs` and the layer lists are host memory and are
+ * consumed by the call.  Enqueued on hip_stream (NULL: the ctx's own stream), returns without synchronising.
+ * Descriptors take effect in order: a later one that names a destination (or reads a frame) an earlier one
+ * wrote sees the earlier result.  Sources are never written.
+ * Kernels: k_avg_fast (up to NTSCSIM_AVG_FAST_LAYERS layers, in the record) or k_avg_general (layer list in
+ * device memory).  Frames whose pointers and linesizes are all multiples of 16 move as 16-byte vectors; any
+ * other frame, and the last width % 4 pixels of a row, as dwords.  Same bytes either way.
+ * NTSCSIM_E_SIZE: a size or layer count other than the bound params', a linesize below 4*width or not a
+ * multiple of 4.  NTSCSIM_E_ARG: a source that overlaps the destination of its descriptor, a NULL destination,
+ * no ntscsim_avg_bind() before.
+ */
+int  ntscsim_avg_frames_device(ntscsim_ctx *ctx, const ntscsim_avg_desc *descs, int n, void *hip_stream);
+/*
+ * The tool's frame loop :1069-1122 for T output frames of a clip resident in device memory.  ring_dev[0..delay)
+ * are the destination frames (the tool zeroes them once, :948-970; the caller does that before the first
+ * call), *ring_index the slot of the first frame (the tool starts at 0), *field its frame number (the tool
+ * starts at 0).  Frame t takes layer l from src_dev[l * T + t] (NULL: absent), rows of src_linesize[l] bytes,
+ * is averaged onto ring slot (*ring_index + t) % delay with field *field + t and delivered to out_dev[t].
+ * After the call the ring holds what the tool's ring holds, and *ring_index and *field are those of frame T: a
+ * following call continues the clip.  One launch of k_avg_clip_fast<layers> (1 to 4 layers) /
+ * k_avg_clip_general walks the min(delay, T) independent chains through all of their frames with the
+ * destination pixel in registers: it is read from the ring once, written to out_dev[t] at every step and to
+ * the ring at the end; the fast form keeps the source loads of a chain's next frames in flight.  Asynchronous
+ * like ntscsim_avg_frames_device(); ring, sources and outputs must not overlap each other (NTSCSIM_E_ARG).
+ */
+int  ntscsim_avg_clip_device(ntscsim_ctx *ctx, void *const *ring_dev, int ring_linesize, int32_t *ring_index,
+                             const void *const *src_dev, const int32_t *src_linesize, void *const *out_dev,
+                             int out_linesize, int T, uint64_t *field, void *hip_stream);
+/* ntscsim_avg_frames_device() on HOST frames: every pointer of descs / layers is host memory.  Each distinct
+ * frame (pointer + linesize) is uploaded once, destinations are downloaded after the last descriptor; all of it
+ * goes through pinned staging of the ctx.  Synchronous.  Same bytes as the device call.  A destination must be disjoint
+ * from every other frame of the call that is not the very same (pointer, linesize): NTSCSIM_E_ARG otherwise. */
+int  ntscsim_avg_frames_host(ntscsim_ctx *ctx, const ntscsim_avg_desc *descs, int n);
+
 #ifdef __cplusplus
 }
 #endif
