@@ -11,14 +11,13 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <map>
 #include <new>
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "ntscsim.h"
-#include "ntsc_avg.hpp"
+#include "ntsc_layer_frames.hpp"
+#include "ntsc_px4.hpp"
 
 namespace ntscsim {
 
@@ -55,40 +54,6 @@ struct AvgClip {                         // the clip forms: the ring behind the 
     uint32_t vec;                        // every pointer and linesize of the clip is a multiple of 16
 };
 
-// device memory is reached through the global address space: a pointer that comes out of a record would otherwise be
-// accessed with flat instructions, which count against the scalar-load counter too, so every record read would wait
-// for the vector loads in flight
-#define AVG_GLOBAL __attribute__((address_space(1)))
-ADEV uint32_t gld(const void *p) { return *(const AVG_GLOBAL uint32_t *)p; }
-typedef uint32_t avg_u4 __attribute__((ext_vector_type(4)));
-ADEV avg_u4 gld4(const void *p) { return *(const AVG_GLOBAL avg_u4 *)p; }
-ADEV void gst(void *p, uint32_t v) { *(AVG_GLOBAL uint32_t *)p = v; }
-ADEV void gst4(void *p, avg_u4 v) { *(AVG_GLOBAL avg_u4 *)p = v; }
-
-template <bool VEC>
-ADEV void avg_load(uint32_t (&v)[4], const uint8_t *__restrict__ p, int npx)
-{
-    if (VEC) {
-        const avg_u4 q = gld4(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < npx) v[k] = gld(p + 4 * k);
-    }
-}
-
-template <bool VEC>
-ADEV void avg_store(uint8_t *__restrict__ p, const uint32_t (&v)[4], int npx)
-{
-    if (VEC) gst4(p, avg_u4{v[0], v[1], v[2], v[3]});
-    else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < npx) gst(p + 4 * k, v[k]);
-    }
-}
-
 // ((((x ^ y) + efield) & 3) * 255) / 3  :821 -- 0, 85, 170 or 255; xy = x ^ y
 ADEV uint32_t avg_dither(uint32_t xy, uint32_t e) { return ((xy + e) & 3u) * 85u; }
 
@@ -124,16 +89,16 @@ ADEV void avg_item_fast(const AvgRec &r, const AvgCfg &cfg, int nl, int y, int x
     // independent of each other and of the destination
 #pragma unroll
     for (int k = 0; k < AVG_FAST; k++) row[k] = k < nl && r.src[k] ? r.src[k] + (size_t)y * (size_t)r.src_ls[k] + (size_t)x * 4u : nullptr;
-    avg_load<VEC>(d, dp, npx);
+    px4_load<VEC>(d, dp, npx);
 #pragma unroll
     for (int k = 0; k < AVG_FAST; k++)
-        if (row[k]) avg_load<VEC>(s[k], row[k], npx);
+        if (row[k]) px4_load<VEC>(s[k], row[k], npx);
 #pragma unroll
     for (int p = 0; p < 4; p++) dth[p] = avg_dither((uint32_t)(x + p) ^ (uint32_t)y, r.e);
 #pragma unroll
     for (int k = 0; k < AVG_FAST; k++)
         if (row[k]) avg_layer(d, s[k], npx, cfg.n[k], dth);
-    avg_store<VEC>(dp, d, npx);
+    px4_store<VEC>(dp, d, npx);
 }
 
 __global__ __launch_bounds__(AVG_THREADS) void k_avg_fast(const AvgRec *__restrict__ recs, AvgCfg cfg, int W, int H, int nl)
@@ -158,7 +123,7 @@ ADEV void avg_apply_general(uint32_t (&d)[4], const AvgRec &r, const uint32_t *_
         const AvgLayerDev L = r.layers[k];
         if (!L.src) continue;
         uint32_t s[4];
-        avg_load<VEC>(s, L.src + (size_t)y * (size_t)L.ls + (size_t)x * 4u, npx);
+        px4_load<VEC>(s, L.src + (size_t)y * (size_t)L.ls + (size_t)x * 4u, npx);
         avg_layer(d, s, npx, gcfg[k], dth);
     }
 }
@@ -168,9 +133,9 @@ ADEV void avg_item_general(const AvgRec &r, const uint32_t *__restrict__ gcfg, i
 {
     uint8_t *dp = r.dst + (size_t)y * (size_t)r.dst_ls + (size_t)x * 4u;
     uint32_t d[4];
-    avg_load<VEC>(d, dp, npx);
+    px4_load<VEC>(d, dp, npx);
     avg_apply_general<VEC>(d, r, gcfg, nl, r.e, y, x, npx);
-    avg_store<VEC>(dp, d, npx);
+    px4_store<VEC>(dp, d, npx);
 }
 
 __global__ __launch_bounds__(AVG_THREADS) void k_avg_general(const AvgRec *__restrict__ recs, const uint32_t *__restrict__ gcfg,
@@ -227,7 +192,7 @@ ADEV void avg_issue(uint32_t (&s)[NL][4], uint8_t *&dst, uint32_t &present, cons
         m |= there ? 1u << k : 0u;
     }
 #pragma unroll
-    for (int k = 0; k < NL; k++) avg_load<VEC>(s[k], p[k], VEC ? 4 : 1);
+    for (int k = 0; k < NL; k++) px4_load<VEC>(s[k], p[k], VEC ? 4 : 1);
     dst = f.dst;
     present = m;
 }
@@ -248,7 +213,7 @@ ADEV void avg_chain_fast(const AvgRec *__restrict__ recs, const AvgClip &clip, u
 #pragma unroll
     for (int p = 0; p < 4; p++) xy[p] = (uint32_t)(x + p) ^ (uint32_t)y;
     uint32_t e = recs[chain].e;
-    avg_load<VEC>(d, rp, npx);
+    px4_load<VEC>(d, rp, npx);
     // the loads are kept in frame order: the wait in front of a step counts back from the youngest load, and the loop's
     // waits have to hold for the prologue's loads too
 #pragma unroll
@@ -284,13 +249,13 @@ ADEV void avg_chain_fast(const AvgRec *__restrict__ recs, const AvgClip &clip, u
 #pragma unroll
                 for (int p = 0; p < 4; p++) d[p] = take ? v[p] : d[p];
             }
-            avg_store<VEC>(tj < T ? dst[j] + ooff : rp, d, npx);
+            px4_store<VEC>(tj < T ? dst[j] + ooff : rp, d, npx);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
     round(chain);
     for (int t = chain + BUFS * dl; t < T; t += BUFS * dl) round(t);
-    avg_store<VEC>(rp, d, npx);
+    px4_store<VEC>(rp, d, npx);
 }
 
 // <NL>: number of layers, 1 .. NTSCSIM_AVG_FAST_LAYERS
@@ -327,13 +292,13 @@ ADEV void avg_chain_general(const AvgRec *__restrict__ recs, const AvgClip &clip
     const size_t ooff = (size_t)y * (size_t)clip.out_ls + (size_t)x * 4u;
     uint32_t d[4];
     uint32_t e = recs[chain].e;
-    avg_load<VEC>(d, rp, npx);
+    px4_load<VEC>(d, rp, npx);
     for (int t = chain; t < clip.T; t += clip.delay, e++) {
         const AvgRec &r = recs[t];
         avg_apply_general<VEC>(d, r, gcfg, nl, e, y, x, npx);
-        avg_store<VEC>(r.dst + ooff, d, npx);
+        px4_store<VEC>(r.dst + ooff, d, npx);
     }
-    avg_store<VEC>(rp, d, npx);
+    px4_store<VEC>(rp, d, npx);
 }
 
 __global__ __launch_bounds__(AVG_CLIP_THREADS) void k_avg_clip_general(const AvgRec *__restrict__ recs, AvgClip clip,
@@ -352,35 +317,21 @@ __global__ __launch_bounds__(AVG_CLIP_THREADS) void k_avg_clip_general(const Avg
 
 // ---- host side -----------------------------------------------------------------------------------------------
 
-struct AvgSlot {                         // records of one launch; "launch finished"
-    unsigned char *host = nullptr, *dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-};
-
 struct AvgState {
     ntscsim_avg_params prm;
     std::vector<uint32_t> cfg;           // (uint32_t)newlevel per layer
     uint32_t *cfg_dev = nullptr;         // general forms
-    AvgSlot slot[4];
-    int slot_idx = 0;
-    // ntscsim_avg_frames_host(): device arena (every distinct frame of the call) and one pinned frame
-    unsigned char *arena = nullptr, *staging = nullptr;
-    size_t arena_cap = 0, staging_cap = 0;
+    RecordSlots<> slots;
+    FrameArena frames;                   // ntscsim_avg_frames_host()
+    LayerGeom geom() const { return LayerGeom{prm.width, prm.height, prm.n_layers}; }
 };
 
 void avg_state_destroy(AvgState *k)
 {
     if (!k) return;
     if (k->cfg_dev) (void)hipFree(k->cfg_dev);
-    for (AvgSlot &s : k->slot) {
-        if (s.host) (void)hipHostFree(s.host);
-        if (s.dev) (void)hipFree(s.dev);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (k->arena) (void)hipFree(k->arena);
-    if (k->staging) (void)hipHostFree(k->staging);
+    k->slots.release();
+    k->frames.release();
     delete k;
 }
 
@@ -388,31 +339,22 @@ void avg_state_destroy(AvgState *k)
 
 using namespace ntscsim;
 
-#define AVGCHK(view, call)                                                             \
-    do {                                                                               \
-        hipError_t e__ = (call);                                                       \
-        if (e__ != hipSuccess) {                                                       \
-            *(view).err = std::string(#call) + ": " + hipGetErrorString(e__);          \
-            return NTSCSIM_E_HIP;                                                      \
-        }                                                                              \
-    } while (0)
-
 extern "C" int ntscsim_avg_bind(ntscsim_ctx *c, const ntscsim_avg_params *p)
 {
     if (!c || !p || p->struct_size != sizeof(*p) || p->n_layers < 0 || (p->n_layers > 0 && !p->layers)) return NTSCSIM_E_ARG;
     if (p->delay < 1 || p->delay > 256) return NTSCSIM_E_PARAM;                 // :647-650
     if (p->width < 1 || p->height < 1 || p->width > (1 << 16) || p->height > (1 << 16) ||
         (uint64_t)p->width * (uint64_t)p->height >= (1ull << 31)) return NTSCSIM_E_SIZE;
-    CtxAvgView v = ctx_avg_view(c);
-    AVGCHK(v, hipSetDevice(v.device));
+    CtxStageView v = ctx_stage_view(c);
+    STAGECHK(v, hipSetDevice(v.device));
     AvgState *k = *v.avg;
     if (!k) {
         k = new (std::nothrow) AvgState();
         if (!k) return NTSCSIM_E_NOMEM;
         *v.avg = k;
     }
-    for (AvgSlot &s : k->slot)           // launches in flight read the layer settings
-        if (s.used) AVGCHK(v, hipEventSynchronize(s.done));
+    const int rc = k->slots.wait_all(v);                                        // launches in flight read the layer settings
+    if (rc != NTSCSIM_OK) return rc;
     k->prm = *p;
     k->prm.layers = nullptr;
     k->prm.output_path = nullptr;
@@ -421,39 +363,19 @@ extern "C" int ntscsim_avg_bind(ntscsim_ctx *c, const ntscsim_avg_params *p)
     for (int l = 0; l < p->n_layers; l++) k->cfg.push_back((uint32_t)p->layers[l].newlevel);   // int -> unsigned, as :819 converts it
     if (k->cfg_dev) { (void)hipFree(k->cfg_dev); k->cfg_dev = nullptr; }
     if (p->n_layers > 0) {
-        AVGCHK(v, hipMalloc((void **)&k->cfg_dev, k->cfg.size() * sizeof(uint32_t)));
-        AVGCHK(v, hipMemcpy(k->cfg_dev, k->cfg.data(), k->cfg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        STAGECHK(v, hipMalloc((void **)&k->cfg_dev, k->cfg.size() * sizeof(uint32_t)));
+        STAGECHK(v, hipMemcpy(k->cfg_dev, k->cfg.data(), k->cfg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     return NTSCSIM_OK;
 }
 
 namespace {
 
-struct Span { uintptr_t a, b; };
-inline bool overlaps(const Span &x, const Span &y) { return x.a < y.b && y.a < x.b; }
-inline Span span_of(const void *p, int ls, int H) { return Span{(uintptr_t)p, (uintptr_t)p + (size_t)ls * (size_t)H}; }
-
-int check_desc(const AvgState *k, const ntscsim_avg_desc &d)
-{
-    const int W = k->prm.width, H = k->prm.height;
-    if (!d.dst_dev || (d.n_layers > 0 && !d.layers)) return NTSCSIM_E_ARG;
-    if (d.width != W || d.height != H || d.n_layers != k->prm.n_layers) return NTSCSIM_E_SIZE;
-    if (d.dst_linesize < 4 * W || (d.dst_linesize & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_SIZE;
-    const Span ds = span_of(d.dst_dev, d.dst_linesize, H);
-    for (int l = 0; l < d.n_layers; l++) {
-        const ntscsim_avg_src &s = d.layers[l];
-        if (!s.src_dev) continue;
-        if (s.src_linesize < 4 * W || (s.src_linesize & 3) || ((uintptr_t)s.src_dev & 3)) return NTSCSIM_E_SIZE;
-        if (overlaps(ds, span_of(s.src_dev, s.src_linesize, H))) return NTSCSIM_E_ARG;
-    }
-    return NTSCSIM_OK;
-}
-
 // One launch over descriptors that do not depend on each other, or -- clip != NULL -- over the frames of a clip,
 // whose chains the kernel itself walks in order.
 int avg_launch(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n, const AvgClip *clip, void *const *ring_host, hipStream_t st)
 {
-    CtxAvgView v = ctx_avg_view(c);
+    CtxStageView v = ctx_stage_view(c);
     AvgState *k = *v.avg;
     const int W = k->prm.width, H = k->prm.height, nl = k->prm.n_layers;
     const uint64_t delay = (uint64_t)k->prm.delay;
@@ -464,19 +386,10 @@ int avg_launch(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n, const AvgCl
     const size_t lay_bytes = general ? (size_t)n * (size_t)nl * sizeof(AvgLayerDev) : 0;
     const size_t ring_bytes = clip ? (size_t)clip->delay * sizeof(uint8_t *) : 0;
     const size_t bytes = rec_bytes + lay_bytes + ring_bytes;
-    AvgSlot &s = k->slot[k->slot_idx];
-    k->slot_idx = (k->slot_idx + 1) & 3;
-    if (!s.done) AVGCHK(v, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (s.used) AVGCHK(v, hipEventSynchronize(s.done));
-    if (bytes > s.cap) {
-        if (s.host) { (void)hipHostFree(s.host); s.host = nullptr; }
-        if (s.dev) { (void)hipFree(s.dev); s.dev = nullptr; }
-        s.cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        AVGCHK(v, hipHostMalloc((void **)&s.host, want, hipHostMallocPortable));
-        AVGCHK(v, hipMalloc((void **)&s.dev, want));
-        s.cap = want;
-    }
+    RecordSlot *slot = nullptr;
+    const int rc = k->slots.acquire(v, bytes, slot);
+    if (rc != NTSCSIM_OK) return rc;
+    RecordSlot &s = *slot;
     AvgRec *recs = reinterpret_cast<AvgRec *>(s.host);
     AvgLayerDev *lays = reinterpret_cast<AvgLayerDev *>(s.host + rec_bytes);
     uint8_t **ringp = reinterpret_cast<uint8_t **>(s.host + rec_bytes + lay_bytes);
@@ -512,7 +425,7 @@ int avg_launch(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n, const AvgCl
         r.vec = (bits & 15) == 0;
         allbits |= bits;
     }
-    AVGCHK(v, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st));
+    STAGECHK(v, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st));
 
     AvgCfg cfg;
     std::memset(&cfg, 0, sizeof(cfg));
@@ -543,8 +456,8 @@ int avg_launch(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n, const AvgCl
         if (general) hipLaunchKernelGGL(k_avg_general, grid, block, 0, st, recs_dev, k->cfg_dev, W, H, nl);
         else hipLaunchKernelGGL(k_avg_fast, grid, block, 0, st, recs_dev, cfg, W, H, nl);
     }
-    AVGCHK(v, hipGetLastError());
-    AVGCHK(v, hipEventRecord(s.done, st));
+    STAGECHK(v, hipGetLastError());
+    STAGECHK(v, hipEventRecord(s.done, st));
     s.used = true;
     if (!v.kernels->empty()) *v.kernels += ';';
     *v.kernels += clip ? (general ? "k_avg_clip_general" : "k_avg_clip_fast<" + std::to_string(nl) + ">") : (general ? "k_avg_general" : "k_avg_fast");
@@ -556,48 +469,14 @@ int avg_launch(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n, const AvgCl
 extern "C" int ntscsim_avg_frames_device(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n, void *hip_stream)
 {
     if (!c || n < 0 || (n > 0 && !descs)) return NTSCSIM_E_ARG;
-    CtxAvgView v = ctx_avg_view(c);
+    CtxStageView v = ctx_stage_view(c);
     AvgState *k = *v.avg;
     if (!k) return NTSCSIM_E_ARG;                                               // ntscsim_avg_bind() first
-    AVGCHK(v, hipSetDevice(v.device));
+    STAGECHK(v, hipSetDevice(v.device));
     v.kernels->clear();
-    for (int i = 0; i < n; i++) {
-        const int rc = check_desc(k, descs[i]);
-        if (rc != NTSCSIM_OK) return rc;
-    }
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream;
-    const int H = k->prm.height, cap = 65535;
-    // descriptors take effect in order: a launch ends in front of the first descriptor that writes what the launch
-    // reads or writes, or reads what it writes
-    std::vector<Span> wr, rd;
-    int first = 0;
-    for (int i = 0; i <= n; i++) {
-        bool cut = i == n || i - first >= cap;
-        if (!cut) {
-            const ntscsim_avg_desc &d = descs[i];
-            const Span ds = span_of(d.dst_dev, d.dst_linesize, H);
-            for (const Span &w : wr) if (overlaps(ds, w)) { cut = true; break; }
-            for (size_t j = 0; !cut && j < rd.size(); j++) cut = overlaps(ds, rd[j]);
-            for (int l = 0; !cut && l < d.n_layers; l++) {
-                if (!d.layers[l].src_dev) continue;
-                const Span ss = span_of(d.layers[l].src_dev, d.layers[l].src_linesize, H);
-                for (const Span &w : wr) if (overlaps(ss, w)) { cut = true; break; }
-            }
-        }
-        if (cut && i > first) {
-            const int rc = avg_launch(c, descs + first, i - first, nullptr, nullptr, st);
-            if (rc != NTSCSIM_OK) return rc;
-            first = i;
-            wr.clear(); rd.clear();
-        }
-        if (i < n) {
-            const ntscsim_avg_desc &d = descs[i];
-            wr.push_back(span_of(d.dst_dev, d.dst_linesize, H));
-            for (int l = 0; l < d.n_layers; l++)
-                if (d.layers[l].src_dev) rd.push_back(span_of(d.layers[l].src_dev, d.layers[l].src_linesize, H));
-        }
-    }
-    return NTSCSIM_OK;
+    return layer_frames_in_order(k->geom(), descs, n, 65535,
+                                 [&](const ntscsim_avg_desc *d, int m) { return avg_launch(c, d, m, nullptr, nullptr, st); });
 }
 
 extern "C" int ntscsim_avg_clip_device(ntscsim_ctx *c, void *const *ring_dev, int ring_linesize, int32_t *ring_index,
@@ -605,62 +484,28 @@ extern "C" int ntscsim_avg_clip_device(ntscsim_ctx *c, void *const *ring_dev, in
                                        int out_linesize, int T, uint64_t *field, void *hip_stream)
 {
     if (!c || !ring_dev || !ring_index || !field || T < 0 || (T > 0 && !out_dev)) return NTSCSIM_E_ARG;
-    CtxAvgView v = ctx_avg_view(c);
+    CtxStageView v = ctx_stage_view(c);
     AvgState *k = *v.avg;
     if (!k) return NTSCSIM_E_ARG;
-    const int W = k->prm.width, H = k->prm.height, nl = k->prm.n_layers, delay = k->prm.delay;
+    const int nl = k->prm.n_layers, delay = k->prm.delay;
     if (nl > 0 && (!src_dev || !src_linesize)) return NTSCSIM_E_ARG;
     if (*ring_index < 0 || *ring_index >= delay) return NTSCSIM_E_ARG;
     if (T > (1 << 24)) return NTSCSIM_E_SIZE;                                   // the kernels count frames in int
-    AVGCHK(v, hipSetDevice(v.device));
+    STAGECHK(v, hipSetDevice(v.device));
     v.kernels->clear();
-    if (ring_linesize < 4 * W || (ring_linesize & 3) || out_linesize < 4 * W || (out_linesize & 3)) return NTSCSIM_E_SIZE;
-    // what the call writes (ring, outputs) must be disjoint from itself and from every source
-    std::vector<Span> wr;
-    for (int i = 0; i < delay; i++) {
-        if (!ring_dev[i]) return NTSCSIM_E_ARG;
-        if ((uintptr_t)ring_dev[i] & 3) return NTSCSIM_E_SIZE;
-        wr.push_back(span_of(ring_dev[i], ring_linesize, H));
-    }
-    for (int t = 0; t < T; t++) {
-        if (!out_dev[t]) return NTSCSIM_E_ARG;
-        if ((uintptr_t)out_dev[t] & 3) return NTSCSIM_E_SIZE;
-        wr.push_back(span_of(out_dev[t], out_linesize, H));
-    }
-    std::sort(wr.begin(), wr.end(), [](const Span &x, const Span &y) { return x.a < y.a; });
-    for (size_t i = 1; i < wr.size(); i++)
-        if (wr[i].a < wr[i - 1].b) return NTSCSIM_E_ARG;
-    std::vector<ntscsim_avg_desc> descs((size_t)T);
-    std::vector<ntscsim_avg_src> lays((size_t)T * (size_t)nl);
+    std::vector<ntscsim_avg_desc> descs;
+    std::vector<ntscsim_avg_src> lays;
+    int rc = layer_clip_descs(k->geom(), delay, ring_dev, ring_linesize, src_dev, src_linesize, out_dev, out_linesize, T, true, descs, lays);
+    if (rc != NTSCSIM_OK) return rc;
     AvgClip clip;
     std::memset(&clip, 0, sizeof(clip));
     clip.ring_ls = ring_linesize; clip.ri = *ring_index; clip.delay = delay; clip.T = T; clip.out_ls = out_linesize;
-    for (int l = 0; l < nl; l++) {
-        if (src_linesize[l] < 4 * W || (src_linesize[l] & 3)) return NTSCSIM_E_SIZE;
-        if (l < AVG_FAST) clip.src_ls[l] = src_linesize[l];
-    }
-    for (int t = 0; t < T; t++) {
-        ntscsim_avg_desc &d = descs[(size_t)t];
-        d.dst_dev = out_dev[t]; d.dst_linesize = out_linesize; d.width = W; d.height = H; d.n_layers = nl;
-        d.layers = lays.data() + (size_t)t * (size_t)nl;
-        d.field = *field + (uint64_t)t;
-        for (int l = 0; l < nl; l++) {
-            ntscsim_avg_src &s = lays[(size_t)t * (size_t)nl + (size_t)l];
-            s.src_dev = src_dev[(size_t)l * (size_t)T + (size_t)t];
-            s.src_linesize = src_linesize[l];
-            s._pad = 0;
-            if (!s.src_dev) continue;
-            if ((uintptr_t)s.src_dev & 3) return NTSCSIM_E_SIZE;
-            const Span ss = span_of(s.src_dev, s.src_linesize, H);
-            auto it = std::upper_bound(wr.begin(), wr.end(), ss, [](const Span &x, const Span &y) { return x.a < y.a; });
-            if (it != wr.end() && overlaps(ss, *it)) return NTSCSIM_E_ARG;
-            if (it != wr.begin() && overlaps(ss, *(it - 1))) return NTSCSIM_E_ARG;
-        }
-    }
+    for (int l = 0; l < nl && l < AVG_FAST; l++) clip.src_ls[l] = src_linesize[l];
+    for (int t = 0; t < T; t++) descs[(size_t)t].field = *field + (uint64_t)t;
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream;
     if (T > 0) {
         // a chain's efield grows by one per step only from the chain's own first frame: the records carry it
-        const int rc = avg_launch(c, descs.data(), T, &clip, ring_dev, st);
+        rc = avg_launch(c, descs.data(), T, &clip, ring_dev, st);
         if (rc != NTSCSIM_OK) return rc;
     }
     *ring_index = (int)(((long long)*ring_index + T) % delay);
@@ -671,76 +516,9 @@ extern "C" int ntscsim_avg_clip_device(ntscsim_ctx *c, void *const *ring_dev, in
 extern "C" int ntscsim_avg_frames_host(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n)
 {
     if (!c || n < 0 || (n > 0 && !descs)) return NTSCSIM_E_ARG;
-    CtxAvgView v = ctx_avg_view(c);
+    CtxStageView v = ctx_stage_view(c);
     AvgState *k = *v.avg;
     if (!k) return NTSCSIM_E_ARG;
-    AVGCHK(v, hipSetDevice(v.device));
-    const int W = k->prm.width, H = k->prm.height;
-    const size_t pitch = ((size_t)W * 4 + 15) & ~(size_t)15, fb = pitch * (size_t)H;
-    // distinct frames of the call (pointer + linesize) -> offset in the device arena
-    typedef std::pair<const void *, int> Key;
-    std::map<Key, size_t> where;
-    std::vector<Key> order, dsts;
-    for (int i = 0; i < n; i++) {
-        const ntscsim_avg_desc &d = descs[i];
-        if (!d.dst_dev || (d.n_layers > 0 && !d.layers)) return NTSCSIM_E_ARG;
-        if (d.width != W || d.height != H || d.n_layers != k->prm.n_layers || d.dst_linesize < 4 * W) return NTSCSIM_E_SIZE;
-        const Key dk(d.dst_dev, d.dst_linesize);
-        if (where.emplace(dk, order.size() * fb).second) order.push_back(dk);
-        if (std::find(dsts.begin(), dsts.end(), dk) == dsts.end()) dsts.push_back(dk);
-        for (int l = 0; l < d.n_layers; l++) {
-            const ntscsim_avg_src &s = d.layers[l];
-            if (!s.src_dev) continue;
-            if (s.src_linesize < 4 * W) return NTSCSIM_E_SIZE;
-            const Key sk(s.src_dev, s.src_linesize);
-            if (where.emplace(sk, order.size() * fb).second) order.push_back(sk);
-        }
-    }
-    if (n == 0) return NTSCSIM_OK;
-    // a frame that is written must be disjoint from every other frame of the call: two host frames that overlap without
-    // being the same (pointer, linesize) would become two device frames, and the result would not be the tool's
-    for (const Key &dk : dsts)
-        for (const Key &ok : order)
-            if (ok != dk && overlaps(span_of(dk.first, dk.second, H), span_of(ok.first, ok.second, H))) return NTSCSIM_E_ARG;
-    if (order.size() * fb > k->arena_cap) {
-        if (k->arena) { (void)hipFree(k->arena); k->arena = nullptr; k->arena_cap = 0; }
-        AVGCHK(v, hipMalloc((void **)&k->arena, order.size() * fb));
-        k->arena_cap = order.size() * fb;
-    }
-    if (fb > k->staging_cap) {
-        if (k->staging) { (void)hipHostFree(k->staging); k->staging = nullptr; k->staging_cap = 0; }
-        AVGCHK(v, hipHostMalloc((void **)&k->staging, fb, hipHostMallocPortable));
-        k->staging_cap = fb;
-    }
-    hipStream_t st = v.stream;
-    for (const Key &key : order) {                                              // every frame once, packed to 16-byte pitched rows
-        for (int y = 0; y < H; y++)
-            std::memcpy(k->staging + (size_t)y * pitch, static_cast<const uint8_t *>(key.first) + (size_t)y * (size_t)key.second, (size_t)W * 4);
-        AVGCHK(v, hipMemcpyAsync(k->arena + where[key], k->staging, fb, hipMemcpyHostToDevice, st));
-        AVGCHK(v, hipStreamSynchronize(st));
-    }
-    std::vector<ntscsim_avg_desc> dd(descs, descs + n);
-    std::vector<ntscsim_avg_src> ll((size_t)n * (size_t)k->prm.n_layers);
-    for (int i = 0; i < n; i++) {
-        ntscsim_avg_desc &d = dd[(size_t)i];
-        d.dst_dev = k->arena + where[Key(descs[i].dst_dev, descs[i].dst_linesize)];
-        d.dst_linesize = (int)pitch;
-        ntscsim_avg_src *first = ll.data() + (size_t)i * (size_t)d.n_layers;
-        for (int l = 0; l < d.n_layers; l++) {
-            const ntscsim_avg_src &s = descs[i].layers[l];
-            first[l].src_dev = s.src_dev ? k->arena + where[Key(s.src_dev, s.src_linesize)] : nullptr;
-            first[l].src_linesize = (int)pitch;
-            first[l]._pad = 0;
-        }
-        d.layers = first;
-    }
-    const int rc = ntscsim_avg_frames_device(c, dd.data(), n, st);
-    if (rc != NTSCSIM_OK) return rc;
-    for (const Key &key : dsts) {
-        AVGCHK(v, hipMemcpyAsync(k->staging, k->arena + where[key], fb, hipMemcpyDeviceToHost, st));
-        AVGCHK(v, hipStreamSynchronize(st));
-        for (int y = 0; y < H; y++)
-            std::memcpy(static_cast<uint8_t *>(const_cast<void *>(key.first)) + (size_t)y * (size_t)key.second, k->staging + (size_t)y * pitch, (size_t)W * 4);
-    }
-    return NTSCSIM_OK;
+    return layer_frames_host(v, k->frames, k->geom(), descs, n,
+                             [&](const ntscsim_avg_desc *d, int m, hipStream_t st) { return ntscsim_avg_frames_device(c, d, m, st); });
 }

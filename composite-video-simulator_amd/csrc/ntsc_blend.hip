@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "ntscsim.h"
-#include "ntsc_blend.hpp"
+#include "ntsc_stage.hpp"
 
 namespace ntscsim {
 
@@ -155,24 +155,14 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_general(const BlendRec 
 
 // ---- host side -----------------------------------------------------------------------------------------------
 
-struct BlendSlot {                       // records of one launch: pinned host copy, device copy, "launch finished"
-    unsigned char *host = nullptr, *dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-};
-
 struct BlendState {
     ntscsim_blend_params prm;
     bool gamma = false;
     uint16_t *dec_dev = nullptr;
     uint32_t *enc_dev = nullptr;
     unsigned char *tab_host = nullptr;   // pinned: 512 bytes dec + 8196 bytes enc
-    BlendSlot slot[4];
-    int slot_idx = 0;
-    // ntscsim_blend_frames_host(): device arena (sources of the call + one chunk of outputs) and pinned staging
-    unsigned char *arena = nullptr, *staging = nullptr;
-    size_t arena_cap = 0, staging_cap = 0;
+    RecordSlots<> slots;
+    FrameArena frames;                   // ntscsim_blend_frames_host(): sources of the call + one chunk of outputs
 };
 
 void blend_state_destroy(BlendState *b)
@@ -181,13 +171,8 @@ void blend_state_destroy(BlendState *b)
     if (b->dec_dev) (void)hipFree(b->dec_dev);
     if (b->enc_dev) (void)hipFree(b->enc_dev);
     if (b->tab_host) (void)hipHostFree(b->tab_host);
-    for (BlendSlot &s : b->slot) {
-        if (s.host) (void)hipHostFree(s.host);
-        if (s.dev) (void)hipFree(s.dev);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (b->arena) (void)hipFree(b->arena);
-    if (b->staging) (void)hipHostFree(b->staging);
+    b->slots.release();
+    b->frames.release();
     delete b;
 }
 
@@ -195,41 +180,32 @@ void blend_state_destroy(BlendState *b)
 
 using namespace ntscsim;
 
-#define BLENDCHK(view, call)                                                           \
-    do {                                                                               \
-        hipError_t e__ = (call);                                                       \
-        if (e__ != hipSuccess) {                                                       \
-            *(view).err = std::string(#call) + ": " + hipGetErrorString(e__);          \
-            return NTSCSIM_E_HIP;                                                      \
-        }                                                                              \
-    } while (0)
-
 extern "C" int ntscsim_blend_bind(ntscsim_ctx *c, const ntscsim_blend_params *p)
 {
     if (!c || !p || p->struct_size != sizeof(*p)) return NTSCSIM_E_ARG;
     if (p->framealt < 1 || p->framealt > 8 || p->rate_num <= 0 || p->rate_den <= 0) return NTSCSIM_E_PARAM;
-    CtxBlendView v = ctx_blend_view(c);
-    BLENDCHK(v, hipSetDevice(v.device));
+    CtxStageView v = ctx_stage_view(c);
+    STAGECHK(v, hipSetDevice(v.device));
     BlendState *b = *v.blend;
     if (!b) {
         b = new (std::nothrow) BlendState();
         if (!b) return NTSCSIM_E_NOMEM;
         *v.blend = b;
     }
-    for (BlendSlot &s : b->slot)         // launches in flight read the tables and their records
-        if (s.used) BLENDCHK(v, hipEventSynchronize(s.done));
+    const int wrc = b->slots.wait_all(v);                                       // launches in flight read the tables and their records
+    if (wrc != NTSCSIM_OK) return wrc;
     b->prm = *p;
     b->prm.input_path = b->prm.output_path = nullptr;
     b->gamma = p->gamma_correction > 1;                                        // :1032
     if (b->gamma) {
-        if (!b->dec_dev) BLENDCHK(v, hipMalloc((void **)&b->dec_dev, 256 * sizeof(uint16_t)));
-        if (!b->enc_dev) BLENDCHK(v, hipMalloc((void **)&b->enc_dev, ENC_WORDS * 4));
-        if (!b->tab_host) BLENDCHK(v, hipHostMalloc((void **)&b->tab_host, 512 + ENC_WORDS * 4, hipHostMallocPortable));
+        if (!b->dec_dev) STAGECHK(v, hipMalloc((void **)&b->dec_dev, 256 * sizeof(uint16_t)));
+        if (!b->enc_dev) STAGECHK(v, hipMalloc((void **)&b->enc_dev, ENC_WORDS * 4));
+        if (!b->tab_host) STAGECHK(v, hipHostMalloc((void **)&b->tab_host, 512 + ENC_WORDS * 4, hipHostMallocPortable));
         std::memset(b->tab_host, 0, 512 + ENC_WORDS * 4);
         const int rc = ntscsim_blend_tables(p->gamma_correction, (uint16_t *)b->tab_host, b->tab_host + 512);
         if (rc != NTSCSIM_OK) return rc;
-        BLENDCHK(v, hipMemcpy(b->dec_dev, b->tab_host, 512, hipMemcpyHostToDevice));
-        BLENDCHK(v, hipMemcpy(b->enc_dev, b->tab_host + 512, ENC_WORDS * 4, hipMemcpyHostToDevice));
+        STAGECHK(v, hipMemcpy(b->dec_dev, b->tab_host, 512, hipMemcpyHostToDevice));
+        STAGECHK(v, hipMemcpy(b->enc_dev, b->tab_host + 512, ENC_WORDS * 4, hipMemcpyHostToDevice));
     }
     return NTSCSIM_OK;
 }
@@ -255,7 +231,7 @@ void launch_form(bool gamma, bool wide, dim3 grid, hipStream_t st, const BlendRe
 // one launch of at most 65535 descriptors
 int blend_launch(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, hipStream_t st)
 {
-    CtxBlendView v = ctx_blend_view(c);
+    CtxStageView v = ctx_stage_view(c);
     BlendState *b = *v.blend;
     const uint64_t mul = b->gamma ? 8192u : 255u;
     bool general = false, wide = false;
@@ -286,19 +262,10 @@ int blend_launch(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, hipStre
     // records (and, for the general form, the tap lists behind them) go up through a pinned slot of their own
     const size_t rec_bytes = (size_t)n * sizeof(BlendRec);
     const size_t bytes = rec_bytes + (general ? n_taps_total * sizeof(BlendTapDev) : 0);
-    BlendSlot &s = b->slot[b->slot_idx];
-    b->slot_idx = (b->slot_idx + 1) & 3;
-    if (!s.done) BLENDCHK(v, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (s.used) BLENDCHK(v, hipEventSynchronize(s.done));
-    if (bytes > s.cap) {
-        if (s.host) { (void)hipHostFree(s.host); s.host = nullptr; }
-        if (s.dev) { (void)hipFree(s.dev); s.dev = nullptr; }
-        s.cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        BLENDCHK(v, hipHostMalloc((void **)&s.host, want, hipHostMallocPortable));
-        BLENDCHK(v, hipMalloc((void **)&s.dev, want));
-        s.cap = want;
-    }
+    RecordSlot *slot = nullptr;
+    const int rc = b->slots.acquire(v, bytes, slot);
+    if (rc != NTSCSIM_OK) return rc;
+    RecordSlot &s = *slot;
     BlendRec *recs = reinterpret_cast<BlendRec *>(s.host);
     BlendTapDev *taps = reinterpret_cast<BlendTapDev *>(s.host + rec_bytes);
     const BlendTapDev *taps_dev = reinterpret_cast<const BlendTapDev *>(s.dev + rec_bytes);
@@ -326,7 +293,7 @@ int blend_launch(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, hipStre
         if (general) { r.taps = taps_dev + tap_at; tap_at += (size_t)d.n_taps; }
         r.vec = (bits & 15) == 0;
     }
-    BLENDCHK(v, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st));
+    STAGECHK(v, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st));
 
     // a workgroup walks several 256-quad slices of its frame (the LDS fill is then small against its pixels), but a short
     // call still spreads over the machine: about 8192 workgroups in all
@@ -335,8 +302,8 @@ int blend_launch(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, hipStre
     const dim3 grid((unsigned)per, (unsigned)n);
     if (general) launch_form<true>(b->gamma, wide, grid, st, reinterpret_cast<const BlendRec *>(s.dev), b->dec_dev, b->enc_dev);
     else launch_form<false>(b->gamma, wide, grid, st, reinterpret_cast<const BlendRec *>(s.dev), b->dec_dev, b->enc_dev);
-    BLENDCHK(v, hipGetLastError());
-    BLENDCHK(v, hipEventRecord(s.done, st));
+    STAGECHK(v, hipGetLastError());
+    STAGECHK(v, hipEventRecord(s.done, st));
     s.used = true;
     if (!v.kernels->empty()) *v.kernels += ';';
     *v.kernels += general ? "k_blend_general<" : "k_blend_fast<";
@@ -350,9 +317,9 @@ int blend_launch(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, hipStre
 extern "C" int ntscsim_blend_frames_device(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, void *hip_stream)
 {
     if (!c || n < 0 || (n > 0 && !descs)) return NTSCSIM_E_ARG;
-    CtxBlendView v = ctx_blend_view(c);
+    CtxStageView v = ctx_stage_view(c);
     if (!*v.blend) return NTSCSIM_E_ARG;                                        // ntscsim_blend_bind() first
-    BLENDCHK(v, hipSetDevice(v.device));
+    STAGECHK(v, hipSetDevice(v.device));
     v.kernels->clear();
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream;
     for (int at = 0; at < n; at += 65535) {
@@ -367,7 +334,7 @@ extern "C" int ntscsim_blend_clip_device(ntscsim_ctx *c, const void *const *src_
                                          int width, int height, int64_t first, int64_t last, void *hip_stream)
 {
     if (!c || !src_dev || !frame_t || n_src <= 0 || first < 0 || last < first || (last > first && !dst_dev)) return NTSCSIM_E_ARG;
-    CtxBlendView v = ctx_blend_view(c);
+    CtxStageView v = ctx_stage_view(c);
     BlendState *b = *v.blend;
     if (!b) return NTSCSIM_E_ARG;
     ntscsim_blend_plan *pl = nullptr;
@@ -407,10 +374,10 @@ extern "C" int ntscsim_blend_clip_device(ntscsim_ctx *c, const void *const *src_
 extern "C" int ntscsim_blend_frames_host(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n)
 {
     if (!c || n < 0 || (n > 0 && !descs)) return NTSCSIM_E_ARG;
-    CtxBlendView v = ctx_blend_view(c);
+    CtxStageView v = ctx_stage_view(c);
     BlendState *b = *v.blend;
     if (!b) return NTSCSIM_E_ARG;
-    BLENDCHK(v, hipSetDevice(v.device));
+    STAGECHK(v, hipSetDevice(v.device));
     const int CHUNK = 16;                // output frames per launch; staging holds as many frames
     auto pitch = [](int w) { return ((size_t)w * 4 + 15) & ~(size_t)15; };
     // distinct sources of the call (pointer + linesize + geometry) -> offset in the device arena
@@ -439,16 +406,9 @@ extern "C" int ntscsim_blend_frames_host(ntscsim_ctx *c, const ntscsim_blend_des
     }
     if (n == 0) return NTSCSIM_OK;
     const size_t stage_bytes = std::max(chunk_max, frame_max * (size_t)CHUNK);
-    if (src_bytes + chunk_max > b->arena_cap) {
-        if (b->arena) { (void)hipFree(b->arena); b->arena = nullptr; b->arena_cap = 0; }
-        BLENDCHK(v, hipMalloc((void **)&b->arena, src_bytes + chunk_max));
-        b->arena_cap = src_bytes + chunk_max;
-    }
-    if (stage_bytes > b->staging_cap) {
-        if (b->staging) { (void)hipHostFree(b->staging); b->staging = nullptr; b->staging_cap = 0; }
-        BLENDCHK(v, hipHostMalloc((void **)&b->staging, stage_bytes, hipHostMallocPortable));
-        b->staging_cap = stage_bytes;
-    }
+    FrameArena &fa = b->frames;
+    const int arc = fa.reserve(v, src_bytes + chunk_max, stage_bytes);
+    if (arc != NTSCSIM_OK) return arc;
     hipStream_t st = v.stream;
     // every source once: packed to 16-byte pitched rows in staging, up in runs that fill the staging buffer
     for (size_t i = 0; i < order.size();) {
@@ -457,13 +417,13 @@ extern "C" int ntscsim_blend_frames_host(ntscsim_ctx *c, const ntscsim_blend_des
         for (; j < order.size(); j++) {
             const Key &k = order[j];
             const size_t pb = pitch(k.w), fb = pb * (size_t)k.h;
-            if (fill + fb > b->staging_cap) break;
+            if (fill + fb > fa.staging_cap) break;
             for (int y = 0; y < k.h; y++)
-                std::memcpy(b->staging + fill + (size_t)y * pb, static_cast<const uint8_t *>(k.p) + (size_t)y * (size_t)k.ls, (size_t)k.w * 4);
+                std::memcpy(fa.staging + fill + (size_t)y * pb, static_cast<const uint8_t *>(k.p) + (size_t)y * (size_t)k.ls, (size_t)k.w * 4);
             fill += fb;
         }
-        BLENDCHK(v, hipMemcpyAsync(b->arena + run_at, b->staging, fill, hipMemcpyHostToDevice, st));
-        BLENDCHK(v, hipStreamSynchronize(st));
+        STAGECHK(v, hipMemcpyAsync(fa.arena + run_at, fa.staging, fill, hipMemcpyHostToDevice, st));
+        STAGECHK(v, hipStreamSynchronize(st));
         i = j;
     }
     std::vector<ntscsim_blend_desc> dd;
@@ -479,27 +439,27 @@ extern "C" int ntscsim_blend_frames_host(ntscsim_ctx *c, const ntscsim_blend_des
         size_t off = 0;
         for (int i = 0; i < m; i++) {
             ntscsim_blend_desc &d = dd[i];
-            d.dst_dev = b->arena + src_bytes + off;
+            d.dst_dev = fa.arena + src_bytes + off;
             d.dst_linesize = (int)pitch(d.width);
             off += pitch(d.width) * (size_t)d.height;
             const ntscsim_blend_tap *first = tt.data() + tt.size();
             for (int k = 0; k < d.n_taps; k++) {
                 const ntscsim_blend_tap &t = descs[at + i].taps[k];
-                tt.push_back(ntscsim_blend_tap{b->arena + where[Key{t.src_dev, t.src_linesize, d.width, d.height}], (int)pitch(d.width), t.weight16});
+                tt.push_back(ntscsim_blend_tap{fa.arena + where[Key{t.src_dev, t.src_linesize, d.width, d.height}], (int)pitch(d.width), t.weight16});
             }
             d.taps = first;
         }
         const int rc = ntscsim_blend_frames_device(c, dd.data(), m, st);
         if (rc != NTSCSIM_OK) return rc;
         if (names.empty()) names = *v.kernels;
-        BLENDCHK(v, hipMemcpyAsync(b->staging, b->arena + src_bytes, off, hipMemcpyDeviceToHost, st));
-        BLENDCHK(v, hipStreamSynchronize(st));
+        STAGECHK(v, hipMemcpyAsync(fa.staging, fa.arena + src_bytes, off, hipMemcpyDeviceToHost, st));
+        STAGECHK(v, hipStreamSynchronize(st));
         off = 0;
         for (int i = 0; i < m; i++) {
             const ntscsim_blend_desc &d = descs[at + i];
             const size_t pb = pitch(d.width);
             for (int y = 0; y < d.height; y++)
-                std::memcpy(static_cast<uint8_t *>(d.dst_dev) + (size_t)y * (size_t)d.dst_linesize, b->staging + off + (size_t)y * pb, (size_t)d.width * 4);
+                std::memcpy(static_cast<uint8_t *>(d.dst_dev) + (size_t)y * (size_t)d.dst_linesize, fa.staging + off + (size_t)y * pb, (size_t)d.width * 4);
             off += pb * (size_t)d.height;
         }
     }

@@ -16,13 +16,12 @@
 #include <map>
 #include <new>
 #include <string>
-#include <tuple>
-#include <utility>
 #include <vector>
 
 #include "key_host.hpp"
 #include "ntscsim.h"
-#include "ntsc_key.hpp"
+#include "ntsc_layer_frames.hpp"
+#include "ntsc_px4.hpp"
 
 namespace ntscsim {
 
@@ -69,16 +68,6 @@ struct KeyClip {                         // the clip forms: the ring behind the 
 
 // ---- k_key_draw -----------------------------------------------------------------------------------------------
 #include "lane_rand.hpp"   // LaneRand, jump61 (shared with the simulator's kernels)
-
-// device memory is reached through the global address space: a pointer that comes out of a record would otherwise be
-// accessed with flat instructions, which count against the scalar-load counter too, so every record read would wait
-// for the vector loads in flight
-#define KEY_GLOBAL __attribute__((address_space(1)))
-KDEV uint32_t gld(const void *p) { return *(const KEY_GLOBAL uint32_t *)p; }
-typedef uint32_t key_u4 __attribute__((ext_vector_type(4)));
-KDEV key_u4 gld4(const void *p) { return *(const KEY_GLOBAL key_u4 *)p; }
-KDEV void gst(void *p, uint32_t v) { *(KEY_GLOBAL uint32_t *)p = v; }
-KDEV void gst4(void *p, key_u4 v) { *(KEY_GLOBAL key_u4 *)p = v; }
 
 __global__ __launch_bounds__(KEY_DRAW_THREADS) void k_key_draw(const KeyJob *__restrict__ jobs, const uint32_t *__restrict__ polys,
                                                                uint32_t lanes)
@@ -158,40 +147,8 @@ KDEV uint32_t key_xdivc(uint32_t xdivr, int x) { return xdivr > 1 ? (uint32_t)x 
 template <bool VEC>
 KDEV void key_load_src(KeyPx &v, const uint8_t *__restrict__ srow, int x, uint32_t r0, int npx)
 {
-    const uint8_t *p = srow + (size_t)x * 4u;
-    if (VEC) {
-        const key_u4 q = gld4(p);
-        v.s[0] = q.x; v.s[1] = q.y; v.s[2] = q.z; v.s[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < npx) v.s[k] = gld(p + 4 * k);
-    }
+    px4_load<VEC>(v.s, srow + (size_t)x * 4u, npx);
     v.left = gld(srow + (size_t)((uint32_t)x - r0) * 4u);      // r0 == 0: the quad's own first pixel, not used
-}
-
-template <bool VEC>
-KDEV void key_load_dst(uint32_t (&v)[4], const uint8_t *__restrict__ p, int npx)
-{
-    if (VEC) {
-        const key_u4 q = gld4(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < npx) v[k] = gld(p + 4 * k);
-    }
-}
-
-template <bool VEC>
-KDEV void key_store(uint8_t *__restrict__ p, const uint32_t (&v)[4], int npx)
-{
-    if (VEC) gst4(p, key_u4{v[0], v[1], v[2], v[3]});
-    else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < npx) gst(p + 4 * k, v[k]);
-    }
 }
 
 // One layer on the pixels x .. x + npx - 1 of a row: d[] the destination pixels, v the layer's source, r0 = xdivc at x,
@@ -271,10 +228,10 @@ KDEV void key_item_fast(const KeyRec &r, const KeyCfg &cfg, int W, int nl, int y
     KeyPx v[KEY_FAST];
 #pragma unroll
     for (int k = 0; k < KEY_FAST; k++) r0[k] = key_xdivc(cfg.l[k].xdivr, x);
-    key_load_dst<VEC>(d, dp, npx);
+    px4_load<VEC>(d, dp, npx);
     key_load_fast<VEC>(v, r, nl, r0, y, x, npx);
     key_apply_fast<NOISE>(d, v, r, cfg, nl, r0, W, y, x, npx);
-    key_store<VEC>(dp, d, npx);
+    px4_store<VEC>(dp, d, npx);
 }
 
 // <NOISE>: a present layer has noisekey > 0 and k_key_draw has left its hit bits
@@ -296,9 +253,9 @@ KDEV void key_item_general(const KeyRec &r, const KeyCfgLayer *__restrict__ gcfg
 {
     uint8_t *dp = r.dst + (size_t)y * (size_t)r.dst_ls + (size_t)x * 4u;
     uint32_t d[4];
-    key_load_dst<VEC>(d, dp, npx);
+    px4_load<VEC>(d, dp, npx);
     key_apply_general<NOISE, VEC>(d, r, gcfg, nl, W, y, x, npx);
-    key_store<VEC>(dp, d, npx);
+    px4_store<VEC>(dp, d, npx);
 }
 
 template <bool NOISE>
@@ -347,7 +304,7 @@ KDEV void key_chain_fast(const KeyRec *__restrict__ recs, const KeyClip &clip, u
     KeyPx v[KEY_BUFS][NL];
 #pragma unroll
     for (int k = 0; k < NL; k++) r0[k] = key_xdivc(cfg.l[k].xdivr, x);
-    key_load_dst<VEC>(d, rp, npx);
+    px4_load<VEC>(d, rp, npx);
 #pragma unroll
     for (int j = 0; j < KEY_AHEAD; j++)       // past the chain's end: a frame of the chain again, loaded and not used
         key_load_chain<VEC, NL>(v[j], recs[chain + j * dl < T ? chain + j * dl : chain], ringrow, r0, y, x);
@@ -365,11 +322,11 @@ KDEV void key_chain_fast(const KeyRec *__restrict__ recs, const KeyClip &clip, u
                 for (int k = 0; k < NL; k++)
                     if (r.src[k])
                         key_layer<NOISE>(d, v[j][k], npx, cfg.l[k], r0[k], NOISE ? r.bits[k] : nullptr, (uint32_t)y * (uint32_t)W, x);
-                key_store<VEC>(r.dst + (size_t)y * (size_t)r.dst_ls + (size_t)x * 4u, d, npx);
+                px4_store<VEC>(r.dst + (size_t)y * (size_t)r.dst_ls + (size_t)x * 4u, d, npx);
             }
         }
     }
-    key_store<VEC>(rp, d, npx);
+    px4_store<VEC>(rp, d, npx);
 }
 
 // <NOISE, NL>: NL = number of layers, 1 .. NTSCSIM_KEY_FAST_LAYERS
@@ -404,13 +361,13 @@ KDEV void key_chain_general(const KeyRec *__restrict__ recs, const KeyClip &clip
 {
     uint8_t *rp = ring + (size_t)y * (size_t)clip.ring_ls + (size_t)x * 4u;
     uint32_t d[4];
-    key_load_dst<VEC>(d, rp, npx);
+    px4_load<VEC>(d, rp, npx);
     for (int t = chain; t < clip.T; t += clip.delay) {
         const KeyRec &r = recs[t];
         key_apply_general<NOISE, VEC>(d, r, gcfg, nl, W, y, x, npx);
-        key_store<VEC>(r.dst + (size_t)y * (size_t)r.dst_ls + (size_t)x * 4u, d, npx);
+        px4_store<VEC>(r.dst + (size_t)y * (size_t)r.dst_ls + (size_t)x * 4u, d, npx);
     }
-    key_store<VEC>(rp, d, npx);
+    px4_store<VEC>(rp, d, npx);
 }
 
 template <bool NOISE>
@@ -431,13 +388,9 @@ __global__ __launch_bounds__(KEY_THREADS) void k_key_clip_general(const KeyRec *
 
 // ---- host side -----------------------------------------------------------------------------------------------
 
-struct KeySlot {                         // records, jobs and hit bits of one launch; "launch finished"
-    unsigned char *host = nullptr, *dev = nullptr;
-    size_t cap = 0;
+struct KeySlot : RecordSlot {            // records and jobs of one launch, and its hit bits
     uint32_t *bits = nullptr;
     size_t bits_cap = 0;                 // words
-    hipEvent_t done = nullptr;
-    bool used = false;
 };
 
 struct KeyState {
@@ -448,16 +401,14 @@ struct KeyState {
     uint32_t *polys_dev = nullptr;       // k_key_draw: x^(768 j), coefficient-major
     uint32_t lanes = 0;                  // draw lanes per noisy (frame, layer)
     size_t bits_limit = (size_t)128 << 20;   // hit bits of one launch, bytes (ntscsim_key_debug_set_bits_limit)
-    KeySlot slot[4];
-    int slot_idx = 0;
+    RecordSlots<KeySlot> slots;
     // the rand() window of the last job, and x^n of the distances met so far: consecutive jobs are a fixed distance apart
     bool have_state = false;
     uint64_t state_pos = 0;
     RandState state;
     std::map<uint64_t, RandPoly> deltas;
-    // ntscsim_key_frames_host(): device arena (every distinct frame of the call) and one pinned frame
-    unsigned char *arena = nullptr, *staging = nullptr;
-    size_t arena_cap = 0, staging_cap = 0;
+    FrameArena frames;                   // ntscsim_key_frames_host()
+    LayerGeom geom() const { return LayerGeom{prm.width, prm.height, prm.n_layers}; }
 };
 
 void key_state_destroy(KeyState *k)
@@ -465,14 +416,10 @@ void key_state_destroy(KeyState *k)
     if (!k) return;
     if (k->cfg_dev) (void)hipFree(k->cfg_dev);
     if (k->polys_dev) (void)hipFree(k->polys_dev);
-    for (KeySlot &s : k->slot) {
-        if (s.host) (void)hipHostFree(s.host);
-        if (s.dev) (void)hipFree(s.dev);
+    for (KeySlot &s : k->slots.slot)
         if (s.bits) (void)hipFree(s.bits);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (k->arena) (void)hipFree(k->arena);
-    if (k->staging) (void)hipHostFree(k->staging);
+    k->slots.release();
+    k->frames.release();
     delete k;
 }
 
@@ -480,31 +427,22 @@ void key_state_destroy(KeyState *k)
 
 using namespace ntscsim;
 
-#define KEYCHK(view, call)                                                             \
-    do {                                                                               \
-        hipError_t e__ = (call);                                                       \
-        if (e__ != hipSuccess) {                                                       \
-            *(view).err = std::string(#call) + ": " + hipGetErrorString(e__);          \
-            return NTSCSIM_E_HIP;                                                      \
-        }                                                                              \
-    } while (0)
-
 extern "C" int ntscsim_key_bind(ntscsim_ctx *c, const ntscsim_key_params *p)
 {
     if (!c || !p || p->struct_size != sizeof(*p) || p->n_layers < 0 || (p->n_layers > 0 && !p->layers)) return NTSCSIM_E_ARG;
     if (p->delay < 1 || p->delay > 256) return NTSCSIM_E_PARAM;                 // :652-655
     if (p->width < 1 || p->height < 1 || p->width > (1 << 16) || p->height > (1 << 16) ||
         (uint64_t)p->width * (uint64_t)p->height >= (1ull << 31)) return NTSCSIM_E_SIZE;
-    CtxKeyView v = ctx_key_view(c);
-    KEYCHK(v, hipSetDevice(v.device));
+    CtxStageView v = ctx_stage_view(c);
+    STAGECHK(v, hipSetDevice(v.device));
     KeyState *k = *v.key;
     if (!k) {
         k = new (std::nothrow) KeyState();
         if (!k) return NTSCSIM_E_NOMEM;
         *v.key = k;
     }
-    for (KeySlot &s : k->slot)           // launches in flight read the layer settings and the polynomials
-        if (s.used) KEYCHK(v, hipEventSynchronize(s.done));
+    const int rc = k->slots.wait_all(v);                                        // launches in flight read the layer settings and the polynomials
+    if (rc != NTSCSIM_OK) return rc;
     k->prm = *p;
     k->prm.layers = nullptr;
     k->prm.output_path = nullptr;
@@ -519,25 +457,21 @@ extern "C" int ntscsim_key_bind(ntscsim_ctx *c, const ntscsim_key_params *p)
     if (k->cfg_dev) { (void)hipFree(k->cfg_dev); k->cfg_dev = nullptr; }
     if (k->polys_dev) { (void)hipFree(k->polys_dev); k->polys_dev = nullptr; }
     if (p->n_layers > 0) {
-        KEYCHK(v, hipMalloc((void **)&k->cfg_dev, k->cfg.size() * sizeof(KeyCfgLayer)));
-        KEYCHK(v, hipMemcpy(k->cfg_dev, k->cfg.data(), k->cfg.size() * sizeof(KeyCfgLayer), hipMemcpyHostToDevice));
+        STAGECHK(v, hipMalloc((void **)&k->cfg_dev, k->cfg.size() * sizeof(KeyCfgLayer)));
+        STAGECHK(v, hipMemcpy(k->cfg_dev, k->cfg.data(), k->cfg.size() * sizeof(KeyCfgLayer), hipMemcpyHostToDevice));
     }
     k->lanes = key_lanes_per_job(p->width, p->height);
     if (k->any_noise) {
         std::vector<uint32_t> polys;
         key_lane_polys(k->lanes, polys);
-        KEYCHK(v, hipMalloc((void **)&k->polys_dev, polys.size() * sizeof(uint32_t)));
-        KEYCHK(v, hipMemcpy(k->polys_dev, polys.data(), polys.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        STAGECHK(v, hipMalloc((void **)&k->polys_dev, polys.size() * sizeof(uint32_t)));
+        STAGECHK(v, hipMemcpy(k->polys_dev, polys.data(), polys.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     k->have_state = false;
     return NTSCSIM_OK;
 }
 
 namespace {
-
-struct Span { uintptr_t a, b; };
-inline bool overlaps(const Span &x, const Span &y) { return x.a < y.b && y.a < x.b; }
-inline Span span_of(const void *p, int ls, int H) { return Span{(uintptr_t)p, (uintptr_t)p + (size_t)ls * (size_t)H}; }
 
 // the rand() window at `pos`: from the last one by the polynomial of the distance where that is ahead of it
 const RandState &key_state_at(KeyState *k, uint64_t pos)
@@ -558,27 +492,11 @@ const RandState &key_state_at(KeyState *k, uint64_t pos)
     return k->state;
 }
 
-int check_desc(const KeyState *k, const ntscsim_key_desc &d)
-{
-    const int W = k->prm.width, H = k->prm.height;
-    if (!d.dst_dev || (d.n_layers > 0 && !d.layers)) return NTSCSIM_E_ARG;
-    if (d.width != W || d.height != H || d.n_layers != k->prm.n_layers) return NTSCSIM_E_SIZE;
-    if (d.dst_linesize < 4 * W || (d.dst_linesize & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_SIZE;
-    const Span ds = span_of(d.dst_dev, d.dst_linesize, H);
-    for (int l = 0; l < d.n_layers; l++) {
-        const ntscsim_key_src &s = d.layers[l];
-        if (!s.src_dev) continue;
-        if (s.src_linesize < 4 * W || (s.src_linesize & 3) || ((uintptr_t)s.src_dev & 3)) return NTSCSIM_E_SIZE;
-        if (overlaps(ds, span_of(s.src_dev, s.src_linesize, H))) return NTSCSIM_E_ARG;
-    }
-    return NTSCSIM_OK;
-}
-
 // One pixel launch (with k_key_draw in front where a present layer draws) over descriptors that do not depend on each
 // other, or -- clip != NULL -- over the frames of a clip, whose chains the kernel itself walks in order.
 int key_launch(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n, const KeyClip *clip, void *const *ring_host, hipStream_t st)
 {
-    CtxKeyView v = ctx_key_view(c);
+    CtxStageView v = ctx_stage_view(c);
     KeyState *k = *v.key;
     const int W = k->prm.width, H = k->prm.height, nl = k->prm.n_layers;
     const bool general = nl > KEY_FAST || (clip && nl == 0);    // the fast clip form is instantiated for 1 .. 4 layers
@@ -595,24 +513,15 @@ int key_launch(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n, const KeyCl
     const size_t job_bytes = njobs * sizeof(KeyJob);
     const size_t ring_bytes = clip ? (size_t)clip->delay * sizeof(uint8_t *) : 0;
     const size_t bytes = rec_bytes + lay_bytes + job_bytes + ring_bytes;
-    KeySlot &s = k->slot[k->slot_idx];
-    k->slot_idx = (k->slot_idx + 1) & 3;
-    if (!s.done) KEYCHK(v, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (s.used) KEYCHK(v, hipEventSynchronize(s.done));
-    if (bytes > s.cap) {
-        if (s.host) { (void)hipHostFree(s.host); s.host = nullptr; }
-        if (s.dev) { (void)hipFree(s.dev); s.dev = nullptr; }
-        s.cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        KEYCHK(v, hipHostMalloc((void **)&s.host, want, hipHostMallocPortable));
-        KEYCHK(v, hipMalloc((void **)&s.dev, want));
-        s.cap = want;
-    }
+    KeySlot *slot = nullptr;
+    const int rc = k->slots.acquire(v, bytes, slot);
+    if (rc != NTSCSIM_OK) return rc;
+    KeySlot &s = *slot;
     if (njobs * job_words > s.bits_cap) {
         if (s.bits) { (void)hipFree(s.bits); s.bits = nullptr; }
         s.bits_cap = 0;
         const size_t want = njobs * job_words + njobs * job_words / 4;
-        KEYCHK(v, hipMalloc((void **)&s.bits, want * sizeof(uint32_t)));
+        STAGECHK(v, hipMalloc((void **)&s.bits, want * sizeof(uint32_t)));
         s.bits_cap = want;
     }
     KeyRec *recs = reinterpret_cast<KeyRec *>(s.host);
@@ -669,14 +578,14 @@ int key_launch(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n, const KeyCl
     }
     if (clip)
         for (int i = 0; i < n; i++) recs[i].vec = (allbits & 15) == 0;
-    KEYCHK(v, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st));
+    STAGECHK(v, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st));
 
     if (noise) {
         for (size_t at = 0; at < njobs; at += 65535) {
             const dim3 grid((k->lanes + KEY_DRAW_THREADS - 1) / KEY_DRAW_THREADS, (unsigned)std::min<size_t>(65535, njobs - at));
             hipLaunchKernelGGL(k_key_draw, grid, dim3(KEY_DRAW_THREADS), 0, st, jobs_dev + at, k->polys_dev, k->lanes);
         }
-        KEYCHK(v, hipGetLastError());
+        STAGECHK(v, hipGetLastError());
         if (!v.kernels->empty()) *v.kernels += ';';
         *v.kernels += "k_key_draw";
     }
@@ -720,8 +629,8 @@ int key_launch(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n, const KeyCl
             else hipLaunchKernelGGL(k_key_fast<false>, grid, block, 0, st, recs_dev, cfg, W, H, nl);
         }
     }
-    KEYCHK(v, hipGetLastError());
-    KEYCHK(v, hipEventRecord(s.done, st));
+    STAGECHK(v, hipGetLastError());
+    STAGECHK(v, hipEventRecord(s.done, st));
     s.used = true;
     if (!v.kernels->empty()) *v.kernels += ';';
     *v.kernels += clip ? (general ? "k_key_clip_general<" : "k_key_clip_fast<") : (general ? "k_key_general<" : "k_key_fast<");
@@ -746,7 +655,7 @@ int key_frames_per_launch(const KeyState *k)
 extern "C" int ntscsim_key_debug_set_bits_limit(ntscsim_ctx *c, size_t bytes)
 {
     if (!c) return NTSCSIM_E_ARG;
-    KeyState *k = *ctx_key_view(c).key;
+    KeyState *k = *ctx_stage_view(c).key;
     if (!k) return NTSCSIM_E_ARG;                                               // ntscsim_key_bind() first
     k->bits_limit = bytes ? bytes : (size_t)128 << 20;
     return NTSCSIM_OK;
@@ -755,48 +664,14 @@ extern "C" int ntscsim_key_debug_set_bits_limit(ntscsim_ctx *c, size_t bytes)
 extern "C" int ntscsim_key_frames_device(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n, void *hip_stream)
 {
     if (!c || n < 0 || (n > 0 && !descs)) return NTSCSIM_E_ARG;
-    CtxKeyView v = ctx_key_view(c);
+    CtxStageView v = ctx_stage_view(c);
     KeyState *k = *v.key;
     if (!k) return NTSCSIM_E_ARG;                                               // ntscsim_key_bind() first
-    KEYCHK(v, hipSetDevice(v.device));
+    STAGECHK(v, hipSetDevice(v.device));
     v.kernels->clear();
-    for (int i = 0; i < n; i++) {
-        const int rc = check_desc(k, descs[i]);
-        if (rc != NTSCSIM_OK) return rc;
-    }
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream;
-    const int H = k->prm.height, cap = key_frames_per_launch(k);
-    // descriptors take effect in order: a launch ends in front of the first descriptor that writes what the launch
-    // reads or writes, or reads what it writes
-    std::vector<Span> wr, rd;
-    int first = 0;
-    for (int i = 0; i <= n; i++) {
-        bool cut = i == n || i - first >= cap;
-        if (!cut) {
-            const ntscsim_key_desc &d = descs[i];
-            const Span ds = span_of(d.dst_dev, d.dst_linesize, H);
-            for (const Span &w : wr) if (overlaps(ds, w)) { cut = true; break; }
-            for (size_t j = 0; !cut && j < rd.size(); j++) cut = overlaps(ds, rd[j]);
-            for (int l = 0; !cut && l < d.n_layers; l++) {
-                if (!d.layers[l].src_dev) continue;
-                const Span ss = span_of(d.layers[l].src_dev, d.layers[l].src_linesize, H);
-                for (const Span &w : wr) if (overlaps(ss, w)) { cut = true; break; }
-            }
-        }
-        if (cut && i > first) {
-            const int rc = key_launch(c, descs + first, i - first, nullptr, nullptr, st);
-            if (rc != NTSCSIM_OK) return rc;
-            first = i;
-            wr.clear(); rd.clear();
-        }
-        if (i < n) {
-            const ntscsim_key_desc &d = descs[i];
-            wr.push_back(span_of(d.dst_dev, d.dst_linesize, H));
-            for (int l = 0; l < d.n_layers; l++)
-                if (d.layers[l].src_dev) rd.push_back(span_of(d.layers[l].src_dev, d.layers[l].src_linesize, H));
-        }
-    }
-    return NTSCSIM_OK;
+    return layer_frames_in_order(k->geom(), descs, n, key_frames_per_launch(k),
+                                 [&](const ntscsim_key_desc *d, int m) { return key_launch(c, d, m, nullptr, nullptr, st); });
 }
 
 extern "C" int ntscsim_key_clip_device(ntscsim_ctx *c, void *const *ring_dev, int ring_linesize, int32_t *ring_index,
@@ -804,51 +679,23 @@ extern "C" int ntscsim_key_clip_device(ntscsim_ctx *c, void *const *ring_dev, in
                                        int out_linesize, int T, uint64_t *rand_pos, void *hip_stream)
 {
     if (!c || !ring_dev || !ring_index || !rand_pos || T < 0 || (T > 0 && !out_dev)) return NTSCSIM_E_ARG;
-    CtxKeyView v = ctx_key_view(c);
+    CtxStageView v = ctx_stage_view(c);
     KeyState *k = *v.key;
     if (!k) return NTSCSIM_E_ARG;
     const int W = k->prm.width, H = k->prm.height, nl = k->prm.n_layers, delay = k->prm.delay;
     if (nl > 0 && (!src_dev || !src_linesize)) return NTSCSIM_E_ARG;
     if (*ring_index < 0 || *ring_index >= delay) return NTSCSIM_E_ARG;
-    KEYCHK(v, hipSetDevice(v.device));
+    STAGECHK(v, hipSetDevice(v.device));
     v.kernels->clear();
-    if (ring_linesize < 4 * W || (ring_linesize & 3) || out_linesize < 4 * W || (out_linesize & 3)) return NTSCSIM_E_SIZE;
-    // what the call writes (ring, outputs) must be disjoint from itself and from every source
-    std::vector<Span> wr;
-    for (int i = 0; i < delay; i++) {
-        if (!ring_dev[i]) return NTSCSIM_E_ARG;
-        if ((uintptr_t)ring_dev[i] & 3) return NTSCSIM_E_SIZE;
-        wr.push_back(span_of(ring_dev[i], ring_linesize, H));
-    }
-    for (int t = 0; t < T; t++) {
-        if (!out_dev[t]) return NTSCSIM_E_ARG;
-        if ((uintptr_t)out_dev[t] & 3) return NTSCSIM_E_SIZE;
-        wr.push_back(span_of(out_dev[t], out_linesize, H));
-    }
-    std::sort(wr.begin(), wr.end(), [](const Span &x, const Span &y) { return x.a < y.a; });
-    for (size_t i = 1; i < wr.size(); i++)
-        if (wr[i].a < wr[i - 1].b) return NTSCSIM_E_ARG;
-    std::vector<ntscsim_key_desc> descs((size_t)T);
-    std::vector<ntscsim_key_src> lays((size_t)T * (size_t)nl);
+    std::vector<ntscsim_key_desc> descs;
+    std::vector<ntscsim_key_src> lays;
+    const int rc = layer_clip_descs(k->geom(), delay, ring_dev, ring_linesize, src_dev, src_linesize, out_dev, out_linesize, T, false, descs, lays);
+    if (rc != NTSCSIM_OK) return rc;
     uint64_t pos = *rand_pos;
     for (int t = 0; t < T; t++) {
-        ntscsim_key_desc &d = descs[(size_t)t];
-        d.dst_dev = out_dev[t]; d.dst_linesize = out_linesize; d.width = W; d.height = H; d.n_layers = nl;
-        d.layers = lays.data() + (size_t)t * (size_t)nl;
-        d.rand_pos = pos;
-        for (int l = 0; l < nl; l++) {
-            ntscsim_key_src &s = lays[(size_t)t * (size_t)nl + (size_t)l];
-            s.src_dev = src_dev[(size_t)l * (size_t)T + (size_t)t];
-            s.src_linesize = src_linesize[l];
-            s._pad = 0;
-            if (!s.src_dev) continue;
-            if (k->cfg[(size_t)l].noisekey > 0) pos += 3ull * (uint64_t)W * (uint64_t)H;
-            if (s.src_linesize < 4 * W || (s.src_linesize & 3) || ((uintptr_t)s.src_dev & 3)) return NTSCSIM_E_SIZE;
-            const Span ss = span_of(s.src_dev, s.src_linesize, H);
-            auto it = std::upper_bound(wr.begin(), wr.end(), ss, [](const Span &x, const Span &y) { return x.a < y.a; });
-            if (it != wr.end() && overlaps(ss, *it)) return NTSCSIM_E_ARG;
-            if (it != wr.begin() && overlaps(ss, *(it - 1))) return NTSCSIM_E_ARG;
-        }
+        descs[(size_t)t].rand_pos = pos;
+        for (int l = 0; l < nl; l++)
+            if (lays[(size_t)t * (size_t)nl + (size_t)l].src_dev && k->cfg[(size_t)l].noisekey > 0) pos += 3ull * (uint64_t)W * (uint64_t)H;
     }
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream;
     // one launch for the whole clip, or one per run of frames whose hit bits fit the bound: the ring carries over
@@ -859,8 +706,8 @@ extern "C" int ntscsim_key_clip_device(ntscsim_ctx *c, void *const *ring_dev, in
         const int m = std::min(cap, T - at);
         const KeyClip clip{nullptr, ring_linesize, ri, delay, m};
         v.kernels->clear();
-        const int rc = key_launch(c, descs.data() + at, m, &clip, ring_dev, st);
-        if (rc != NTSCSIM_OK) return rc;
+        const int lrc = key_launch(c, descs.data() + at, m, &clip, ring_dev, st);
+        if (lrc != NTSCSIM_OK) return lrc;
         if (names.empty()) names = *v.kernels;
         ri = (int)(((long long)ri + m) % delay);
     }
@@ -873,76 +720,9 @@ extern "C" int ntscsim_key_clip_device(ntscsim_ctx *c, void *const *ring_dev, in
 extern "C" int ntscsim_key_frames_host(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n)
 {
     if (!c || n < 0 || (n > 0 && !descs)) return NTSCSIM_E_ARG;
-    CtxKeyView v = ctx_key_view(c);
+    CtxStageView v = ctx_stage_view(c);
     KeyState *k = *v.key;
     if (!k) return NTSCSIM_E_ARG;
-    KEYCHK(v, hipSetDevice(v.device));
-    const int W = k->prm.width, H = k->prm.height;
-    const size_t pitch = ((size_t)W * 4 + 15) & ~(size_t)15, fb = pitch * (size_t)H;
-    // distinct frames of the call (pointer + linesize) -> offset in the device arena
-    typedef std::pair<const void *, int> Key;
-    std::map<Key, size_t> where;
-    std::vector<Key> order, dsts;
-    for (int i = 0; i < n; i++) {
-        const ntscsim_key_desc &d = descs[i];
-        if (!d.dst_dev || (d.n_layers > 0 && !d.layers)) return NTSCSIM_E_ARG;
-        if (d.width != W || d.height != H || d.n_layers != k->prm.n_layers || d.dst_linesize < 4 * W) return NTSCSIM_E_SIZE;
-        const Key dk(d.dst_dev, d.dst_linesize);
-        if (where.emplace(dk, order.size() * fb).second) order.push_back(dk);
-        if (std::find(dsts.begin(), dsts.end(), dk) == dsts.end()) dsts.push_back(dk);
-        for (int l = 0; l < d.n_layers; l++) {
-            const ntscsim_key_src &s = d.layers[l];
-            if (!s.src_dev) continue;
-            if (s.src_linesize < 4 * W) return NTSCSIM_E_SIZE;
-            const Key sk(s.src_dev, s.src_linesize);
-            if (where.emplace(sk, order.size() * fb).second) order.push_back(sk);
-        }
-    }
-    if (n == 0) return NTSCSIM_OK;
-    // a frame that is written must be disjoint from every other frame of the call: two host frames that overlap without
-    // being the same (pointer, linesize) would become two device frames, and the result would not be the tool's
-    for (const Key &dk : dsts)
-        for (const Key &ok : order)
-            if (ok != dk && overlaps(span_of(dk.first, dk.second, H), span_of(ok.first, ok.second, H))) return NTSCSIM_E_ARG;
-    if (order.size() * fb > k->arena_cap) {
-        if (k->arena) { (void)hipFree(k->arena); k->arena = nullptr; k->arena_cap = 0; }
-        KEYCHK(v, hipMalloc((void **)&k->arena, order.size() * fb));
-        k->arena_cap = order.size() * fb;
-    }
-    if (fb > k->staging_cap) {
-        if (k->staging) { (void)hipHostFree(k->staging); k->staging = nullptr; k->staging_cap = 0; }
-        KEYCHK(v, hipHostMalloc((void **)&k->staging, fb, hipHostMallocPortable));
-        k->staging_cap = fb;
-    }
-    hipStream_t st = v.stream;
-    for (const Key &key : order) {                                              // every frame once, packed to 16-byte pitched rows
-        for (int y = 0; y < H; y++)
-            std::memcpy(k->staging + (size_t)y * pitch, static_cast<const uint8_t *>(key.first) + (size_t)y * (size_t)key.second, (size_t)W * 4);
-        KEYCHK(v, hipMemcpyAsync(k->arena + where[key], k->staging, fb, hipMemcpyHostToDevice, st));
-        KEYCHK(v, hipStreamSynchronize(st));
-    }
-    std::vector<ntscsim_key_desc> dd(descs, descs + n);
-    std::vector<ntscsim_key_src> ll((size_t)n * (size_t)k->prm.n_layers);
-    for (int i = 0; i < n; i++) {
-        ntscsim_key_desc &d = dd[(size_t)i];
-        d.dst_dev = k->arena + where[Key(descs[i].dst_dev, descs[i].dst_linesize)];
-        d.dst_linesize = (int)pitch;
-        ntscsim_key_src *first = ll.data() + (size_t)i * (size_t)d.n_layers;
-        for (int l = 0; l < d.n_layers; l++) {
-            const ntscsim_key_src &s = descs[i].layers[l];
-            first[l].src_dev = s.src_dev ? k->arena + where[Key(s.src_dev, s.src_linesize)] : nullptr;
-            first[l].src_linesize = (int)pitch;
-            first[l]._pad = 0;
-        }
-        d.layers = first;
-    }
-    const int rc = ntscsim_key_frames_device(c, dd.data(), n, st);
-    if (rc != NTSCSIM_OK) return rc;
-    for (const Key &key : dsts) {
-        KEYCHK(v, hipMemcpyAsync(k->staging, k->arena + where[key], fb, hipMemcpyDeviceToHost, st));
-        KEYCHK(v, hipStreamSynchronize(st));
-        for (int y = 0; y < H; y++)
-            std::memcpy(static_cast<uint8_t *>(const_cast<void *>(key.first)) + (size_t)y * (size_t)key.second, k->staging + (size_t)y * pitch, (size_t)W * 4);
-    }
-    return NTSCSIM_OK;
+    return layer_frames_host(v, k->frames, k->geom(), descs, n,
+                             [&](const ntscsim_key_desc *d, int m, hipStream_t st) { return ntscsim_key_frames_device(c, d, m, st); });
 }

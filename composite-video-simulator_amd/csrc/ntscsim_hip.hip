@@ -26,9 +26,7 @@
 #include "ntsc422_fused.hip"
 #include "ntsc_scale.hip"
 #include "ntsc_float.hpp"       // NTSCSIM_MODE_FLOAT: its kernels are a translation unit of their own
-#include "ntsc_blend.hpp"       // the frameblend stage (ntscsim_blend_*): likewise, csrc/ntsc_blend.hip
-#include "ntsc_key.hpp"         // the colorkey stage (ntscsim_key_*): likewise, csrc/ntsc_key.hip
-#include "ntsc_avg.hpp"         // the average_delay stage (ntscsim_avg_*): likewise, csrc/ntsc_avg.hip
+#include "ntsc_stage.hpp"       // the frameblend, colorkey and average_delay stages (ntscsim_blend_* / _key_* / _avg_*): likewise, csrc/ntsc_{blend,key,avg}.hip
 
 using namespace ntscsim;
 
@@ -224,17 +222,9 @@ struct ntscsim_ctx {
     ntscsim::KeyState *key = nullptr;       // ntscsim_key_bind(): state of the colorkey stage (csrc/ntsc_key.hip)
     ntscsim::AvgState *avg = nullptr;       // ntscsim_avg_bind(): state of the average_delay stage (csrc/ntsc_avg.hip)
 };
-ntscsim::CtxBlendView ntscsim::ctx_blend_view(ntscsim_ctx *c)
+ntscsim::CtxStageView ntscsim::ctx_stage_view(ntscsim_ctx *c)
 {
-    return CtxBlendView{c->device, c->stream, &c->err, &c->kernels, &c->blend};
-}
-ntscsim::CtxKeyView ntscsim::ctx_key_view(ntscsim_ctx *c)
-{
-    return CtxKeyView{c->device, c->stream, &c->err, &c->kernels, &c->key};
-}
-ntscsim::CtxAvgView ntscsim::ctx_avg_view(ntscsim_ctx *c)
-{
-    return CtxAvgView{c->device, c->stream, &c->err, &c->kernels, &c->avg};
+    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg};
 }
 static void declared_pins_destroy(ntscsim_ctx *c);
 static uint8_t *pinned_device_ptr(ntscsim_ctx *c, const void *p, size_t span);      // ntscsim_submit.hip

@@ -518,20 +518,22 @@ class FrameBlender:
         self.sim.sync()
 
 
-class ColorKeyer:
-    """The colorkey stage (ntscsim_key_*): keys layers over a destination that is never cleared, as ffmpeg_colorkey
-    does.  `argv` are the tool's switches, e.g. ("-d", "2", "-i", "bg", "-i", "fg", "-color", "0x00FF00", "-threshhold",
-    "96"): every -i opens a layer (the name is only recorded) and the per-layer switches behind it apply to it.
-    width / height: the frame size (the tool has no -height).  sim: share the context of a FieldSimulator (its outputs
-    can then be keyed on the same stream without leaving device memory); otherwise a context of its own is created.
-    torch is used only for device memory and streams."""
+class _LayerStage:
+    """What ColorKeyer and FrameAverager share: a stage bound on a shared or owned FieldSimulator context whose frames are
+    a destination and a list of layers.  A subclass names its C entry points (_NAME: ntscsim_<_NAME>_*), its ctypes
+    descriptor and source types, and the uint64 field that tags a descriptor (_TAG)."""
+    _NAME = _DESC = _SRC = _TAG = None
 
-    def __init__(self, argv=(), width=None, height=None, device=0, params=None, sim=None):
-        self.params = params if params is not None else _capi.make_key_params(argv, width=width, height=height)
+    def __init__(self, params, device, sim):
+        self.params = params
         self._own = sim is None
         self.sim = sim if sim is not None else FieldSimulator(device=device)
         self._lib = self.sim._lib
-        self.sim._chk(self._lib.ntscsim_key_bind(self.sim._h, C.byref(self.params)), "ntscsim_key_bind")
+        self._call("bind", C.byref(self.params))
+
+    def _call(self, what, *args):
+        name = "ntscsim_%s_%s" % (self._NAME, what)
+        self.sim._chk(getattr(self._lib, name)(self.sim._h, *args), name)
 
     def close(self):
         if self._own and self.sim is not None:
@@ -545,6 +547,70 @@ class ColorKeyer:
     @property
     def delay(self):
         return int(self.params.delay)
+
+    def _descs(self, jobs, ptr, linesize):
+        """jobs: list of (dst, [src or None per layer], tag), frames [H, W, 4] uint8 with contiguous pixels."""
+        arr = (self._DESC * max(1, len(jobs)))()
+        keep = []
+        for d, (dst, srcs, tag) in zip(arr, jobs):
+            h, w = dst.shape[0], dst.shape[1]
+            t = (self._SRC * max(1, len(srcs)))()
+            for k, src in enumerate(srcs):
+                if src is not None:
+                    assert tuple(src.shape) == (h, w, 4)
+                    t[k].src_dev, t[k].src_linesize = ptr(src), linesize(src)
+            keep.append(t)
+            d.dst_dev, d.dst_linesize, d.width, d.height, d.n_layers, d.layers = ptr(dst), linesize(dst), w, h, len(srcs), t
+            setattr(d, self._TAG, int(tag))
+        return arr, keep
+
+    def _frames_device(self, jobs, stream):
+        arr, keep = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("frames_device", arr, len(jobs), C.c_void_p(stream))
+
+    def _frames_host(self, jobs):
+        arr, keep = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self._call("frames_host", arr, len(jobs))
+
+    def _clip(self, ring, layers, out, ring_index, tag, stream):
+        """The *_clip_device call; returns (ring_index, tag) behind the last frame."""
+        T, nl = len(out), self.n_layers
+        assert len(ring) == self.delay and len(layers) == nl and all(len(lay) == T for lay in layers)
+        rp = (C.c_void_p * max(1, len(ring)))(*[r.data_ptr() for r in ring])
+        sp = (C.c_void_p * max(1, nl * T))(*[(f.data_ptr() if f is not None else None) for lay in layers for f in lay])
+        ls = (C.c_int32 * max(1, nl))()
+        for k, lay in enumerate(layers):
+            strides = set(f.stride(0) for f in lay if f is not None)
+            assert len(strides) <= 1
+            ls[k] = strides.pop() if strides else 4 * int(self.params.width)
+        op = (C.c_void_p * max(1, T))(*[o.data_ptr() for o in out])
+        ri, tg = C.c_int32(int(ring_index)), C.c_uint64(int(tag))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("clip_device", rp, ring[0].stride(0) if len(ring) else 0, C.byref(ri), sp, ls, op,
+                   out[0].stride(0) if T else 4 * int(self.params.width), T, C.byref(tg), C.c_void_p(stream))
+        return int(ri.value), int(tg.value)
+
+    def last_kernels(self):
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
+
+
+class ColorKeyer(_LayerStage):
+    """The colorkey stage (ntscsim_key_*): keys layers over a destination that is never cleared, as ffmpeg_colorkey
+    does.  `argv` are the tool's switches, e.g. ("-d", "2", "-i", "bg", "-i", "fg", "-color", "0x00FF00", "-threshhold",
+    "96"): every -i opens a layer (the name is only recorded) and the per-layer switches behind it apply to it.
+    width / height: the frame size (the tool has no -height).  sim: share the context of a FieldSimulator (its outputs
+    can then be keyed on the same stream without leaving device memory); otherwise a context of its own is created.
+    torch is used only for device memory and streams."""
+    _NAME, _DESC, _SRC, _TAG = "key", _capi.KeyDesc, _capi.KeySrc, "rand_pos"
+
+    def __init__(self, argv=(), width=None, height=None, device=0, params=None, sim=None):
+        super().__init__(params if params is not None else _capi.make_key_params(argv, width=width, height=height), device, sim)
 
     def rand_advance(self, pos, present=None):
         """ntscsim_key_rand_advance: the position of the rand() stream behind one output frame that starts at `pos`;
@@ -559,158 +625,54 @@ class ColorKeyer:
             raise NtscsimError(rc, "ntscsim_key_rand_advance")
         return int(v.value)
 
-    def _descs(self, jobs, ptr, linesize):
-        """jobs: list of (dst, [src or None per layer], rand_pos), frames [H, W, 4] uint8 with contiguous pixels."""
-        arr = (_capi.KeyDesc * max(1, len(jobs)))()
-        keep = []
-        for d, (dst, srcs, pos) in zip(arr, jobs):
-            h, w = dst.shape[0], dst.shape[1]
-            t = (_capi.KeySrc * max(1, len(srcs)))()
-            for k, src in enumerate(srcs):
-                if src is not None:
-                    assert tuple(src.shape) == (h, w, 4)
-                    t[k].src_dev, t[k].src_linesize = ptr(src), linesize(src)
-            keep.append(t)
-            d.dst_dev, d.dst_linesize, d.width, d.height, d.n_layers, d.layers = ptr(dst), linesize(dst), w, h, len(srcs), t
-            d.rand_pos = int(pos)
-        return arr, keep
-
     def key_frames(self, jobs, stream=None):
         """ntscsim_key_frames_device: jobs = [(dst, [src or None per layer], rand_pos), ...] of torch uint8 CUDA tensors
         [H, W, 4] (any row stride); dst is keyed in place.  Enqueues; does not synchronise."""
-        arr, keep = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
-        if stream is None:
-            stream = self.sim._torch_stream()
-        rc = self._lib.ntscsim_key_frames_device(self.sim._h, arr, len(jobs), C.c_void_p(stream))
-        self.sim._chk(rc, "ntscsim_key_frames_device")
+        self._frames_device(jobs, stream)
 
     def key_frames_host(self, jobs):
         """ntscsim_key_frames_host: the same on numpy uint8 arrays [H, W, 4].  Synchronous."""
-        arr, keep = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
-        self.sim._chk(self._lib.ntscsim_key_frames_host(self.sim._h, arr, len(jobs)), "ntscsim_key_frames_host")
+        self._frames_host(jobs)
 
     def key_clip(self, ring, layers, out, ring_index=0, rand_pos=0, stream=None):
         """ntscsim_key_clip_device: ring = list of `delay` torch uint8 CUDA frames [H, W, 4] (the destination ring, kept
         between calls), layers = per layer a list of T frames (None: absent in that frame), out = list of T frames.
         Frames of one list share a row stride.  Returns (ring_index, rand_pos) behind the last frame, to be handed to
         the next call.  Enqueues; does not synchronise."""
-        T, nl = len(out), self.n_layers
-        assert len(ring) == self.delay and len(layers) == nl and all(len(lay) == T for lay in layers)
-        rp = (C.c_void_p * max(1, len(ring)))(*[r.data_ptr() for r in ring])
-        sp = (C.c_void_p * max(1, nl * T))(*[(f.data_ptr() if f is not None else None) for lay in layers for f in lay])
-        ls = (C.c_int32 * max(1, nl))()
-        for k, lay in enumerate(layers):
-            strides = set(f.stride(0) for f in lay if f is not None)
-            assert len(strides) <= 1
-            ls[k] = strides.pop() if strides else 4 * int(self.params.width)
-        op = (C.c_void_p * max(1, T))(*[o.data_ptr() for o in out])
-        ri, pos = C.c_int32(int(ring_index)), C.c_uint64(int(rand_pos))
-        if stream is None:
-            stream = self.sim._torch_stream()
-        rc = self._lib.ntscsim_key_clip_device(self.sim._h, rp, ring[0].stride(0) if len(ring) else 0, C.byref(ri), sp, ls, op,
-                                               out[0].stride(0) if T else 4 * int(self.params.width), T, C.byref(pos),
-                                               C.c_void_p(stream))
-        self.sim._chk(rc, "ntscsim_key_clip_device")
-        return int(ri.value), int(pos.value)
+        return self._clip(ring, layers, out, ring_index, rand_pos, stream)
 
     def debug_set_bits_limit(self, nbytes):
         """ntscsim_key_debug_set_bits_limit: bound on the hit bits of one launch (0: the default)."""
-        self.sim._chk(self._lib.ntscsim_key_debug_set_bits_limit(self.sim._h, int(nbytes)), "ntscsim_key_debug_set_bits_limit")
-
-    def last_kernels(self):
-        return self.sim.last_kernels()
-
-    def sync(self):
-        self.sim.sync()
+        self._call("debug_set_bits_limit", int(nbytes))
 
 
-class FrameAverager:
+class FrameAverager(_LayerStage):
     """The average_delay stage (ntscsim_avg_*): averages layers into a destination that is never cleared, as
     ffmpeg_average_delay does.  `argv` are the tool's switches, e.g. ("-d", "2", "-i", "a", "-n", "64"): every -i opens a
     layer (the name is only recorded) and -n behind it sets its level (256 = all new, 0 = all old).  width / height:
     the frame size (the tool has no -height).  sim: share the context of a FieldSimulator (its outputs can then be
     averaged on the same stream without leaving device memory); otherwise a context of its own is created.  torch is
     used only for device memory and streams."""
+    _NAME, _DESC, _SRC, _TAG = "avg", _capi.AvgDesc, _capi.AvgSrc, "field"
 
     def __init__(self, argv=(), width=None, height=None, device=0, params=None, sim=None):
-        self.params = params if params is not None else _capi.make_avg_params(argv, width=width, height=height)
-        self._own = sim is None
-        self.sim = sim if sim is not None else FieldSimulator(device=device)
-        self._lib = self.sim._lib
-        self.sim._chk(self._lib.ntscsim_avg_bind(self.sim._h, C.byref(self.params)), "ntscsim_avg_bind")
-
-    def close(self):
-        if self._own and self.sim is not None:
-            self.sim.close()
-        self.sim = None
-
-    @property
-    def n_layers(self):
-        return int(self.params.n_layers)
-
-    @property
-    def delay(self):
-        return int(self.params.delay)
-
-    def _descs(self, jobs, ptr, linesize):
-        """jobs: list of (dst, [src or None per layer], field), frames [H, W, 4] uint8 with contiguous pixels."""
-        arr = (_capi.AvgDesc * max(1, len(jobs)))()
-        keep = []
-        for d, (dst, srcs, field) in zip(arr, jobs):
-            h, w = dst.shape[0], dst.shape[1]
-            t = (_capi.AvgSrc * max(1, len(srcs)))()
-            for k, src in enumerate(srcs):
-                if src is not None:
-                    assert tuple(src.shape) == (h, w, 4)
-                    t[k].src_dev, t[k].src_linesize = ptr(src), linesize(src)
-            keep.append(t)
-            d.dst_dev, d.dst_linesize, d.width, d.height, d.n_layers, d.layers = ptr(dst), linesize(dst), w, h, len(srcs), t
-            d.field = int(field)
-        return arr, keep
+        super().__init__(params if params is not None else _capi.make_avg_params(argv, width=width, height=height), device, sim)
 
     def average_frames(self, jobs, stream=None):
         """ntscsim_avg_frames_device: jobs = [(dst, [src or None per layer], field), ...] of torch uint8 CUDA tensors
         [H, W, 4] (any row stride); dst is averaged in place.  Enqueues; does not synchronise."""
-        arr, keep = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
-        if stream is None:
-            stream = self.sim._torch_stream()
-        rc = self._lib.ntscsim_avg_frames_device(self.sim._h, arr, len(jobs), C.c_void_p(stream))
-        self.sim._chk(rc, "ntscsim_avg_frames_device")
+        self._frames_device(jobs, stream)
 
     def average_frames_host(self, jobs):
         """ntscsim_avg_frames_host: the same on numpy uint8 arrays [H, W, 4].  Synchronous."""
-        arr, keep = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
-        self.sim._chk(self._lib.ntscsim_avg_frames_host(self.sim._h, arr, len(jobs)), "ntscsim_avg_frames_host")
+        self._frames_host(jobs)
 
     def average_clip(self, ring, layers, out, ring_index=0, field=0, stream=None):
         """ntscsim_avg_clip_device: ring = list of `delay` torch uint8 CUDA frames [H, W, 4] (the destination ring, kept
         between calls), layers = per layer a list of T frames (None: absent in that frame), out = list of T frames.
         Frames of one list share a row stride.  Returns (ring_index, field) behind the last frame, to be handed to the
         next call.  Enqueues; does not synchronise."""
-        T, nl = len(out), self.n_layers
-        assert len(ring) == self.delay and len(layers) == nl and all(len(lay) == T for lay in layers)
-        rp = (C.c_void_p * max(1, len(ring)))(*[r.data_ptr() for r in ring])
-        sp = (C.c_void_p * max(1, nl * T))(*[(f.data_ptr() if f is not None else None) for lay in layers for f in lay])
-        ls = (C.c_int32 * max(1, nl))()
-        for k, lay in enumerate(layers):
-            strides = set(f.stride(0) for f in lay if f is not None)
-            assert len(strides) <= 1
-            ls[k] = strides.pop() if strides else 4 * int(self.params.width)
-        op = (C.c_void_p * max(1, T))(*[o.data_ptr() for o in out])
-        ri, fld = C.c_int32(int(ring_index)), C.c_uint64(int(field))
-        if stream is None:
-            stream = self.sim._torch_stream()
-        rc = self._lib.ntscsim_avg_clip_device(self.sim._h, rp, ring[0].stride(0) if len(ring) else 0, C.byref(ri), sp, ls, op,
-                                               out[0].stride(0) if T else 4 * int(self.params.width), T, C.byref(fld),
-                                               C.c_void_p(stream))
-        self.sim._chk(rc, "ntscsim_avg_clip_device")
-        return int(ri.value), int(fld.value)
-
-    def last_kernels(self):
-        return self.sim.last_kernels()
-
-    def sync(self):
-        self.sim.sync()
+        return self._clip(ring, layers, out, ring_index, field, stream)
 
 
 class Pool:
