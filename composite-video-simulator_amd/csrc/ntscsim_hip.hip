@@ -9,13 +9,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <unistd.h>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "ntscsim.h"
 #include "ntsc_device.hpp"
+#include "engine_host.hpp"     // what the host-frame engines decide without the GPU: row maps, copy lists, copy threads, pinned ranges
 
 // single translation unit: the kernels are compiled together with their launcher
 #include "ntsc_kernels.hip"
@@ -95,7 +95,7 @@ struct Geometry {
 
 struct SubmitEngine;      // ntscsim_submit.hip (included at the end of this file)
 struct Host422Engine;     // ntscsim_host422.hip (likewise)
-struct PinCache;          // ntscsim_submit.hip: registrations of caller memory
+struct PinCache;          // ntscsim_pins.hip: registrations of caller memory
 
 struct ntscsim_ctx {
     ntscsim_params prm;
@@ -226,8 +226,6 @@ ntscsim::CtxStageView ntscsim::ctx_stage_view(ntscsim_ctx *c)
 {
     return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg};
 }
-static void declared_pins_destroy(ntscsim_ctx *c);
-static uint8_t *pinned_device_ptr(ntscsim_ctx *c, const void *p, size_t span);      // ntscsim_submit.hip
 static void submit_engine_destroy(ntscsim_ctx *c);
 static int sub_wait_ticket(ntscsim_ctx *c, uint64_t ticket);
 static void host422_engine_destroy(ntscsim_ctx *c);
@@ -242,6 +240,9 @@ static int h422_launch(ntscsim_ctx *c);
             return NTSCSIM_E_HIP;                                                      \
         }                                                                              \
     } while (0)
+
+// ---- pinning of caller memory: ntscsim_host_pin() and its relatives
+#include "ntscsim_pins.hip"
 
 // which kernel form a launch site chose (read back by ntscsim_debug_last_kernels; the parity tests
 // assert on it, so that a specialised form cannot silently stop being the one that runs)
@@ -1992,42 +1993,7 @@ extern "C" int ntscsim_field(ntscsim_ctx *c, const uint8_t *src, int src_ls, int
 // chunk slots, so the PCIe transfers of neighbouring chunks overlap the kernels (and each other:
 // the link is full duplex).  The caller's buffers are pinned in place (hipHostRegister) for the
 // duration of the call; if that fails the copies still work, just synchronously.
-// Pin two caller buffers in place for the duration of a call (whole pages, explicitly).  Small buffers are not
-// worth a registration, and two registrations must never share a page: small heap allocations often do, and
-// unpinning the first one then pulls the page from under the second (seen as sporadic aborts inside later,
-// unrelated hipMemcpy calls of the process).
-struct HostPins {
-    uintptr_t s0 = 0, d0 = 0;
-    bool pin_src = false, pin_dst = false;
-    void pin(const void *src, size_t src_span, void *dst, size_t dst_span, unsigned flags)
-    {
-        const uintptr_t PG = 4096, MIN_PIN = 1u << 20;
-        uintptr_t s1 = ((uintptr_t)src + src_span + PG - 1) & ~(PG - 1);
-        uintptr_t d1 = ((uintptr_t)dst + dst_span + PG - 1) & ~(PG - 1);
-        s0 = (uintptr_t)src & ~(PG - 1);
-        d0 = (uintptr_t)dst & ~(PG - 1);
-        bool want_src = src_span >= MIN_PIN, want_dst = dst_span >= MIN_PIN;
-        // (never memory of the brk heap: its pages are trimmed and recycled by the allocator)
-        const uintptr_t brk = (uintptr_t)sbrk(0);
-        want_src = want_src && (uintptr_t)src >= brk;
-        want_dst = want_dst && (uintptr_t)dst >= brk;
-        if (want_src && want_dst && s0 < d1 && d0 < s1) {          // page ranges touch: one registration
-            s0 = s0 < d0 ? s0 : d0; s1 = s1 > d1 ? s1 : d1;
-            want_dst = false;
-        } else if (s0 < d1 && d0 < s1) {
-            want_src = want_dst = false;                            // a small buffer inside the other's pages
-        }
-        pin_src = want_src && hipHostRegister((void *)s0, s1 - s0, flags) == hipSuccess;
-        pin_dst = want_dst && hipHostRegister((void *)d0, d1 - d0, flags) == hipSuccess;
-        (void)hipGetLastError();
-    }
-    void unpin()
-    {
-        if (pin_src) (void)hipHostUnregister((void *)s0);
-        if (pin_dst) (void)hipHostUnregister((void *)d0);
-        pin_src = pin_dst = false;
-    }
-};
+// (HostPins, ntscsim_pins.hip).
 
 // Deal: the call works on the frames of blocks blk_index, blk_index + blk_count, ... (blocks of blk_frames frames) of
 // the run only -- the share of one context of a pool (ntscsim_pool_frames_host); blk_count = 1: all of them.  Every
@@ -2285,6 +2251,7 @@ extern "C" int ntscsim_debug_read_composite(ntscsim_ctx *c, int32_t *out, size_t
 }
 
 // ---- asynchronous host-frame drop-in: ntscsim_submit() / ntscsim_wait()
+#include "ntscsim_queue.hip"
 #include "ntscsim_submit.hip"
 #include "ntscsim_host422.hip"
 

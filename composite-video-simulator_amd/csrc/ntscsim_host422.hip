@@ -22,7 +22,9 @@
 // Both deliver the rows of `field` of the frame (and of the filter frame), and the encoder frame when one was
 // given, back into the caller's memory at ntscsim_wait(), in submit order.  Everything runs on the ctx's stream;
 // sources are snapshotted into a pinned staging ring by the submitting thread and uploaded on a copy stream.
-#include <deque>
+//
+// Tickets, launches in flight and the source ring are the LaunchQueue's (ntscsim_queue.hip), the rows of a field, the record
+// layout's copy list and the copy threads engine_host.hpp's, pinning ntscsim_pins.hip's.
 
 namespace {
 
@@ -95,7 +97,35 @@ __global__ void k422_pad(const PadRec422 *__restrict__ recs)
 
 } // namespace
 
-struct Host422Engine {
+struct Mirror422 {
+    const uint8_t *host[3]; int ls[3]; int H;
+    DevBuf<uint8_t> dev; size_t off[3];
+    bool stale = true;
+};
+struct Host422Item {
+    uint64_t ticket = 0;
+    int slot = 0, fslot = 0, sslot = -1;
+    bool serial = false;
+    bool tight = false;               // batched although linesize[0] < width + 2: the pad bytes are chained on the device
+    int chain_fslot = -1;             // device frame that holds the other field as the previous iteration left it (-1: none, snapshot)
+    uint64_t chain_ticket = 0;        // ... and the ticket of the iteration that wrote it
+    ntscsim_loop422 it;
+    Mirror422 *mfrm = nullptr, *mflt = nullptr;
+    uint64_t rng_pos = 0;
+    uint8_t *frm_dev[3] = {nullptr, nullptr, nullptr};    // device-visible addresses of the caller's planes when pinned
+    uint8_t *flt_dev[3] = {nullptr, nullptr, nullptr};
+    uint8_t *out_dev[3] = {nullptr, nullptr, nullptr};
+    uint8_t *src_dev[3] = {nullptr, nullptr, nullptr};    // ntscsim_field422(): pinned source planes, read in place (no snapshot)
+    // set at launch -- how each of the three results reaches the caller: 0 through the staging record (copied at
+    // ntscsim_wait), 1 written by the delivery kernels into the pinned frame, 2 not at all (a later iteration of the same
+    // launch writes the same rows of the same pinned frame)
+    int frm_how = 0, flt_how = 0, out_how = 0;
+};
+struct NoLaunchExtra {};
+
+struct Host422Engine : LaunchQueue<Host422Item, NoLaunchExtra> {
+    using Item = Host422Item;
+    using Mirror = Mirror422;
     int depth = 32, nslots = 128;     // configured: iterations per launch, iterations that may be in flight
     int ring_want = 0;                // the request the rings were sized for (ring may be smaller: the byte budget)
     int ring = 0;                     // slots the rings were allocated with (<= nslots: lazily, and capped by a byte budget)
@@ -119,53 +149,12 @@ struct Host422Engine {
     // NTSCSIM_SUBMIT422_PIN=0: everything through the staging rings.
     PinCache pins;
 
-    struct Mirror {
-        const uint8_t *host[3]; int ls[3]; int H;
-        DevBuf<uint8_t> dev; size_t off[3];
-        bool stale = true;
-    };
     std::vector<Mirror *> mirrors;
 
-    struct Item {
-        uint64_t ticket = 0;
-        int slot = 0, fslot = 0, sslot = -1;
-        bool serial = false;
-        bool tight = false;               // batched although linesize[0] < width + 2: the pad bytes are chained on the device
-        int chain_fslot = -1;             // device frame that holds the other field as the previous iteration left it (-1: none, snapshot)
-        uint64_t chain_ticket = 0;        // ... and the ticket of the iteration that wrote it
-        ntscsim_loop422 it;
-        Mirror *mfrm = nullptr, *mflt = nullptr;
-        uint64_t rng_pos = 0;
-        uint8_t *frm_dev[3] = {nullptr, nullptr, nullptr};    // device-visible addresses of the caller's planes when pinned
-        uint8_t *flt_dev[3] = {nullptr, nullptr, nullptr};
-        uint8_t *out_dev[3] = {nullptr, nullptr, nullptr};
-        uint8_t *src_dev[3] = {nullptr, nullptr, nullptr};    // ntscsim_field422(): pinned source planes, read in place (no snapshot)
-        // set at launch -- how each of the three results reaches the caller: 0 through the staging record (copied at
-        // ntscsim_wait), 1 written by the delivery kernels into the pinned frame, 2 not at all (a later iteration of the same
-        // launch writes the same rows of the same pinned frame)
-        int frm_how = 0, flt_how = 0, out_how = 0;
-    };
-    std::vector<Item> pending;
     // TIGHT rows: who wrote each field of a caller frame last, and into which device frame (see h422_submit)
     struct Writer { const uint8_t *frame; uint64_t ticket[2]; int fslot[2]; };
     std::vector<Writer> writers;
-    struct Batch {
-        uint64_t first = 0, last = 0;
-        hipEvent_t done = nullptr;
-        std::vector<Item> items;
-        int rc = NTSCSIM_OK;
-        bool launched_ok = false;
-        bool posted = false;              // staged results: handed to the copy threads (Delivery), id = `last`
-    };
-    std::deque<Batch> inflight;
-    Delivery dlv;                         // staging ring -> caller frames, off the caller's thread
-    std::vector<hipEvent_t> ev_pool;
     hipEvent_t ev_up = nullptr;
-    uint64_t next_ticket = 1, done_ticket = 0;
-    int src_cur = -1;
-    uint64_t src_ring_pos = 0;
-    std::vector<uint64_t> src_last_ticket;
-    uint64_t stats_two_pass = 0;           // launches that ran twice (TIGHT rows chained inside the launch)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [0] submitted [1] launches [2] uploads [3] FAST [4] SERIAL [5] mirror uploads [6] iterations with a result written by the delivery kernels into pinned caller planes
 };
 
@@ -220,12 +209,10 @@ static void host422_engine_destroy(ntscsim_ctx *c)
     if (!e) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    e->dlv.stop(true);
-    for (auto &b : e->inflight) if (b.done) (void)hipEventDestroy(b.done);
-    for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
+    e->shutdown();
     for (auto *m : e->mirrors) { m->dev.release(); delete m; }
     h422_release_rings(e);
-    pin_release_all(e->pins);
+    pin_release(e->pins, nullptr);
     if (e->s_up) (void)hipStreamDestroy(e->s_up);
     if (e->s_dn) (void)hipStreamDestroy(e->s_dn);
     if (e->ev_up) (void)hipEventDestroy(e->ev_up);
@@ -302,21 +289,9 @@ static int h422_ensure_rings(ntscsim_ctx *c, Host422Engine *e, int W, int H, siz
     if (!e->ev_up) HIPCHK(c, hipEventCreateWithFlags(&e->ev_up, hipEventDisableTiming));
     if (!e->ev_k) HIPCHK(c, hipEventCreateWithFlags(&e->ev_k, hipEventDisableTiming));
     e->W = W; e->H = H; e->L = L; e->ring = ns; e->ring_want = want;
-    e->src_last_ticket.assign((size_t)ns, 0);
-    e->src_ring_pos = 0;
-    e->src_cur = -1;
+    e->src_reset((size_t)ns);
     return NTSCSIM_OK;
 }
-
-static int h422_field_rows(int H, unsigned field) { return H > (int)field ? (H - (int)field + 1) / 2 : 0; }
-
-// chroma rows of the encoder frame that output_frame() writes inside the plane (:1177-1236)
-static int h422_out_chroma_rows(int H, uint32_t mode) { return (mode == NTSCSIM_OUT422_BOB422 || mode == NTSCSIM_OUT422_FRAME) ? H : (H + 1) / 2; }
-
-// ... and the rows the record keeps per chroma plane (the interlaced repack writes one row past a 4:2:0 plane for a
-// height of 2 mod 4, :1215-1223: it has room here and is not delivered)
-static int h422_out_chroma_alloc(int H, uint32_t mode) { return h422_out_chroma_rows(H, mode) + 1; }
-static size_t h422_out_bytes(int W, int H, uint32_t mode) { return (size_t)W * H + 2 * (size_t)(W / 2) * (size_t)h422_out_chroma_alloc(H, mode); }
 
 // (`keep`: a mirror the caller already holds for the same iteration -- it survives the eviction below)
 static Host422Engine::Mirror *h422_mirror(ntscsim_ctx *c, Host422Engine *e, const ntscsim_frame422 &f, int H,
@@ -373,77 +348,18 @@ static int h422_refresh_mirror(ntscsim_ctx *c, Host422Engine *e, Host422Engine::
     return NTSCSIM_OK;
 }
 
-// what the copy threads do for one launch: the staged results of its iterations, staging record -> caller planes
-static void h422_delivery_ops(const Host422Engine *e, const Host422Engine::Batch &b, std::vector<CopyOp> &ops)
-{
-    const int W = e->W, H = e->H, W2 = W / 2;
-    for (const auto &it : b.items) {
-        const uint8_t *st = e->hdn + e->dbytes * (size_t)it.slot;
-        const int n = h422_field_rows(H, it.it.field);
-        auto rows_out = [&](const ntscsim_frame422 &f, const uint8_t *s) {
-            for (int k = 0; k < 3; k++) {
-                const size_t rb = k ? (size_t)W2 : (size_t)W;
-                if (n > 0) ops.push_back({f.data[k] + (size_t)f.linesize[k] * it.it.field, s, 2 * (size_t)f.linesize[k], rb, rb, n});
-                s += rb * (size_t)n;
-            }
-        };
-        if (it.frm_how == 0) rows_out(it.it.frame, st + e->dn_frm);
-        if (it.serial && it.mflt && it.flt_how == 0) rows_out(it.it.filter, st + e->dn_flt);
-        if (it.it.out.data[0] && it.out_how == 0) {
-            const uint8_t *s = st + e->dn_out;
-            const int ch = h422_out_chroma_rows(H, it.it.out_mode);
-            for (int k = 0; k < 3; k++) {
-                const size_t rb = k ? (size_t)W2 : (size_t)W;
-                const int nr = k ? ch : H;
-                // (luma in two halves: the ops of a launch are the unit the copy threads share out)
-                if (k == 0 && nr >= 64) {
-                    const int h0 = nr / 2;
-                    ops.push_back({it.it.out.data[0], s, (size_t)it.it.out.linesize[0], rb, rb, h0});
-                    ops.push_back({it.it.out.data[0] + (size_t)it.it.out.linesize[0] * h0, s + rb * (size_t)h0, (size_t)it.it.out.linesize[0], rb, rb, nr - h0});
-                } else
-                    ops.push_back({it.it.out.data[k], s, (size_t)it.it.out.linesize[k], rb, rb, nr});
-                s += rb * (size_t)(k ? h422_out_chroma_alloc(H, it.it.out_mode) : H);
-            }
-        }
-    }
-}
-
-static int h422_retire_front(ntscsim_ctx *c, Host422Engine *e)
-{
-    Host422Engine::Batch &b = e->inflight.front();
-    int rc = b.rc;
-    if (b.launched_ok) {
-        bool ok;
-        if (b.posted) ok = e->dlv.wait(b.last);          // (the copy threads synchronised on the event)
-        else ok = hipEventSynchronize(b.done) == hipSuccess;
-        if (!ok) { (void)hipGetLastError(); c->err = "submit422: a launch failed on the device (hipEventSynchronize)"; rc = NTSCSIM_E_HIP; }
-    }
-    e->done_ticket = b.last;
-    if (b.done) e->ev_pool.push_back(b.done);
-    e->inflight.pop_front();
-    return rc;
-}
-
 static int h422_wait_ticket(ntscsim_ctx *c, uint64_t ticket)
 {
     Host422Engine *e = c->h422;
     if (!e) return ticket == NTSCSIM_TICKET_ALL ? NTSCSIM_OK : NTSCSIM_E_ARG;
-    if (ticket == NTSCSIM_TICKET_ALL) ticket = e->next_ticket - 1;
-    if (ticket == 0) return NTSCSIM_OK;
-    if (ticket >= e->next_ticket) return NTSCSIM_E_ARG;
-    int rc = NTSCSIM_OK;
-    if (!e->pending.empty() && ticket >= e->pending.front().ticket) {
+    auto launch = [&] {
         static const bool own_stream = std::getenv("NTSCSIM_SUBMIT422_DLVSTREAM") && std::getenv("NTSCSIM_SUBMIT422_DLVSTREAM")[0] == '1';   // developer A/B
         e->launch_for_wait = !own_stream;
         const int r = h422_launch(c);
         e->launch_for_wait = false;
-        if (r != NTSCSIM_OK) rc = r;
-    }
-    while (!e->inflight.empty() && e->inflight.front().first <= ticket) {
-        const int r = h422_retire_front(c, e);
-        if (r != NTSCSIM_OK && rc == NTSCSIM_OK) rc = r;
-    }
-    return rc;
+        return r;
+    };
+    return e->wait_ticket(c, "submit422", ticket, launch, [](Host422Engine::Batch &) {});
 }
 
 // Enqueue the pending iterations (all FAST, or one SERIAL) as one launch on the ctx's stream.
@@ -452,21 +368,12 @@ static int h422_launch(ntscsim_ctx *c)
     Host422Engine *e = c->h422;
     if (!e || e->pending.empty()) return NTSCSIM_OK;
     Host422Engine::Batch b;
-    b.first = e->pending.front().ticket;
-    b.last = e->pending.back().ticket;
-    b.items.swap(e->pending);
-    e->pending.clear();
-    const int n = (int)b.items.size();
-    auto finish = [&](int rc) {
-        b.rc = rc;
-        e->inflight.push_back(std::move(b));
-        return rc;
-    };
-    if (!e->ev_pool.empty()) { b.done = e->ev_pool.back(); e->ev_pool.pop_back(); }
-    else if (hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) {
+    auto finish = [&](int rc) { return e->close(b, rc); };
+    if (!e->open(b)) {
         c->err = "hipEventCreate failed";
         return finish(NTSCSIM_E_HIP);
     }
+    const int n = (int)b.items.size();
     const int W = e->W, H = e->H, W2 = W / 2;
     hipStream_t st = c->stream;
     // uploads of this launch's sources have been enqueued on the copy stream
@@ -627,7 +534,6 @@ static int h422_launch(ntscsim_ctx *c)
         c->latency_form = false;
         c->rng_pos = keep_pos;
         if (rc != NTSCSIM_OK) return finish(rc);
-        e->stats_two_pass++;
     }
     // Delivery -- output_frame's copy, the rows of the field, the download of what is staged -- runs on a stream of its own
     // behind the batch's kernels: the NEXT launch's kernels do not wait for it (batched iterations own their device frames
@@ -675,10 +581,12 @@ static int h422_launch(ntscsim_ctx *c)
     // (the synchronous call: the next call's setup kernel behind the event this one waits for -- ntscsim_hip.hip)
     if (e->launch_for_wait && n == 1 && sd == st) speculate_setup(c, st);
     if (any_staged) {
+        // the copy threads move the staged results, staging record -> caller planes, as soon as the event fires
+        const H422Record R{W, H, e->dbytes, e->dn_frm, e->dn_out, e->dn_flt};
         std::vector<CopyOp> ops;
-        h422_delivery_ops(e, b, ops);
-        e->dlv.post(c->device, b.done, std::move(ops), b.last);
-        b.posted = true;
+        for (const auto &it : b.items)
+            h422_delivery_ops(R, e->hdn + e->dbytes * (size_t)it.slot, it.it, it.serial && it.mflt, it.frm_how, it.flt_how, it.out_how, ops);
+        e->post(b, c->device, std::move(ops));
     }
     return finish(NTSCSIM_OK);
 }
@@ -691,24 +599,23 @@ static int h422_validate(const ntscsim_ctx *c, const ntscsim_loop422 *L)
     if (L->field > 1 || L->out_field > 1) return NTSCSIM_E_ARG;
     if (L->flags & ~(NTSCSIM_422_INTERLACED | NTSCSIM_422_TFF | NTSCSIM_422_SRC420 | NTSCSIM_422_SECOND | NTSCSIM_422_NOCOMP))
         return NTSCSIM_E_ARG;
-    auto planes = [&](const ntscsim_frame422 &f, int rows_c_min) -> int {
-        (void)rows_c_min;
+    auto planes = [&](const ntscsim_frame422 &f) -> int {
         for (int k = 0; k < 3; k++) {
             if (!f.data[k]) return NTSCSIM_E_ARG;
             if (f.linesize[k] < (k ? W / 2 : W)) return NTSCSIM_E_SIZE;
         }
         return NTSCSIM_OK;
     };
-    int rc = planes(L->frame, H);
+    int rc = planes(L->frame);
     if (rc != NTSCSIM_OK) return rc;
     if (L->src.data[0]) {
-        rc = planes(L->src, 0);
+        rc = planes(L->src);
         if (rc != NTSCSIM_OK) return rc;
         if (L->src_height < ((L->flags & NTSCSIM_422_INTERLACED) ? 4 : 2) || L->src_height > 16384) return NTSCSIM_E_SIZE;
     }
-    if (L->filter.data[0]) { rc = planes(L->filter, H); if (rc != NTSCSIM_OK) return rc; }
+    if (L->filter.data[0]) { rc = planes(L->filter); if (rc != NTSCSIM_OK) return rc; }
     if (L->out.data[0]) {
-        rc = planes(L->out, 0);
+        rc = planes(L->out);
         if (rc != NTSCSIM_OK) return rc;
         if (L->out_mode > NTSCSIM_OUT422_FRAME) return NTSCSIM_E_ARG;
     }
@@ -740,9 +647,10 @@ static int h422_submit(ntscsim_ctx *c, const ntscsim_loop422 *L, uint32_t flags,
     }
     // ring space: ticket t uses slot t mod nslots; its previous user and that one's pair partner must have retired
     const uint64_t t = e->next_ticket;
-    if (t + 1 > (uint64_t)e->ring && e->done_ticket < t + 1 - (uint64_t)e->ring) {
+    // (hence ring - 1)
+    if (const uint64_t holder = e->slot_holder((uint64_t)e->ring - 1)) {
         e->stats[7]++;
-        rc = h422_wait_ticket(c, t + 1 - (uint64_t)e->ring);
+        rc = h422_wait_ticket(c, holder);
         if (rc != NTSCSIM_OK) return rc;
     }
     const bool bkey = c->prm.black_key_level_feedback >= 0 && L->filter.data[0] != nullptr;
@@ -862,9 +770,9 @@ static int h422_submit(ntscsim_ctx *c, const ntscsim_loop422 *L, uint32_t flags,
         for (int k = 0; k < 3; k++) it.src_dev[k] = nullptr;
         int sslot = e->src_cur;
         if (!(flags & NTSCSIM_SUBMIT_SAME_SRC) || sslot < 0) {
-            sslot = (int)(e->src_ring_pos % (uint64_t)e->ring);
-            const uint64_t last = e->src_last_ticket[(size_t)sslot];
-            if (last > e->done_ticket) {
+            uint64_t last;
+            sslot = e->src_next((uint64_t)e->ring, &last);
+            if (last) {
                 rc = h422_wait_ticket(c, last);
                 if (rc != NTSCSIM_OK) return rc;
             }
@@ -896,8 +804,7 @@ static int h422_submit(ntscsim_ctx *c, const ntscsim_loop422 *L, uint32_t flags,
             }
             HIPCHK(c, hipMemcpyAsync(e->dsrc.p + e->sbytes * (size_t)sslot, hs, src_bytes, hipMemcpyHostToDevice, e->s_up));
             }
-            e->src_ring_pos++;
-            e->src_cur = sslot;
+            e->src_filled(sslot);
             e->stats[2]++;
         }
         it.sslot = sslot;
@@ -969,29 +876,16 @@ extern "C" void ntscsim_submit422_stats(const ntscsim_ctx *c, uint64_t out[8])
     for (int i = 0; i < 8; i++) out[i] = (c && c->h422) ? c->h422->stats[i] : 0;
 }
 
-// ntscsim_host_unpin() for the frames this engine has pinned: everything in flight is delivered first
-static int h422_host_unpin(ntscsim_ctx *c, const void *base)
+// ntscsim_host_unpin() and its relatives (ntscsim_pins.hip)
+static PinCache *h422_pins(ntscsim_ctx *c) { return c->h422 ? &c->h422->pins : nullptr; }
+static int h422_quiesce(ntscsim_ctx *c, int *wait_rc)
 {
     Host422Engine *e = c->h422;
     HIPCHK(c, hipSetDevice(c->device));
-    const int rc = h422_wait_ticket(c, NTSCSIM_TICKET_ALL);
+    *wait_rc = h422_wait_ticket(c, NTSCSIM_TICKET_ALL);
     if (e->s_up) HIPCHK(c, hipStreamSynchronize(e->s_up));
     if (e->s_dn) HIPCHK(c, hipStreamSynchronize(e->s_dn));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!base) pin_release_all(e->pins);
-    else (void)pin_release(e->pins, base);
     e->src_cur = -1;
-    return rc;
-}
-
-static bool h422_pins_overlap(ntscsim_ctx *c, uintptr_t p0, uintptr_t p1)
-{
-    if (!c->h422) return false;
-    for (auto &r : c->h422->pins.regs) if (p0 < r.p1 && r.p0 < p1) return true;
-    return false;
-}
-
-static void h422_set_pin_policy(ntscsim_ctx *c, int policy)
-{
-    if (c->h422) c->h422->pins.policy = policy;
+    return NTSCSIM_OK;
 }
