@@ -22,6 +22,8 @@
 // "lite", 16-byte aligned destination rows, composite plane (plus the head-switch displacement) within
 // 32-bit buffer offsets; VHS form: chroma noise + phase noise on, composite (not s-video) out.  Head-switch
 // displacements beyond W/10 samples (wrap-around inside the 1.1 W window) run the WR instantiation.
+#include "ntsc_pack.hpp"
+
 #pragma clang fp contract(off)
 
 namespace ntscsim {
@@ -406,7 +408,13 @@ DEV int cs_load(const CT &C, int x)
 DEV int opaque_v(int v) { asm volatile("" : "+v"(v)); return v; }
 DEV int opaque_s(int v) { return __builtin_amdgcn_readfirstlane(v); }   // (also proves uniformity)
 
-DEV int wave_up(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }   // wave_shr:1
+// the value of the lane above (wave_shr:1), 0 in lane 0.  Lane 0 has no source lane: with bound_ctrl it reads 0 by itself,
+// without it the 0 is an `old` operand that costs a v_mov_b32 per shift wherever the shift does not fold into its user
+#ifdef NTSC_WAVE_UP_OLD0            /* A/B: the zero as the old operand */
+DEV int wave_up(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
+#else
+DEV int wave_up(int v) { return __builtin_amdgcn_mov_dpp(v, 0x138, 0xf, 0xf, true); }
+#endif
 
 DEV uint32_t cvt_sat_u32(double x) { uint32_t r; asm("v_cvt_u32_f64 %0, %1" : "=v"(r) : "v"(x)); return r; }
 DEV uint32_t cvt_sat_u32(float x) { uint32_t r; asm("v_cvt_u32_f32 %0, %1" : "=v"(r) : "v"(x)); return r; }
@@ -430,10 +438,12 @@ DEV uint32_t yiq_to_bgra(int Yo, RT fU, RT fV)
     // the lower clamp is the conversion's own: v_cvt_u32 saturates (negative -> 0, too large -> 2^32 - 1), so
     // clamp((int)x >> 8, 0, 255) == min((unsigned)x >> 8, 255) for every x -- a full-rate v_min_u32 per channel in
     // place of a half-rate v_med3_i32 (C's conversion of a negative double to unsigned is undefined, hence the asm)
-    const uint32_t r = umin32(cvt_sat_u32((y + (RT(0.956) * fU)) + (RT(0.621) * fV)) >> 8, 255u);
-    const uint32_t g = umin32(cvt_sat_u32((y + (RT(-0.272) * fU)) + (RT(-0.647) * fV)) >> 8, 255u);
-    const uint32_t b = umin32(cvt_sat_u32((y + (RT(-1.106) * fU)) + (RT(1.703) * fV)) >> 8, 255u);
-    return ((r << 16) | b) | (g << 8);
+    // The shift and the pack are one step (ntsc_pack.hpp): clamp to 0xFFFF, then two v_perm_b32 gather byte 1 of the
+    // three words -- 5 VALU per pixel where shift, clamp and shift / or took 8.
+    const uint32_t r = cvt_sat_u32((y + (RT(0.956) * fU)) + (RT(0.621) * fV));
+    const uint32_t g = cvt_sat_u32((y + (RT(-0.272) * fU)) + (RT(-0.647) * fV));
+    const uint32_t b = cvt_sat_u32((y + (RT(-1.106) * fU)) + (RT(1.703) * fV));
+    return pack_bgra(r, g, b);
 #endif
 }
 
@@ -470,8 +480,8 @@ DEV int vcr_step(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C,
     T.D1.template push<pick1, neg1, false, CT::back, false, CT::anyxi>(pc, C.hi, -1, Yd, U, V, C.bmul, C.bshift, C.odd, C.mo);
     // chroma noise :1719-1735
     U += S.nU; V += S.nV;
-    S.nU = sdiv2(S.nU + (int)umod31(S.rng.template draw<2 * J>(T.rb, T.rb0), P.m_cnoise) - P.cnoise_k);
-    S.nV = sdiv2(S.nV + (int)umod31(S.rng.template draw<2 * J + 1>(T.rb, T.rb0), P.m_cnoise) - P.cnoise_k);
+    S.nU = noise_next(S.nU, S.rng.template draw<2 * J>(T.rb, T.rb0), P.m_cnoise, P.cnoise_k);
+    S.nV = noise_next(S.nV, S.rng.template draw<2 * J + 1>(T.rb, T.rb0), P.m_cnoise, P.cnoise_k);
     // chroma phase noise :1748-1762; (double)(int)d == trunc(d) up to the sign of zero, which
     // no later stage can observe
     const RT u = (RT)U, v = (RT)V;
@@ -568,8 +578,8 @@ DEV int vcr_edge(const DevParams &P, State<true, RT> &S, const CT &C, uint32_t *
     int fU = 0, fV = 0;
     if (in1) {
         U += S.nU; V += S.nV;
-        S.nU = sdiv2(S.nU + (int)umod31(S.rng.next(ring, C.lane), P.m_cnoise) - P.cnoise_k);
-        S.nV = sdiv2(S.nV + (int)umod31(S.rng.next(ring, C.lane), P.m_cnoise) - P.cnoise_k);
+        S.nU = noise_next(S.nU, S.rng.next(ring, C.lane), P.m_cnoise, P.cnoise_k);
+        S.nV = noise_next(S.nV, S.rng.next(ring, C.lane), P.m_cnoise, P.cnoise_k);
         const RT u = (RT)U, v = (RT)V;
         U = (int)((u * C.cosv) - (v * C.sinv));
         V = (int)((u * C.sinv) + (v * C.cosv));

@@ -104,7 +104,7 @@ DEV int step(const DevParams &P, EState<RT> &S, const EConst<RT> &C, uint32_t *r
     if (PRE) Y = preemphasis<RT>(S, C, Y);
     // luma noise :1632-1644
     Y += S.noise;
-    S.noise = sdiv2(S.noise + (int)umod31(S.rng.template draw<J>(rb, rb0), P.m_noise) - P.noise_k);
+    S.noise = noise_next(S.noise, S.rng.template draw<J>(rb, rb0), P.m_noise, P.noise_k);
     return Y;
 }
 
@@ -177,7 +177,7 @@ DEV void edge_step_px(const DevParams &P, EState<RT> &S, const EConst<RT> &C, ui
     int Y = Yx + chroma;
     if (PRE) Y = preemphasis<RT>(S, C, Y);
     Y += S.noise;
-    S.noise = sdiv2(S.noise + (int)umod31(S.rng.next(ring, C.lane), P.m_noise) - P.noise_k);
+    S.noise = noise_next(S.noise, S.rng.next(ring, C.lane), P.m_noise, P.noise_k);
     Y = gh.emit(x, Y);
     __builtin_amdgcn_raw_buffer_store_b32(Y, C.comp, C.vcol, (int)((unsigned)x * (unsigned)C.rowbytes), NTSC_COMP_STORE_AUX);
 }

@@ -34,6 +34,26 @@ DEV int sdiv2(int n) { return (n + (int)((unsigned)n >> 31)) >> 1; }   // C `/ 2
 DEV int sdiv4(int n) { return (n + ((n >> 31) & 3)) >> 2; }             // C `/ 4`
 DEV unsigned udiv31(unsigned n, const Magic31 &m) { return __umulhi(n, m.mul) >> m.shift; }
 DEV unsigned umod31(unsigned n, const Magic31 &m) { return n - udiv31(n, m) * m.div; }
+// One update of a noise accumulator, n <- (n + draw % div - k) / 2 (ffmpeg_ntsc.cpp:1632-1644, :1719-1735), with the
+// sum re-associated: n + draw - k is ONE three-operand add that does not wait for the multiply, and q * div comes off
+// it afterwards -- 8 VALU instead of 9 per draw, and one instruction less behind the v_mul_hi.  Same bits: the sums are
+// taken modulo 2^32 (unsigned), and the value itself never leaves the int range -- |n| <= k <= 2^20
+// (ntscsim_params_validate), draw < 2^31, 0 <= draw % div < div = 2k + 1, so |n + draw % div - k| <= 2^21; the one
+// intermediate beyond that, n + draw - k, lies in (-2^21, 2^31).
+DEV int noise_next(int n, unsigned draw, const Magic31 &m, int k)
+{
+#ifdef NTSC_NOISE_UPDATE_OLD        /* A/B: the modulus first, then the two adds */
+    return sdiv2(n + (int)umod31(draw, m) - k);
+#else
+    // (-k laundered through a scalar register, the sum through a vector one: otherwise the compiler subtracts k on its
+    //  own and folds the rest back into q * div + k, draw - that, + n.  k is wave-uniform: the negation is scalar work.)
+    int nk = -k;
+    asm("" : "+s"(nk));
+    unsigned t = ((unsigned)n + draw) + (unsigned)nk;
+    asm("" : "+v"(t));
+    return sdiv2((int)(t - udiv31(draw, m) * m.div));
+#endif
+}
 DEV int sdivm(int n, const Magic31 &m)                                   // C `/ d`, d > 0
 {
     if (m.mul == 0) return n;                  // d == 1 has no 32-bit magic (wave-uniform branch)

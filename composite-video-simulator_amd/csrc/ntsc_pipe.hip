@@ -334,8 +334,8 @@ DEV void sep_role(const DevParams &P, const Row &R, const int *__restrict__ comp
         const int x1 = t - 7;
         if (x1 >= 0 && x1 < W) {
             U += nU; V += nV;                                                       // chroma noise :1719-1735
-            nU = sdiv2(nU + (int)umod31(rng.next(ring, lane), P.m_cnoise) - P.cnoise_k);
-            nV = sdiv2(nV + (int)umod31(rng.next(ring, lane), P.m_cnoise) - P.cnoise_k);
+            nU = noise_next(nU, rng.next(ring, lane), P.m_cnoise, P.cnoise_k);
+            nV = noise_next(nV, rng.next(ring, lane), P.m_cnoise, P.cnoise_k);
         }
         ab[slot_of(t, SKT) * 64 + lane] = u32x2{(uint32_t)U, (uint32_t)V};
         publish(fl + F_AB_P, t + 1);
@@ -357,8 +357,8 @@ DEV void sep_role(const DevParams &P, const Row &R, const int *__restrict__ comp
             int Yd, U, V;                                                                         \
             S1.template push<pick1, neg1, false, BK, false, XA>(pc[J], C.hi, -1, Yd, U, V, C.bmul, C.bshift, C.odd, C.mo); \
             U += nU; V += nV;                                                                     \
-            nU = sdiv2(nU + (int)umod31(rng.template draw<2 * (J)>(rb, rb0), P.m_cnoise) - P.cnoise_k);     \
-            nV = sdiv2(nV + (int)umod31(rng.template draw<2 * (J) + 1>(rb, rb0), P.m_cnoise) - P.cnoise_k); \
+            nU = noise_next(nU, rng.template draw<2 * (J)>(rb, rb0), P.m_cnoise, P.cnoise_k);     \
+            nV = noise_next(nV, rng.template draw<2 * (J) + 1>(rb, rb0), P.m_cnoise, P.cnoise_k); \
             PRE;                                                                                  \
             o[(J) * 64] = u32x2{(uint32_t)U, (uint32_t)V};                                        \
             NTSC_STEP_SCHED_BARRIER();                                                            \
