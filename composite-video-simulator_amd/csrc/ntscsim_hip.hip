@@ -26,7 +26,7 @@
 #include "ntsc422_fused.hip"
 #include "ntsc_scale.hip"
 #include "ntsc_float.hpp"       // NTSCSIM_MODE_FLOAT: its kernels are a translation unit of their own
-#include "ntsc_stage.hpp"       // the frameblend, colorkey and average_delay stages (ntscsim_blend_* / _key_* / _avg_*): likewise, csrc/ntsc_{blend,key,avg}.hip
+#include "ntsc_stage.hpp"       // the frameblend, colorkey, average_delay and scanimate stages (ntscsim_blend_* / _key_* / _avg_* / _scan_*): likewise, csrc/ntsc_{blend,key,avg,scan}.hip
 
 using namespace ntscsim;
 
@@ -221,10 +221,11 @@ struct ntscsim_ctx {
     ntscsim::BlendState *blend = nullptr;   // ntscsim_blend_bind(): state of the frameblend stage (csrc/ntsc_blend.hip)
     ntscsim::KeyState *key = nullptr;       // ntscsim_key_bind(): state of the colorkey stage (csrc/ntsc_key.hip)
     ntscsim::AvgState *avg = nullptr;       // ntscsim_avg_bind(): state of the average_delay stage (csrc/ntsc_avg.hip)
+    ntscsim::ScanState *scan = nullptr;     // ntscsim_scan_bind(): state of the scanimate stage (csrc/ntsc_scan.hip)
 };
 ntscsim::CtxStageView ntscsim::ctx_stage_view(ntscsim_ctx *c)
 {
-    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg};
+    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan};
 }
 static void submit_engine_destroy(ntscsim_ctx *c);
 static int sub_wait_ticket(ntscsim_ctx *c, uint64_t ticket);
@@ -477,6 +478,7 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     if (c->blend) { ntscsim::blend_state_destroy(c->blend); c->blend = nullptr; }
     if (c->key) { ntscsim::key_state_destroy(c->key); c->key = nullptr; }
     if (c->avg) { ntscsim::avg_state_destroy(c->avg); c->avg = nullptr; }
+    if (c->scan) { ntscsim::scan_state_destroy(c->scan); c->scan = nullptr; }
     for (Geometry *e : c->geoms) {
         e->lskip.release(); e->pskip.release(); e->jrow.release(); e->sstart.release(); e->jwarm.release();
         delete e;
@@ -589,10 +591,12 @@ extern "C" void ntscsim_debug_no_fast_decode(ntscsim_ctx *c, int on)
 extern "C" int ntscsim_debug_last_kernels(const ntscsim_ctx *c, char *out, size_t cap)
 {
     if (!c || !out || cap == 0) return NTSCSIM_E_ARG;
-    const size_t n = std::min(cap - 1, c->kernels.size());
-    std::memcpy(out, c->kernels.data(), n);
+    std::string kernels = c->kernels;
+    if (c->scan) ntscsim::scan_kernels_tap(c->scan, c->device, kernels);       // "+spill" comes from a device counter
+    const size_t n = std::min(cap - 1, kernels.size());
+    std::memcpy(out, kernels.data(), n);
     out[n] = 0;
-    return (int)c->kernels.size();
+    return (int)kernels.size();
 }
 
 extern "C" void ntscsim_debug_set_warmup(ntscsim_ctx *c, int luma_draws, int chroma_draws)

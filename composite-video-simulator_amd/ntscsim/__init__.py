@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -673,6 +673,104 @@ class FrameAverager(_LayerStage):
         Frames of one list share a row stride.  Returns (ring_index, field) behind the last frame, to be handed to the
         next call.  Enqueues; does not synchronise."""
         return self._clip(ring, layers, out, ring_index, field, stream)
+
+
+class Scanimator:
+    """The scanimate stage (ntscsim_scan_*): the CRT raster re-scan effect of ffmpeg_scanimate.  `flags` are the tool's
+    switches, e.g. ("-inntsc", "-tvstd", "pal"); width / height: the output size (the tool has no -height).  A source
+    frame may have any size: the tool's (params.src_width x src_height) is only what its own input scaler produces.
+    sim: share the context of a FieldSimulator; otherwise a context of its own is created.  torch is used only for
+    device memory and streams.  Frames are uint8 [H, W, 4] with contiguous pixels and any row stride."""
+
+    def __init__(self, flags=(), width=None, height=None, sim=None, device=0, params=None):
+        self.params = params if params is not None else _capi.make_scan_params(flags, width=width, height=height)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        self._call("bind", C.byref(self.params))
+
+    def _call(self, what, *args):
+        name = "ntscsim_scan_%s" % what
+        self.sim._chk(getattr(self._lib, name)(self.sim._h, *args), name)
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    def _descs(self, jobs, ptr, linesize):
+        w, h = int(self.params.output_width), int(self.params.output_height)
+        arr = (_capi.ScanDesc * max(1, len(jobs)))()
+        for d, (dst, src, fieldno) in zip(arr, jobs):
+            if tuple(dst.shape) != (h, w, 4):           # the descriptor carries no destination size: the bound one is meant
+                raise NtscsimError(_capi.E_SIZE, "scan: destination %r is not the bound %dx%d" % (tuple(dst.shape), w, h))
+            assert len(src.shape) == 3 and src.shape[2] == 4
+            d.dst_dev, d.dst_linesize = ptr(dst), linesize(dst)
+            d.src_dev, d.src_linesize, d.src_width, d.src_height = ptr(src), linesize(src), src.shape[1], src.shape[0]
+            d.fieldno = int(fieldno)
+        return arr
+
+    def scan_frames(self, jobs, stream=None):
+        """ntscsim_scan_frames_device: jobs = [(dst, src, fieldno), ...] of torch uint8 CUDA tensors.  Rows field ..
+        of dst are written, field = (fieldno & 1) ^ 1.  Enqueues; does not synchronise."""
+        arr = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("frames_device", arr, len(jobs), C.c_void_p(stream))
+
+    def scan_frames_host(self, jobs):
+        """ntscsim_scan_frames_host: the same on numpy uint8 arrays.  Synchronous."""
+        arr = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self._call("frames_host", arr, len(jobs))
+
+    def scan_clip(self, srcs, out, fieldno=0, stream=None):
+        """ntscsim_scan_clip_device: srcs / out = lists of T torch uint8 CUDA frames (one source size and one row stride
+        per list); out[t] becomes the field of fieldno + t, row 0 of the field == 1 outputs zeroed.  Returns the
+        field number behind the last one.  Enqueues; does not synchronise."""
+        T = len(out)
+        assert len(srcs) == T
+        w, h = int(self.params.output_width), int(self.params.output_height)
+        for o in out:
+            if tuple(o.shape) != (h, w, 4):
+                raise NtscsimError(_capi.E_SIZE, "scan: output %r is not the bound %dx%d" % (tuple(o.shape), w, h))
+        assert len(set((tuple(f.shape), f.stride(0)) for f in srcs)) <= 1 and len(set(o.stride(0) for o in out)) <= 1
+        sp = (C.c_void_p * max(1, T))(*[f.data_ptr() for f in srcs])
+        op = (C.c_void_p * max(1, T))(*[o.data_ptr() for o in out])
+        fn = C.c_uint64(int(fieldno))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        sh, sw = (srcs[0].shape[0], srcs[0].shape[1]) if T else (1, 1)
+        self._call("clip_device", sp, srcs[0].stride(0) if T else 4, sw, sh, op, out[0].stride(0) if T else 4 * w, T,
+                   C.byref(fn), C.c_void_p(stream))
+        return int(fn.value)
+
+    def last_kernels(self):
+        """Synchronises: whether k_scan_splat spilled is read from a device counter."""
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
+
+    def debug_keep_raster(self, on=True):
+        self._call("debug_keep_raster", 1 if on else 0)
+
+    def debug_raster(self):
+        """The accumulator plane of the last descriptor of the last call (numpy uint32 [H, W]), before the >> 1 and
+        the clamp; debug_keep_raster() first."""
+        import numpy as np
+        out = np.empty((int(self.params.output_height), int(self.params.output_width)), np.uint32)
+        self._call("debug_raster", C.c_void_p(out.ctypes.data))
+        return out
+
+    def debug_set_window_rows(self, rows):
+        """Caps the rows of the splat kernel's on-chip window (0: everything spills; negative: the default)."""
+        self._call("debug_set_window_rows", int(rows))
+
+    def debug_spill(self):
+        """(workgroups of the last call that drew a dot, those of them that spilled)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._call("debug_spill", C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
 
 
 class Pool:

@@ -54,6 +54,10 @@ EXPORTS = (
     "ntscsim_key_frames_host", "ntscsim_key_debug_lane_state", "ntscsim_key_debug_set_bits_limit",
     "ntscsim_avg_params_init", "ntscsim_avg_params_free", "ntscsim_avg_params_add_layer", "ntscsim_avg_parse_argv",
     "ntscsim_avg_bind", "ntscsim_avg_frames_device", "ntscsim_avg_clip_device", "ntscsim_avg_frames_host",
+    "ntscsim_scan_params_init", "ntscsim_scan_parse_argv", "ntscsim_scan_effect", "ntscsim_scan_field_of",
+    "ntscsim_scan_bind", "ntscsim_scan_frames_device", "ntscsim_scan_clip_device", "ntscsim_scan_frames_host",
+    "ntscsim_scan_debug_keep_raster", "ntscsim_scan_debug_raster", "ntscsim_scan_debug_set_window_rows",
+    "ntscsim_scan_debug_spill",
 )
 
 
@@ -309,6 +313,22 @@ class AvgDesc(C.Structure):
 
 
 AVG_FAST_LAYERS = 4
+
+
+class ScanParams(C.Structure):
+    """struct ntscsim_scan_params -- keep in lock-step with include/ntscsim.h."""
+    _fields_ = [("struct_size", C.c_uint32), ("output_width", C.c_int32), ("output_height", C.c_int32),
+                ("tv_standard", C.c_int32), ("field_rate_num", C.c_int32), ("field_rate_den", C.c_int32),
+                ("input_ntsc", C.c_int32), ("output_pal", C.c_int32), ("use_422_colorspace", C.c_int32),
+                ("n_inputs", C.c_int32), ("src_width", C.c_int32), ("src_height", C.c_int32), ("_pad", C.c_int32),
+                ("last_input_path", C.c_char_p), ("output_path", C.c_char_p)]
+
+
+class ScanDesc(C.Structure):
+    """struct ntscsim_scan_desc"""
+    _fields_ = [("dst_dev", C.c_void_p), ("dst_linesize", C.c_int32), ("src_linesize", C.c_int32),
+                ("src_dev", C.c_void_p), ("src_width", C.c_int32), ("src_height", C.c_int32), ("fieldno", C.c_uint64)]
+
 
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
@@ -579,6 +599,31 @@ def lib():
     L.ntscsim_avg_clip_device.restype = C.c_int
     L.ntscsim_avg_frames_host.argtypes = [C.c_void_p, C.POINTER(AvgDesc), C.c_int]
     L.ntscsim_avg_frames_host.restype = C.c_int
+    L.ntscsim_scan_params_init.argtypes = [C.POINTER(ScanParams)]
+    L.ntscsim_scan_params_init.restype = None
+    L.ntscsim_scan_parse_argv.argtypes = [C.POINTER(ScanParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ntscsim_scan_parse_argv.restype = C.c_int
+    L.ntscsim_scan_effect.argtypes = [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.ntscsim_scan_effect.restype = None
+    L.ntscsim_scan_field_of.argtypes = [C.c_uint64]
+    L.ntscsim_scan_field_of.restype = C.c_uint32
+    L.ntscsim_scan_bind.argtypes = [C.c_void_p, C.POINTER(ScanParams)]
+    L.ntscsim_scan_bind.restype = C.c_int
+    L.ntscsim_scan_frames_device.argtypes = [C.c_void_p, C.POINTER(ScanDesc), C.c_int, C.c_void_p]
+    L.ntscsim_scan_frames_device.restype = C.c_int
+    L.ntscsim_scan_clip_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_void_p]
+    L.ntscsim_scan_clip_device.restype = C.c_int
+    L.ntscsim_scan_frames_host.argtypes = [C.c_void_p, C.POINTER(ScanDesc), C.c_int]
+    L.ntscsim_scan_frames_host.restype = C.c_int
+    L.ntscsim_scan_debug_keep_raster.argtypes = [C.c_void_p, C.c_int]
+    L.ntscsim_scan_debug_keep_raster.restype = C.c_int
+    L.ntscsim_scan_debug_raster.argtypes = [C.c_void_p, C.c_void_p]
+    L.ntscsim_scan_debug_raster.restype = C.c_int
+    L.ntscsim_scan_debug_set_window_rows.argtypes = [C.c_void_p, C.c_int]
+    L.ntscsim_scan_debug_set_window_rows.restype = C.c_int
+    L.ntscsim_scan_debug_spill.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.ntscsim_scan_debug_spill.restype = C.c_int
     _lib = L
     return L
 
@@ -689,4 +734,24 @@ def make_avg_params(flags=(), require_io=False, width=None, height=None):
         p.width = int(width)
     if height is not None:
         p.height = int(height)
+    return p
+
+
+def make_scan_params(flags=(), require_io=False, width=None, height=None):
+    """ntscsim_scan_params from ffmpeg_scanimate's switches (ffmpeg_scanimate.cpp parse_argv :643).  width / height
+    override the output size after parsing (the tool has no -height).  The returned struct keeps the argv strings alive
+    (last_input_path / output_path point into them)."""
+    L = lib()
+    p = ScanParams()
+    L.ntscsim_scan_params_init(C.byref(p))
+    argv = [b"ffmpeg_scanimate"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    p._argv = arr
+    rc = L.ntscsim_scan_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
+    if rc != OK:
+        raise NtscsimError(rc, "scan parse_argv(%r)" % (list(flags),))
+    if width is not None:
+        p.output_width = int(width)
+    if height is not None:
+        p.output_height = int(height)
     return p

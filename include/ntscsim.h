@@ -708,7 +708,9 @@ void ntscsim_debug_no_fast_decode(ntscsim_ctx *ctx, int on);
  * trace without the argument list (e.g. "k_field_setup;k_row_states;k_encode_fast<double>;
  * k_decode_fast<true,double>").  Returns the length of the full list (it is truncated to cap-1
  * characters), or NTSCSIM_E_ARG.  The parity tests assert on it so that a specialised form cannot
- * silently stop being the one that runs. */
+ * silently stop being the one that runs.  Behind a scan call (ntscsim_scan_*) the list names k_scan_splat, and
+ * whether it is "k_scan_splat+spill" is read from a device counter: the call then selects the ctx's device and
+ * SYNCHRONISES it (hipDeviceSynchronize) before it copies the counter back; otherwise it touches no device. */
 int ntscsim_debug_last_kernels(const ntscsim_ctx *ctx, char *out, size_t cap);
 
 /* Test hook (pure host arithmetic, no ctx): 1 when a batch of n_fields fields of width x height may take
@@ -1168,6 +1170,112 @@ int  ntscsim_avg_clip_device(ntscsim_ctx *ctx, void *const *ring_dev, int ring_l
  * goes through pinned staging of the ctx.  Synchronous.  Same bytes as the device call.  A destination must be disjoint
  * from every other frame of the call that is not the very same (pointer, linesize): NTSCSIM_E_ARG otherwise. */
 int  ntscsim_avg_frames_host(ntscsim_ctx *ctx, const ntscsim_avg_desc *descs, int n);
+
+/* ---- scanimate: the CRT raster re-scan effect (ffmpeg_scanimate.cpp) ----
+ * A camera re-scans a picture drawn on a CRT.  Every source sample (two per source pixel) becomes a phosphor
+ * dot whose position, size and brightness come from a per-field raster warp -- trapezoid, vertical rotate,
+ * vertical stretch, sine "diffuse", 180 fields each -- and the dot is splatted as a cone into a 32-bit
+ * accumulator plane, which is then halved, clamped and written out as grey BGRA.  Mapping:
+ *
+ *   globals + preset_* :601-635 + parse_argv() :643-723, source size :190-197 | ntscsim_scan_params, _init(), _parse_argv()
+ *   effect / ef_field :865-867, (current & 1) ^ 1 :1224                       | ntscsim_scan_effect(), ntscsim_scan_field_of()
+ *   phosphor_dot() :817-854, scanimate_modify_raster() :859-891,
+ *   composite_layer() :894-974                                               | ntscsim_scan_frames_device() / _frames_host()
+ *   the field loop :1195-1244, one input                                     | ntscsim_scan_clip_device()
+ *
+ * With several -i the tool runs composite_layer() once per input onto the same frame, and every call overwrites
+ * all of rows field .. height-1: the output is the LAST input's.  The stage therefore takes one source per
+ * output, and ntscsim_scan_params keeps the last -i.  Decoding, scaling (sws_scale) to the source size,
+ * encoding and the audio pass-through stay with the caller.  Frames are BGRA in device
+ * memory; only the green byte of a source pixel is read.
+ */
+typedef struct ntscsim_scan_params {
+    uint32_t struct_size;            /* = sizeof(ntscsim_scan_params)                                      */
+    int32_t  output_width, output_height;   /* 720 x 480 (preset_NTSC), the -tvstd presets, -width          */
+    int32_t  tv_standard;            /* 0 NTSC, 1 PAL, 2 720p60, 3 1080p60 (-tvstd)                        */
+    int32_t  field_rate_num, field_rate_den;    /* 60000 / 1001, PAL 50 / 1                                */
+    int32_t  input_ntsc;             /* -inntsc: the source is an interlaced 480-line picture, one field per output */
+    int32_t  output_pal;             /* set by preset_PAL only                                             */
+    int32_t  use_422_colorspace;     /* false (-422 / -420); recorded, not acted on                        */
+    int32_t  n_inputs;               /* number of -i                                                       */
+    int32_t  src_width, src_height;  /* derived :190-197 after all of argv: 600 x 800; -inntsc 480 x 480, 480 x 576 when output_pal */
+    int32_t  _pad;
+    const char *last_input_path;     /* the last -i (points into argv), NULL if none                       */
+    const char *output_path;         /* -o                                                                 */
+} ntscsim_scan_params;
+
+void ntscsim_scan_params_init(ntscsim_scan_params *p);
+/* Mirror of parse_argv() :643-723: -i -o -width -422 -420 -inntsc -tvstd pal|ntsc|720p60|1080p60, -h / -help (any
+ * number of leading '-'); -width goes through strtoul with base 0 and the tool's cast to int, and changes the width
+ * only.  argv[0] is the program name.  NTSCSIM_E_FLAG (the tool's "return 1") for -width < 32, an unknown standard,
+ * an unknown switch, a bare word and a missing value -- the tool hands the NULL behind a trailing -tvstd to
+ * strcmp(); here that is the flag error too.  require_io != 0 applies the "No output file / No input files"
+ * checks (:713-720).  src_width / src_height are derived when the whole of argv has been read, as the tool derives
+ * them when it opens its inputs: the order of -inntsc and -tvstd does not matter.  NTSCSIM_E_HELP for -h / -help. */
+int  ntscsim_scan_parse_argv(ntscsim_scan_params *p, int argc, const char *const *argv, int require_io);
+/* :865-867: *effect = (fieldno / 180) % 4 (0 trapezoid, 1 rotate, 2 stretch, 3 sine) and *ef_field = fieldno % 180,
+ * in the tool's types: the quotient is cut to an unsigned int before it is used, so from fieldno = 180 * 2^32 on both
+ * differ from that and ef_field can exceed 179.  Either pointer may be NULL. */
+void ntscsim_scan_effect(uint64_t fieldno, uint32_t *effect, uint32_t *ef_field);
+/* :1224: the `field` the tool hands to composite_layer() for field number fieldno, (fieldno & 1) ^ 1. */
+uint32_t ntscsim_scan_field_of(uint64_t fieldno);
+
+/* Snapshot the parameters on a ctx (any ntscsim_params it was created with).  Waits for scan work in flight on the
+ * ctx.  NTSCSIM_E_SIZE for an output or source size below 1 x 1 or above 65536 in either direction, and when
+ * 2 * src_width * src_height or output_width * output_height reaches 2^31 (the tool's unsigned int products must
+ * not wrap). */
+int  ntscsim_scan_bind(ntscsim_ctx *ctx, const ntscsim_scan_params *p);
+
+typedef struct ntscsim_scan_desc {
+    void       *dst_dev;             /* device pointer, BGRA frame of the bound output size                 */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                    */
+    int32_t     src_linesize;        /* bytes, >= 4*src_width, multiple of 4                                */
+    const void *src_dev;             /* device pointer, BGRA frame; never written                           */
+    int32_t     src_width, src_height;   /* any size within the bind limits: the params' are the tool's defaults, not a limit */
+    uint64_t    fieldno;             /* the tool's field counter `current`: field = (fieldno & 1) ^ 1       */
+} ntscsim_scan_desc;
+/*
+ * composite_layer() :894-974 for `n` output fields.  Writes bytes 0 .. 4*width of rows field .. height-1 of the
+ * destination and nothing else: row 0 when field == 1, the row padding and the bytes around the frame are not
+ * touched (the tool's memset :1196 is the caller's).  All frame pointers are DEVICE pointers; `descs` is host
+ * memory and is consumed by the call.  Enqueued on hip_stream (NULL: the ctx's own stream), returns without
+ * synchronising.  Descriptors take effect in order.  Bit-identical to the tool: the accumulator is an integer sum,
+ * every fp64 expression keeps the tool's order (no contraction), and the tool's sin / cos are computed by the
+ * host's libm -- per field, and for the sine effect once per source size as two tables over the source samples.
+ * Kernels: k_scan_splat (a workgroup sums the dots of a tile of source samples in an on-chip window and flushes
+ * the window to the ctx's accumulator plane; a dot whose box leaves the window is added to the plane directly --
+ * ntscsim_debug_last_kernels() then says k_scan_splat+spill) and k_scan_resolve.  The ctx owns up to 8 accumulator
+ * planes: up to 8 descriptors of a call are in flight together.
+ * The descriptor carries no destination size: dst_dev is ASSUMED to hold the bound output_width x output_height
+ * with rows of dst_linesize bytes, unchecked -- the call cannot refuse a destination of another size (the Python
+ * veneer, which sees the tensor's shape, does, with NTSCSIM_E_SIZE).
+ * NTSCSIM_E_ARG: a NULL pointer, a source that overlaps the destination, no ntscsim_scan_bind() before.
+ * NTSCSIM_E_SIZE: a linesize below 4*width or not a multiple of 4, a pointer that is not a multiple of 4, a source
+ * size outside the bind limits.
+ */
+int  ntscsim_scan_frames_device(ntscsim_ctx *ctx, const ntscsim_scan_desc *descs, int n, void *hip_stream);
+/*
+ * The tool's field loop :1195-1244 with one input, for T fields of a clip resident in device memory: output t is
+ * the field of *fieldno + t from src_dev[t] (src_w x src_h, rows of src_linesize bytes) in out_dev[t].  Row 0 of a
+ * field == 1 output is written as zeros, as the tool's memset leaves it; the row padding is not touched.
+ * *fieldno advances by T.  Asynchronous like ntscsim_scan_frames_device(); outputs must not overlap each other
+ * or a source (NTSCSIM_E_ARG).
+ */
+int  ntscsim_scan_clip_device(ntscsim_ctx *ctx, const void *const *src_dev, int src_linesize, int src_w, int src_h,
+                              void *const *out_dev, int out_linesize, int T, uint64_t *fieldno, void *hip_stream);
+/* ntscsim_scan_frames_device() on HOST frames, through pinned staging of the ctx.  Synchronous.  Same bytes as the
+ * device call: the rows and bytes the device call leaves alone keep what the host frame held. */
+int  ntscsim_scan_frames_host(ntscsim_ctx *ctx, const ntscsim_scan_desc *descs, int n);
+/* Debug taps.  keep_raster(on): k_scan_resolve clears the accumulator as it reads it, so while `on` the plane of the
+ * last descriptor of every call is copied aside in front of it.  raster(): that copy -- width * height words, before
+ * the >> 1 and the clamp -- to host memory; synchronises; NTSCSIM_E_ARG when nothing was kept.
+ * set_window_rows(rows): caps the rows of k_scan_splat's on-chip window (0: every dot takes the spill path; a
+ * negative value restores the default).  spill(): workgroups of the last call that drew a dot, and how many of them
+ * spilled; synchronises.  All require ntscsim_scan_bind() and are kept across later binds. */
+int  ntscsim_scan_debug_keep_raster(ntscsim_ctx *ctx, int on);
+int  ntscsim_scan_debug_raster(ntscsim_ctx *ctx, uint32_t *out_host);
+int  ntscsim_scan_debug_set_window_rows(ntscsim_ctx *ctx, int rows);
+int  ntscsim_scan_debug_spill(ntscsim_ctx *ctx, uint64_t *workgroups, uint64_t *spilled);
 
 #ifdef __cplusplus
 }
