@@ -23,6 +23,7 @@
 // 32-bit buffer offsets; VHS form: chroma noise + phase noise on, composite (not s-video) out.  Head-switch
 // displacements beyond W/10 samples (wrap-around inside the 1.1 W window) run the WR instantiation.
 #include "ntsc_pack.hpp"
+#include "ntsc_rowend_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -269,6 +270,13 @@ struct DemodS {
     int e1, e2, o1, o2;           // raw chroma of the last two positions of the pick parity / of the other parity
     int y0, y1, y2, y3, y4;       // box-filtered luma at q-5 .. q-1
     int ieP, qeP, ieN, qeN;
+    DEV void init()
+    {
+        c1 = pA = pB = 0;
+        e1 = e2 = o1 = o2 = 0;
+        y0 = y1 = y2 = y3 = y4 = 0;
+        ieP = qeP = ieN = qeN = 0;
+    }
     DEV void from(const DemodR &D, bool pick_next)
     {
         c1 = D.c2; pA = D.c2 + D.c1; pB = D.c1 + D.c0;
@@ -689,49 +697,17 @@ DEV bool edge_step(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t 
     return true;
 }
 
-// Steady-state loop: every stage strictly inside the row.  Starts at t = SKT (mod 4), 4 pixels per
-// iteration, the next iteration's composite samples requested before the current ones are used.
+// The steady loop itself: 4 pixels per iteration from t (= SKT mod 4) while t + 4 <= t_end, every stage strictly inside
+// the row.  T = the separators and the luma box in their steady form, pc / pl = the composite samples of positions
+// t .. t+3 (requested by the caller), sbase = ring slot of the first draw (a multiple of 8).  On return pc / pl hold what
+// was requested for the four positions behind the last iteration (a position at or beyond W: not to be used).
 template <bool VHS, int DPH, class RT, class CT>
-DEV int steady(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t *ring, uint32_t *lring,
-               uint32_t *ostage, const unsigned long long *orow, uint32_t *drow, bool is_out, int t)
+DEV int steady_run(const DevParams &P, State<VHS, RT> &S, Steady &T, const CT &C, uint32_t *ring,
+                   uint32_t *ostage, const unsigned long long *orow, uint32_t *drow, bool is_out, int t, int t_end,
+                   int (&pc)[4], int (&pl)[4], int &sbase)
 {
-    // last steady position: every composite sample inside the row (t < W) and no raw chroma tail
-    // needed yet (x1 = t - 7 < W - d)
-    const int t_end = C.W - (C.d > 7 ? C.d - 7 : 0);
     const int SKT = C.SKT, LOFF = C.LOFF, lane = C.lane;
-    if (t + 4 > t_end) return t;
-    // the rand() ring's static offsets need the iteration's first slot on a multiple of 8 (LaneRand32::init arranges
-    // that for a row wider than the pipeline is deep; otherwise the guarded steps do the whole row)
-    if (VHS && (S.rng.pos & 7)) return t;
-    // the separators and the luma box in their steady form: the next position is t; the first separator (x1 = t - 7 =
-    // DPH mod 4) picks there iff DPH is odd, the second one / the only one of the non-VHS form (x3 = 4n + 1) always
-    Steady T;
-    constexpr bool pick3_next = ((1 + CT::SH) & 1) != 0;        // x3 = 1 + SH (mod 4) at J = 0
-    T.D1.from(S.D1, VHS ? (DPH & 1) != 0 : pick3_next);
-    T.D2.from(S.D2, pick3_next);
-    T.lc1 = S.l2; T.lpA = S.l2 + S.l1; T.lpB = S.l1 + S.l0;
-    if constexpr (CT::fullout) {
-        // (x3 = 4 (mod 4) at J = 0: unrolled position J rewrites the slot of positions = J (mod 4); read before the
-        //  loop)
-#pragma unroll
-        for (int q = 0; q < 4; q++) T.yd[q] = (int)C.xs[q * 64];
-        T.ud[0] = (int)S.Uf2[0]; T.ud[1] = (int)S.Uf2[1];
-    }
-    // (the separator in front of the TV stages carries the dropout mask on everything it has picked: the guarded steps
-    //  apply it to their outputs instead, so what they left behind is masked here)
-    DemodS &Dout = (VHS && !CT::svideo) ? T.D2 : T.D1;
-    if (!(VHS && CT::svideo)) { Dout.ieP &= C.dm; Dout.qeP &= C.dm; Dout.ieN &= C.dm; Dout.qeN &= C.dm; }
-    int sbase = VHS ? S.rng.pos : 0;
-    // samples in flight per stream: one unrolled iteration
-    constexpr int PD = 4;
-    int pc[PD], pl[PD];
-#pragma unroll
-    for (int j = 0; j < PD; j++) { pc[j] = cs_load(C, t + j); pl[j] = VHS ? cs_load<NTSC_COMP_LOAD2_AUX>(C, t + j - LOFF) : 0; }
-    // (The VCR's luma path reads every composite sample a second time, LOFF = 5 + d positions behind the chroma path.
-    //  Tried in round 4: an LDS ring of 20 + 3 slots that keeps each sample until the luma path wants it -- the second
-    //  pass over the plane disappears from the L2's memory side, but the ring takes the workgroup from 14 to 20 KB of
-    //  LDS, eight decoder workgroups then fill a CU's 160 KB, and the encoder waves of the neighbouring steps no longer
-    //  fit beside them: kernel 0.766 -> 0.776 ms, four steps in flight 769k -> 755k fields/s.  Not shipped.)
+    constexpr int PD = 4;     // samples in flight per stream: one unrolled iteration
     // Where the registers allow it (non-VHS form) the next iteration's samples are requested at the
     // top of the current one: a whole iteration of arithmetic hides the HBM latency.  The one-launch
     // VHS form has no registers to spare and reloads each sample right after its step consumed it
@@ -812,6 +788,53 @@ DEV int steady(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t *rin
     }
     NTSC_FAST_FLUSH()
 #undef NTSC_FAST_FLUSH
+    return t;
+}
+
+// Steady-state loop: every stage strictly inside the row.  Starts at t = SKT (mod 4), 4 pixels per
+// iteration, the next iteration's composite samples requested before the current ones are used.
+template <bool VHS, int DPH, class RT, class CT>
+DEV int steady(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t *ring, uint32_t *lring,
+               uint32_t *ostage, const unsigned long long *orow, uint32_t *drow, bool is_out, int t)
+{
+    // last steady position: every composite sample inside the row (t < W) and no raw chroma tail
+    // needed yet (x1 = t - 7 < W - d)
+    const int t_end = C.W - (C.d > 7 ? C.d - 7 : 0);
+    const int LOFF = C.LOFF;
+    if (t + 4 > t_end) return t;
+    // the rand() ring's static offsets need the iteration's first slot on a multiple of 8 (LaneRand32::init arranges
+    // that for a row wider than the pipeline is deep; otherwise the guarded steps do the whole row)
+    if (VHS && (S.rng.pos & 7)) return t;
+    // the separators and the luma box in their steady form: the next position is t; the first separator (x1 = t - 7 =
+    // DPH mod 4) picks there iff DPH is odd, the second one / the only one of the non-VHS form (x3 = 4n + 1) always
+    Steady T;
+    constexpr bool pick3_next = ((1 + CT::SH) & 1) != 0;        // x3 = 1 + SH (mod 4) at J = 0
+    T.D1.from(S.D1, VHS ? (DPH & 1) != 0 : pick3_next);
+    T.D2.from(S.D2, pick3_next);
+    T.lc1 = S.l2; T.lpA = S.l2 + S.l1; T.lpB = S.l1 + S.l0;
+    if constexpr (CT::fullout) {
+        // (x3 = 4 (mod 4) at J = 0: unrolled position J rewrites the slot of positions = J (mod 4); read before the
+        //  loop)
+#pragma unroll
+        for (int q = 0; q < 4; q++) T.yd[q] = (int)C.xs[q * 64];
+        T.ud[0] = (int)S.Uf2[0]; T.ud[1] = (int)S.Uf2[1];
+    }
+    // (the separator in front of the TV stages carries the dropout mask on everything it has picked: the guarded steps
+    //  apply it to their outputs instead, so what they left behind is masked here)
+    DemodS &Dout = (VHS && !CT::svideo) ? T.D2 : T.D1;
+    if (!(VHS && CT::svideo)) { Dout.ieP &= C.dm; Dout.qeP &= C.dm; Dout.ieN &= C.dm; Dout.qeN &= C.dm; }
+    int sbase = VHS ? S.rng.pos : 0;
+    // samples in flight per stream: one unrolled iteration
+    constexpr int PD = 4;
+    int pc[PD], pl[PD];
+#pragma unroll
+    for (int j = 0; j < PD; j++) { pc[j] = cs_load(C, t + j); pl[j] = VHS ? cs_load<NTSC_COMP_LOAD2_AUX>(C, t + j - LOFF) : 0; }
+    // (The VCR's luma path reads every composite sample a second time, LOFF = 5 + d positions behind the chroma path.
+    //  Tried in round 4: an LDS ring of 20 + 3 slots that keeps each sample until the luma path wants it -- the second
+    //  pass over the plane disappears from the L2's memory side, but the ring takes the workgroup from 14 to 20 KB of
+    //  LDS, eight decoder workgroups then fill a CU's 160 KB, and the encoder waves of the neighbouring steps no longer
+    //  fit beside them: kernel 0.766 -> 0.776 ms, four steps in flight 769k -> 755k fields/s.  Not shipped.)
+    t = steady_run<VHS, DPH, RT, CT>(P, S, T, C, ring, ostage, orow, drow, is_out, t, t_end, pc, pl, sbase);
     // back to the guarded steps' layout (t has advanced by a multiple of 4: the same position phases as at the entry)
     T.D1.to(S.D1, VHS ? (DPH & 1) != 0 : pick3_next);
     T.D2.to(S.D2, pick3_next);
@@ -826,6 +849,192 @@ DEV int steady(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t *rin
     S.l2 = T.lc1; S.l1 = T.lpA - T.lc1; S.l0 = T.lpB - S.l1; S.lsum = S.l0 + S.l1 + S.l2;
     if (VHS) S.rng.pos = sbase;
     return t;
+}
+
+// ------------------------------------------------------------------ row ends in groups of four (round 8)
+// Pipeline fill and drain of the rows the steady loop enters, in the steady loop's own layout: groups of four positions
+// on its phase (t = SKT mod 4, the first and the last group partial), unrolled position J with the pick and sign phases
+// it has in step(), the separators and the luma box as DemodS / Steady from the row's first position to its last (every
+// delay line register renaming, no DemodR <-> DemodS conversion), the rand() draws at static ring offsets, the composite
+// samples requested one group ahead.  What the one-position form (edge_step / vcr_edge) decides per position with selects
+// is here a wave-uniform branch around the stage's block, taken from the schedule of ntsc_rowend_plan.hpp
+// (rowend::position; swept on the host by tests/rowend_plan_check.cpp).  END = false: the fill (t < SKT: only the lower
+// bounds of the stages can bind); END = true: the drain (only the upper ones, and the row-end rules: the m guard :1550 and
+// the x >= xe zeroing :1553 of the separators, the raw chroma tail :1830, the TV filter's last sample :1419).
+// Forms: the composite -vhs forms with an even scanline phase and the TV output filter (plain, WR, BK).  The S-Video, XA,
+// FO and non-VHS forms keep the one-position form (decode_fast_body says so where it chooses).
+template <int DPH, int J, bool END, class RT, class CT>
+DEV uint32_t group_step(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C, const rowend::Pos &q,
+                        int t, int pc, int pl)
+{
+    const int W = C.W;                                       // (q, t: wave-uniform)
+    constexpr bool pick1 = ((DPH + J) & 1) != 0, neg1 = ((DPH + J) & 3) == 3;
+    constexpr bool pick3 = ((J + 1) & 1) != 0, neg3 = ((J + 1) & 3) == 3;
+    int Yd, U = 0, V = 0;
+    int fU = 0, fV = 0;
+    // A delay line renames only where its push is unconditional: a branch around a push turns every shift into a v_mov
+    // again (the skipped path keeps the old assignment).  So the separators and the luma box push at EVERY position of
+    // the fill and -- the first separator apart, whose state is dead for the drain's last 8 + d positions -- of the
+    // drain: outside a stage's range they push the zeros its input reads there, onto state that is still zero (fill:
+    // a zero input leaves zero state zero) or dead already (drain).  The branches go around what updates in place: the
+    // filter poles, the noise accumulators and the rand() draws.
+    if (!END || q.sep1) {
+        if constexpr (END) {
+            // m guard: the pick at odd x1 stands iff x1 + 2 + xi < W (xi = 0 / 2 per lane); everything from xe on is zeroed
+            const int x1 = t - 7;
+            const int mg = pick1 ? ((x1 + 2 - W + (C.mL & 2)) >> 31) : -1;
+            T.D1.template push<pick1, neg1, false, CT::back, true, false>(pc, C.hi, mg, Yd, U, V, C.bmul, C.bshift);
+            if (x1 >= C.xe) { U = 0; V = 0; }
+        } else {
+            T.D1.template push<pick1, neg1, false, CT::back, false, false>(pc, C.hi, -1, Yd, U, V, C.bmul, C.bshift);
+        }
+    }
+    if (q.in1) {
+        U += S.nU; V += S.nV;
+        S.nU = noise_next(S.nU, S.rng.template draw<2 * J>(T.rb, T.rb0), P.m_cnoise, P.cnoise_k);
+        S.nV = noise_next(S.nV, S.rng.template draw<2 * J + 1>(T.rb, T.rb0), P.m_cnoise, P.cnoise_k);
+        const RT u = (RT)U, v = (RT)V;
+        const RT Ud = rtrunc<RT>((u * C.cosv) - (v * C.sinv));
+        const RT Vd = rtrunc<RT>((u * C.sinv) + (v * C.cosv));
+        fU = (int)S.vcU.push(Ud, C.a_vc);
+        fV = (int)S.vcV.push(Vd, C.a_vc);
+        if (END && q.tail_wr) {
+            const int x1 = t - 7;
+            C.tailU[(size_t)(x1 & 15) * C.rstride] = (int)Ud;
+            C.tailU[(size_t)(16 + (x1 & 15)) * C.rstride] = (int)Vd;
+        }
+    }
+    int yb;
+    {
+        const int lp = pl + T.lc1;
+        yb = sdiv4s(lp + T.lpB);
+        T.lc1 = pl; T.lpB = T.lpA; T.lpA = lp;
+    }
+    int c2 = 0;
+    if (q.in2) {
+        if (END && q.tail_rd) {
+            const int x2 = t - 7 - C.d;
+            fU = C.tailU[(size_t)(x2 & 15) * C.rstride];
+            fV = C.tailU[(size_t)(16 + (x2 & 15)) * C.rstride];
+        }
+        RT m2;
+        RT s = S.vl.push((RT)yb, C.a_vl, m2);
+        s += S.vpre.hp(s, m2, C.a_vl) * RT(1.6);
+        const RT s0 = rtrunc<RT>(s);
+        const RT ts = S.sh.push(s0, C.a_sh);
+        const int Y = (int)(s0 + ((s0 - ts) * C.sharp2));
+        // (each position re-modulates either U or V: the other component's blend is dead code, as in vcr_step)
+        const int Ub = ((wave_up(fU) & C.bA) + fU + C.bC) >> C.bC;
+        const int Vb = ((wave_up(fV) & C.bA) + fV + C.bC) >> C.bC;
+        const int chroma = (J & 1) ? Vb : Ub;                 // x2 = J (mod 4)
+        const int mm = (J & 2) ? C.mNL : C.mL;
+        c2 = Y + ((chroma ^ mm) - mm);
+    }
+    int Y3 = 0, U3 = 0, V3 = 0;
+    {
+        if constexpr (END) {
+            const int x3 = t - 14 - C.d;
+            const int mg = pick3 ? (((x3 + 2 - W + (C.mL & 2)) >> 31) & C.dm) : -1;
+            T.D2.template push<pick3, neg3, true, false, true, false>(c2, C.hi, mg, Y3, U3, V3);
+            if (x3 >= C.xe) { U3 = 0; V3 = 0; }
+        } else {
+            T.D2.template push<pick3, neg3, true, false, true, false>(c2, C.hi, C.dm, Y3, U3, V3);
+        }
+    }
+    uint32_t px = 0;
+    if (q.tv) {
+        // composite_lowpass_tv :1399-1427 (delay 1).  The position behind the row (x3 = W) puts out the row's last pixel,
+        // which keeps the filter's input at x3 = W - 1 -- zero: W - 1 >= xe
+        RT fUd = 0, fVd = 0;
+        const int Yo = S.Yprev;
+        if (q.in3) {
+            fUd = rtrunc<RT>(S.oU.push((RT)U3, C.a_tv));
+            fVd = rtrunc<RT>(S.oV.push((RT)V3, C.a_tv));
+            S.Yprev = Y3;
+        }
+        if (q.out) px = yiq_to_bgra<RT>(Yo, fUd, fVd);
+    }
+    return px;
+}
+
+// the groups [t0, t_stop) (t0 = SKT mod 4).  pc / pl: the samples of the first group on entry (positions outside the row
+// hold 0), of the group at t_stop on return.
+template <int DPH, bool END, class RT, class CT>
+DEV void group_run(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C, const rowend::Plan &RP,
+                   uint32_t *ring, uint32_t *ostage, uint32_t *drow, bool is_out, int t0, int t_stop,
+                   int (&pc)[4], int (&pl)[4], int &sbase)
+{
+    const int lane = C.lane, W = C.W;
+    for (; t0 < t_stop; t0 += 4) {
+        T.rb = ring + sbase * 64 + lane;
+        T.rb0 = sbase == 0;
+        sbase = (sbase + 8) & 31;
+        uint32_t o[4] = {0u, 0u, 0u, 0u};
+        bool burst = false, rest = false;
+#define NTSC_GROUP_STEP(J)                                                                        \
+        {                                                                                         \
+            const int tj = t0 + J;          /* (a partial group's positions outside the row: nothing is live) */ \
+            const rowend::Pos q = rowend::position(RP, tj);                                       \
+            o[J] = group_step<DPH, J, END, RT, CT>(P, S, T, C, q, tj, pc[J], pl[J]);              \
+            burst = burst || q.burst; rest = rest || q.rest;                                      \
+            const int tn = tj + 4;          /* the next group's samples, where the schedule has them inside the row */ \
+            const rowend::Pos qn = rowend::position(RP, tn);                                      \
+            pc[J] = qn.load_c ? cs_load(C, tn) : 0;                                               \
+            pl[J] = qn.load_l ? cs_load<NTSC_COMP_LOAD2_AUX>(C, tn - RP.LOFF) : 0;                \
+            NTSC_STEP_SCHED_BARRIER();                                                            \
+        }
+        NTSC_GROUP_STEP(0)
+        NTSC_GROUP_STEP(1)
+        NTSC_GROUP_STEP(2)
+        NTSC_GROUP_STEP(3)
+#undef NTSC_GROUP_STEP
+        if constexpr (END) {
+            // stage the group's pixels as the steady loop does (xo0 = a multiple of 4; the last group's pixels behind
+            // the row are never stored); a complete 16-pixel burst, or the row's rest, leaves from the lane's own slots
+            // with plain stores, exactly as in the one-position drain (decode_fast_body) -- not as the steady loop's
+            // cooperative 64-byte streaming stores (NTSC_OUT_STORE).  The drain's stores were left as they
+            // were: at most two bursts per row leave here (against ~43 from the loop at W = 720), too few to crowd the
+            // luma re-read out of the L2, which is what the streaming form is for; it was not measured either way
+            const int xo0 = t0 - RP.SKT;
+            const int sub = (xo0 >> 2) & 3;
+            *reinterpret_cast<uint4 *>(&ostage[lane * 20 + sub * 4]) = make_uint4(o[0], o[1], o[2], o[3]);
+            const int xb = xo0 & ~15;
+            if (burst) {
+                if (is_out) {
+                    const uint4 *sp = reinterpret_cast<const uint4 *>(&ostage[lane * 20]);
+                    g_v4u_ptr dp = (g_v4u_ptr)(drow + xb);
+                    const uint4 a = sp[0], b = sp[1], c4 = sp[2], d4 = sp[3];
+                    dp[0] = to_v4u(a); dp[1] = to_v4u(b); dp[2] = to_v4u(c4); dp[3] = to_v4u(d4);
+                }
+            } else if (rest && is_out) {
+                for (int x = xb; x < W; x++) ((g_u32_ptr)drow)[x] = ostage[lane * 20 + (x - xb)];
+            }
+        }
+    }
+}
+
+
+// one row, fill to drain, in groups (rowend::grouped rows only).  DPH = d mod 4, as for steady().
+template <int DPH, class RT, class CT>
+DEV void grouped_row(const DevParams &P, State<true, RT> &S, const CT &C, const rowend::Plan &RP, uint32_t *ring,
+                     uint32_t *ostage, const unsigned long long *orow, uint32_t *drow, bool is_out)
+{
+    Steady T;
+    T.D1.init(); T.D2.init();
+    T.lc1 = T.lpA = T.lpB = 0;
+    int sbase = rowend::group_slot(S.rng.pos, RP.g0);
+    int pc[4], pl[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {          // (the luma path's first sample is LOFF > 4 positions away)
+        pc[j] = rowend::position(RP, RP.g0 + j).load_c ? cs_load(C, RP.g0 + j) : 0;
+        pl[j] = 0;
+    }
+    group_run<DPH, false, RT, CT>(P, S, T, C, RP, ring, ostage, drow, is_out, RP.g0, RP.st0, pc, pl, sbase);
+    const int t = steady_run<true, DPH, RT, CT>(P, S, T, C, ring, ostage, orow, drow, is_out, RP.st0, RP.t_end, pc, pl, sbase);
+    // (the steady loop's last requests may lie behind the row: those read 0)
+#pragma unroll
+    for (int j = 0; j < 4; j++) pc[j] = rowend::position(RP, t + j).load_c ? pc[j] : 0;
+    group_run<DPH, true, RT, CT>(P, S, T, C, RP, ring, ostage, drow, is_out, t, RP.glast + 4, pc, pl, sbase);
 }
 
 } // namespace fastdec
@@ -898,8 +1107,10 @@ DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *
     C.xe = (W & 1) ? W - 1 : W - 2;
     C.lane = lane;
     C.d = VHS ? P.cdelay : 0;
-    C.SKT = (VHS ? (CT::svideo ? 8 : 15) + C.d : 8) + CT::SH;
-    C.LOFF = 5 + C.d;
+    // the row's schedule (ntsc_rowend_plan.hpp): the pipeline's depth and the luma path's offset of every form come from it
+    const rowend::Plan RP = rowend::make_plan(W, C.d, VHS, SV, FO);
+    C.SKT = RP.SKT;                   // (VHS ? (SV ? 8 : 15) + d : 8) + SH
+    C.LOFF = RP.LOFF;                 // 5 + d
     C.mL = opaque_v(C.hi ? -1 : 0);
     C.mNL = opaque_v(~C.mL);
     const bool vb = VHS && P.vblend && P.ntsc;
@@ -948,11 +1159,30 @@ DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *
     if (VHS) {
         // the pipeline fill draws twice at every step from x1 = 0 on (t = 7 .. SKT - 1): place the window so that the
         // steady loop's first draw lands on a slot that is a multiple of 8
-        const int fill_draws = 2 * (C.SKT - 7);
-        S.rng.init(ring, rs_chroma + rc, P.Rpad, lane, (-(31 + fill_draws)) & 7);
+        S.rng.init(ring, rs_chroma + rc, P.Rpad, lane, rowend::ring_offset(C.SKT));
         S.nU = n0_u[rc]; S.nV = n0_v[rc];
     }
 
+    // ---------------- the rows the steady loop enters: fill, loop and drain in groups of four (group_run) -- the composite
+    // -vhs forms with even scanline phases and the TV output filter (plain, WR, BK).  The S-Video, XA, FO and non-VHS forms
+    // keep the one-position form below for every row, as do rows too narrow for the loop.
+#ifdef NTSC_ROWENDS_OLD            /* A/B: the one-position row ends of round 7 everywhere */
+    constexpr bool GROUPS = false;
+#else
+    constexpr bool GROUPS = VHS && !SV && !XA && !FO;
+#endif
+    if constexpr (GROUPS) {
+        // (one instantiation per position phase of the first separator, d mod 4, as for steady(); the tape speeds give
+        //  d = 9, 12, 14 -- a delay of 3 mod 4 has no grouped code and takes the one-position form)
+        if (rowend::grouped(RP) && (C.d & 3) != 3) {
+            switch (C.d & 3) {
+                case 0: grouped_row<0, RT, CT>(P, S, C, RP, ring, ostage, orow, drow, is_out); break;
+                case 1: grouped_row<1, RT, CT>(P, S, C, RP, ring, ostage, orow, drow, is_out); break;
+                default: grouped_row<2, RT, CT>(P, S, C, RP, ring, ostage, orow, drow, is_out); break;
+            }
+            return;
+        }
+    }
     const int SKT = C.SKT;
     const int total = W + SKT;
     int t = 0;
