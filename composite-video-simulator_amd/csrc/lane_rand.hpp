@@ -40,6 +40,9 @@ struct LaneRand {
 // Jump-ahead: state advanced by the polynomial c (x^n mod x^31 - x^28 - 1) given the 61-word
 // extension w of the starting window:  out[j] = sum_k c[k] * w[j+k].  Fully unrolled so that
 // everything stays in registers (private arrays with dynamic indices would live in scratch).
+// Each product and its add are ONE v_mad_u64_u32 whose low word is kept (the sums are taken modulo 2^32): 961
+// instructions where v_mul_lo_u32 and the adds the compiler pairs into v_add3_u32 were 1,423, and k_row_states, which is
+// little else, 34.4 us where that form took 38.3 (profiles/r09_rowstates_ab.txt; -DNTSC_JUMP61_MUL_ADD: that form, A/B).
 DEV void jump61(const uint32_t *__restrict__ c, const uint32_t *__restrict__ w, uint32_t (&o)[31])
 {
     uint32_t cc[31], ww[61];
@@ -49,9 +52,17 @@ DEV void jump61(const uint32_t *__restrict__ c, const uint32_t *__restrict__ w, 
     for (int i = 0; i < 61; i++) ww[i] = w[i];
 #pragma unroll
     for (int j = 0; j < 31; j++) {
+#ifndef NTSC_JUMP61_MUL_ADD
+        unsigned long long acc = 0, carry;
+#pragma unroll
+        for (int k = 0; k < 31; k++)
+            asm("v_mad_u64_u32 %0, %1, %2, %3, %0" : "+v"(acc), "=s"(carry) : "v"(cc[k]), "v"(ww[j + k]));
+        o[j] = (uint32_t)acc;
+#else
         uint32_t acc = 0;
 #pragma unroll
         for (int k = 0; k < 31; k++) acc += cc[k] * ww[j + k];
         o[j] = acc;
+#endif
     }
 }

@@ -33,7 +33,7 @@ struct DevParams {
     double a_in_i, a_in_q, a_tv, a_vl, a_vc, a_sh;
     double sharpen;                  // vhs_out_sharpen
     int src_al16, dst_al16;          // all src/dst rows 16-byte aligned
-    int warm_luma, warm_chroma;      // warm-up draws used by k_row_states
+    int warm_luma, warm_chroma;      // draws k_row_states looks back at first (ntsc_rowstate_lookback.hpp)
     int variant;                     // 0 ffmpeg_ntsc (BGRA), 1 ffmpeg_to_composite (YUV422P)
     int ghost_taps, ghost_delay[4], ghost_gain[4];   // extension (not in the reference)
 };
@@ -53,9 +53,7 @@ static_assert(sizeof(FieldDev) == 288, "FieldDev layout");
 struct GeomDev {
     const uint32_t *lskip;    // [2 par][31]  x^(draws before the head-switch draws)
     const uint32_t *pskip;    // [2 par][31]  x^(draws before the phase-noise / dropout draws)
-    const uint32_t *jrow;     // [2 stream][2 par][Lslot][31]  x^(row start - warm-up)
-    const int32_t  *jwarm;    // [2 stream][2 par][Lslot]      warm-up draws (== start -> exact)
-    const uint32_t *sstart;   // [2 stream][2 par][31]         x^(stream start within the field)
+    const uint32_t *jrow;     // [2 stream][2 par][Lslot][31]  x^(row start)
     const double   *ptab;     // [2*pnoise_k+1][2]             cos,sin of noise*pi/100
 };
 

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ntsc_device.hpp"
+#include "ntsc_rowstate_lookback.hpp"
 
 #pragma clang fp contract(off)
 
@@ -249,11 +250,41 @@ __global__ __launch_bounds__(64) void k_field_setup(DevParams P, GeomDev G,
 
 // =============================================================================== k_row_states
 // rand() state and noise accumulator(s) at the first pixel of every scanline.
-// The accumulators are carried across rows in the reference (noise = (noise + d - k) / 2, C
-// truncation), but the map is monotone in `noise` and halves the distance, so running it from
-// both extremes (-k and +k) over a short warm-up pins the exact value as soon as the two
-// trajectories meet.  If they have not met after the warm-up (probability ~2^-warm) the lane
-// recomputes serially from the start of the field -- exact by construction either way.
+// The jump lands on the row's first draw: its 31 output words are the window the consumer loads, and the raw words of
+// the last 31 draws before the row.  The accumulators are carried across rows in the reference (noise = (noise + d -
+// k) / 2, C truncation), but the map is monotone in `noise` and halves the distance, so running it from both extremes
+// (-k and +k) over those last draws pins the exact value as soon as the two trajectories meet
+// (ntsc_rowstate_lookback.hpp: the last 24 draws for luma, all 31 for chroma, straight from the registers).  A wave
+// with a lane that has not met walks that lane's window further back in LDS, 32 draws at a time, until it has met or
+// has reached the stream's first draw of the field -- exact by construction either way, and bounded by the wave's own
+// rows.  The same walk serves the waves whose rows have fewer draws behind them than the look-back (narrow frames) and
+// the look-back lengths of the test hook (ntscsim_debug_set_warmup).
+template <bool CHROMA>
+DEV void row_lookback(const DevParams &P, const uint32_t (&st)[31], uint32_t *ring, int lane, long long start,
+                      rowstate::Acc &a)
+{
+    constexpr int M0 = CHROMA ? rowstate::LOOK_CHROMA : rowstate::LOOK_LUMA;
+    const int K = CHROMA ? P.cnoise_k : P.noise_k;
+    const Magic31 M = CHROMA ? P.m_cnoise : P.m_noise;
+    const int m0 = CHROMA ? P.warm_chroma : P.warm_luma;
+    // the window's own draws do where the configured look-back is the default one and every row of the wave has that
+    // many draws behind it (or none: the field's first row)
+    const bool window = m0 == M0 && !__builtin_amdgcn_ballot_w64(start != 0 && start < M0);
+    bool open = true;
+    if (window) {
+        rowstate::from_window<M0, CHROMA>(st, M, K, start <= M0, a);
+        if (start == 0) a.init(true, CHROMA, K);
+        open = !a.settled();
+    }
+    if (!__builtin_amdgcn_ballot_w64(open)) return;
+    rowstate::Ring r;
+    r.col = ring + lane; r.stride = 64;
+    r.load(st);
+    const long long m = rowstate::clip(start, m0);
+    if (!window) rowstate::replay(r, m, start, CHROMA, M, K, a);
+    (void)rowstate::extend(r, m, start, CHROMA, M, K, a);
+}
+
 DEV void row_states_body(const DevParams &P, const GeomDev &G, const FieldDev *__restrict__ fields,
                          uint32_t *__restrict__ rs_luma, int *__restrict__ n0_luma,
                          uint32_t *__restrict__ rs_chroma, int *__restrict__ n0_u, int *__restrict__ n0_v,
@@ -269,58 +300,21 @@ DEV void row_states_body(const DevParams &P, const GeomDev &G, const FieldDev *_
     if (k >= field_rows(P, par)) return;
 
     const size_t jidx = ((size_t)(stream * 2 + par) * P.Lslot + k);
-    const int warm = G.jwarm[jidx];
-    const int K = stream == 0 ? P.noise_k : P.cnoise_k;
-    const Magic31 M = stream == 0 ? P.m_noise : P.m_cnoise;
     // draws made before this row: luma 1/pixel; chroma 2/pixel (BGRA path) or 2/chroma sample
     const long long cpr = P.variant ? 2ll * (P.W / 2) : 2ll * P.W;
     const long long start = stream == 0 ? (long long)k * P.W : cpr * k;
-    const bool exact = (long long)warm == start;   // warm-up reaches the start of the stream
 
     uint32_t st[31];
-    SetupRand g;
     jump61(G.jrow + jidx * 31, fd.rng, st);
-    g.init(ring, st, lane);
-
-    int lo0 = exact ? 0 : -K, hi0 = exact ? 0 : K;   // luma / U
-    int lo1 = stream == 0 ? 0 : lo0, hi1 = stream == 0 ? 0 : hi0;   // V (chroma stream only)
-    if (stream == 0) {
-        for (int i = 0; i < warm; i++) {
-            const int d = (int)umod31(g.next(ring, lane), M) - K;
-            lo0 = sdiv2(lo0 + d); hi0 = sdiv2(hi0 + d);
-        }
-    } else {
-        for (int i = 0; i < warm; i += 2) {
-            int d = (int)umod31(g.next(ring, lane), M) - K;
-            lo0 = sdiv2(lo0 + d); hi0 = sdiv2(hi0 + d);
-            d = (int)umod31(g.next(ring, lane), M) - K;
-            lo1 = sdiv2(lo1 + d); hi1 = sdiv2(hi1 + d);
-        }
-    }
-    if (lo0 != hi0 || lo1 != hi1) {
-        // not pinned: serial replay from the first draw of this stream in this field
-        jump61(G.sstart + (size_t)(stream * 2 + par) * 31, fd.rng, st);
-        g.init(ring, st, lane);
-        lo0 = lo1 = 0;
-        if (stream == 0) {
-            for (long long i = 0; i < start; i++)
-                lo0 = sdiv2(lo0 + (int)umod31(g.next(ring, lane), M) - K);
-        } else {
-            for (long long i = 0; i < start; i += 2) {
-                lo0 = sdiv2(lo0 + (int)umod31(g.next(ring, lane), M) - K);
-                lo1 = sdiv2(lo1 + (int)umod31(g.next(ring, lane), M) - K);
-            }
-        }
-    }
+    rowstate::Acc a;
+    if (stream == 0) row_lookback<false>(P, st, ring, lane, start, a);
+    else row_lookback<true>(P, st, ring, lane, start, a);
 
     uint32_t *rs = stream == 0 ? rs_luma : rs_chroma;
-    int q = g.slot;
-    for (int j = 0; j < 31; j++) {
-        rs[(size_t)j * P.Rpad + rho] = ring[q * 64 + lane];
-        q = (q == 30) ? 0 : q + 1;
-    }
-    if (stream == 0) n0_luma[rho] = lo0;
-    else { n0_u[rho] = lo0; n0_v[rho] = lo1; }
+#pragma unroll
+    for (int j = 0; j < 31; j++) rs[(size_t)j * P.Rpad + rho] = st[j];
+    if (stream == 0) n0_luma[rho] = a.lo0;
+    else { n0_u[rho] = a.lo0; n0_v[rho] = a.lo1; }
 }
 
 __global__ __launch_bounds__(64) void k_row_states(DevParams P, GeomDev G,

@@ -67,6 +67,10 @@ struct KeyClip {                         // the clip forms: the ring behind the 
 };
 
 // ---- k_key_draw -----------------------------------------------------------------------------------------------
+// (this kernel's starting window is the job's, the same for every lane: the compiler keeps it in scalar registers and
+//  folds it into v_mul_lo_u32 as such.  The one-instruction product of the simulator's kernels takes vector operands
+//  only -- 100 registers here instead of 66 -- and was not measured in this kernel, which keeps the form it has)
+#define NTSC_JUMP61_MUL_ADD
 #include "lane_rand.hpp"   // LaneRand, jump61 (shared with the simulator's kernels)
 
 __global__ __launch_bounds__(KEY_DRAW_THREADS) void k_key_draw(const KeyJob *__restrict__ jobs, const uint32_t *__restrict__ polys,

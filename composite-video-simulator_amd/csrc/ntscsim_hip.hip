@@ -86,8 +86,7 @@ struct DevBuf {
 struct Geometry {
     int W = 0, H = 0, variant = 0;
     bool valid = false;
-    DevBuf<uint32_t> lskip, pskip, jrow, sstart;
-    DevBuf<int32_t> jwarm;
+    DevBuf<uint32_t> lskip, pskip, jrow;
     uint64_t calls[2] = {0, 0};
 };
 
@@ -329,8 +328,8 @@ static void fill_dev_params(const ntscsim_params &p, DevParams &D)
     D.a_vc = alpha_for(chroma_cut);
     D.a_sh = alpha_for(luma_cut * 4);
     D.sharpen = p.vhs_out_sharpen;
-    D.warm_luma = 64;
-    D.warm_chroma = 128;
+    D.warm_luma = rowstate::LOOK_LUMA;
+    D.warm_chroma = rowstate::LOOK_CHROMA;
     D.ghost_taps = p.ghost_taps;
     for (int k = 0; k < 4; k++) { D.ghost_delay[k] = p.ghost_delay[k]; D.ghost_gain[k] = p.ghost_gain[k]; }
 }
@@ -352,7 +351,7 @@ static int build_geometry(ntscsim_ctx *c, int W, int H, const DevParams &D)
         // a context that cycles through more than 16 geometries: drain the device, then start over
         HIPCHK(c, hipDeviceSynchronize());
         for (Geometry *e : c->geoms) {
-            e->lskip.release(); e->pskip.release(); e->jrow.release(); e->sstart.release(); e->jwarm.release();
+            e->lskip.release(); e->pskip.release(); e->jrow.release();
             delete e;
         }
         c->geoms.clear();
@@ -367,8 +366,7 @@ static int build_geometry(ntscsim_ctx *c, int W, int H, const DevParams &D)
     const uint64_t cdraws = D.variant ? 2ull * (uint64_t)(W / 2) : 2ull * (uint64_t)W;
     const int Lslot = (H + 1) / 2;
     const int Lp[2] = {(H + 1) / 2, H / 2};
-    std::vector<uint32_t> lskip(2 * 31), pskip(4 * 31), sstart(4 * 31), jrow((size_t)4 * Lslot * 31);
-    std::vector<int32_t> jwarm((size_t)4 * Lslot);
+    std::vector<uint32_t> lskip(2 * 31), pskip(4 * 31), jrow((size_t)4 * Lslot * 31);
     const RandPoly xW = rand_poly_pow((uint64_t)W), x2W = rand_poly_pow(cdraws);
     for (int par = 0; par < 2; par++) {
         // draws before the 4 head-switch draws, and before the per-row phase-noise draws
@@ -387,36 +385,27 @@ static int build_geometry(ntscsim_ctx *c, int W, int H, const DevParams &D)
         for (int s = 0; s < 2; s++) {
             const uint64_t off = s == 0 ? 0 : chroma_stream_offset(c->prm, W, Lp[par]);
             const RandPoly so = rand_poly_pow(off);
-            std::memcpy(&sstart[(size_t)(s * 2 + par) * 31], so.c, sizeof(so.c));
-            const uint64_t warm_max = s == 0 ? (uint64_t)D.warm_luma : (uint64_t)D.warm_chroma;
             const uint64_t per_row = s == 0 ? (uint64_t)W : cdraws;
             const RandPoly &step = s == 0 ? xW : x2W;
             RandPoly cur = so;
             uint64_t cur_e = off;
             for (int k = 0; k < Lslot; k++) {
-                const uint64_t start = per_row * (uint64_t)k;
-                const uint64_t warm = start < warm_max ? start : warm_max;
-                const uint64_t e = off + start - warm;
+                const uint64_t e = off + per_row * (uint64_t)k;      // the row's first draw
                 if (e != cur_e) {
                     cur = (e - cur_e == per_row) ? rand_poly_mul(cur, step) : rand_poly_pow(e);
                     cur_e = e;
                 }
                 const size_t idx = (size_t)(s * 2 + par) * Lslot + k;
                 std::memcpy(&jrow[idx * 31], cur.c, sizeof(cur.c));
-                jwarm[idx] = (int32_t)warm;
             }
         }
     }
     HIPCHK(c, g.lskip.ensure(lskip.size()));
     HIPCHK(c, g.pskip.ensure(pskip.size()));
-    HIPCHK(c, g.sstart.ensure(sstart.size()));
     HIPCHK(c, g.jrow.ensure(jrow.size()));
-    HIPCHK(c, g.jwarm.ensure(jwarm.size()));
     HIPCHK(c, upload_table(g.lskip.p, lskip.data(), lskip.size() * 4));
     HIPCHK(c, upload_table(g.pskip.p, pskip.data(), pskip.size() * 4));
-    HIPCHK(c, upload_table(g.sstart.p, sstart.data(), sstart.size() * 4));
     HIPCHK(c, upload_table(g.jrow.p, jrow.data(), jrow.size() * 4));
-    HIPCHK(c, upload_table(g.jwarm.p, jwarm.data(), jwarm.size() * 4));
     g.W = W; g.H = H; g.variant = D.variant; g.valid = true;
     return NTSCSIM_OK;
 }
@@ -480,7 +469,7 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     if (c->avg) { ntscsim::avg_state_destroy(c->avg); c->avg = nullptr; }
     if (c->scan) { ntscsim::scan_state_destroy(c->scan); c->scan = nullptr; }
     for (Geometry *e : c->geoms) {
-        e->lskip.release(); e->pskip.release(); e->jrow.release(); e->sstart.release(); e->jwarm.release();
+        e->lskip.release(); e->pskip.release(); e->jrow.release();
         delete e;
     }
     c->geoms.clear();
@@ -604,10 +593,7 @@ extern "C" void ntscsim_debug_set_warmup(ntscsim_ctx *c, int luma_draws, int chr
     if (!c) return;
     c->warm_override[0] = luma_draws;
     c->warm_override[1] = chroma_draws & ~1;
-    // (test hook only) the tables depend on the warm-up lengths: drain and forget them
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    for (Geometry *e : c->geoms) e->valid = false;
+    // (test hook only; the lengths travel with each launch's parameters, the jump tables do not depend on them)
 }
 
 // The draws that are not per-pixel (k_field_setup) and the rand() / noise state of every row start (k_row_states):
@@ -865,7 +851,7 @@ static int launch_records(ntscsim_ctx *c, const DevParams &D, const FieldDev *fi
 
     GeomDev G;
     G.lskip = c->geom_cur->lskip.p; G.pskip = c->geom_cur->pskip.p; G.jrow = c->geom_cur->jrow.p;
-    G.jwarm = c->geom_cur->jwarm.p; G.sstart = c->geom_cur->sstart.p; G.ptab = c->ptab.p;
+    G.ptab = c->ptab.p;
 
     c->kernels.clear();
     launch_setup(c, D, G, fields_dev, n, st);
@@ -1502,7 +1488,7 @@ static int launch422(ntscsim_ctx *c, const Prep422 &P, const FieldDev *fields_de
     }
     GeomDev G;
     G.lskip = c->geom_cur->lskip.p; G.pskip = c->geom_cur->pskip.p; G.jrow = c->geom_cur->jrow.p;
-    G.jwarm = c->geom_cur->jwarm.p; G.sstart = c->geom_cur->sstart.p; G.ptab = c->ptab.p;
+    G.ptab = c->ptab.p;
     Scratch422 Sc;
     Sc.S = S;
     Sc.Y = c->scratch422.p;

@@ -687,8 +687,9 @@ int  ntscsim_get_timings_ms(ntscsim_ctx *ctx, float out_ms[4], int *n_calls);
  * before head switching -- into host memory. */
 int ntscsim_debug_read_composite(ntscsim_ctx *ctx, int32_t *out, size_t out_elems);
 
-/* Test hook: shorten the noise-accumulator warm-up of k_row_states (default 64 / 128 draws) so
- * that the exact serial-replay fallback is exercised.  Results must not change. */
+/* Test hook: the number of draws k_row_states looks back at first for the noise accumulators
+ * (default 24 / 31, taken from the row's rand() window), e.g. 2 / 2 so that most rows go through
+ * the backward extension of that look-back.  Results must not change. */
 void ntscsim_debug_set_warmup(ntscsim_ctx *ctx, int luma_draws, int chroma_draws);
 
 /* Test hook: always launch the GENERIC kernels (options read at run time) instead of the PRESET
