@@ -1,5 +1,5 @@
 // ntsc_stage.hpp -- the host scaffold of the device stages that are translation units of their own (frameblend:
-// csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip): what they see of an ntscsim_ctx,
+// csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip): what they see of an ntscsim_ctx,
 // whose definition stays private to ntscsim_hip.hip, the pinned record slots their launches go up through, and the
 // arena their *_frames_host() calls copy host frames through.  What only the two layer stages share: ntsc_layer.hpp
 // (no HIP in it) and ntsc_layer_frames.hpp.
@@ -18,6 +18,7 @@ struct BlendState;                       // ntsc_blend.hip: bound params, tables
 struct KeyState;                         // ntsc_key.hip: bound params, record slots, noise bits, host-frame arena
 struct AvgState;                         // ntsc_avg.hip: bound params, record slots, host-frame arena
 struct ScanState;                        // ntsc_scan.hip: bound params, record slots, accumulator planes, sine tables, host-frame arena
+struct LedState;                         // ntsc_led.hip: bound params, record slots, edges plane of the debug tap, host-frame arena
 
 struct CtxStageView {
     int device;
@@ -28,12 +29,14 @@ struct CtxStageView {
     KeyState **key;
     AvgState **avg;
     ScanState **scan;
+    LedState **led;
 };
 CtxStageView ctx_stage_view(ntscsim_ctx *c);     // ntscsim_hip.hip
 void blend_state_destroy(BlendState *b);         // ntsc_blend.hip
 void key_state_destroy(KeyState *k);             // ntsc_key.hip
 void avg_state_destroy(AvgState *k);             // ntsc_avg.hip
 void scan_state_destroy(ScanState *k);           // ntsc_scan.hip
+void led_state_destroy(LedState *k);             // ntsc_led.hip
 // ntscsim_debug_last_kernels(): "k_scan_splat" becomes "k_scan_splat+spill" if a workgroup of the last call spilled
 void scan_kernels_tap(ScanState *k, int device, std::string &kernels);   // ntsc_scan.hip
 

@@ -26,7 +26,7 @@
 #include "ntsc422_fused.hip"
 #include "ntsc_scale.hip"
 #include "ntsc_float.hpp"       // NTSCSIM_MODE_FLOAT: its kernels are a translation unit of their own
-#include "ntsc_stage.hpp"       // the frameblend, colorkey, average_delay and scanimate stages (ntscsim_blend_* / _key_* / _avg_* / _scan_*): likewise, csrc/ntsc_{blend,key,avg,scan}.hip
+#include "ntsc_stage.hpp"       // the frameblend, colorkey, average_delay, scanimate and vhsled stages (ntscsim_blend_* / _key_* / _avg_* / _scan_* / _led_*): likewise, csrc/ntsc_{blend,key,avg,scan,led}.hip
 
 using namespace ntscsim;
 
@@ -221,10 +221,11 @@ struct ntscsim_ctx {
     ntscsim::KeyState *key = nullptr;       // ntscsim_key_bind(): state of the colorkey stage (csrc/ntsc_key.hip)
     ntscsim::AvgState *avg = nullptr;       // ntscsim_avg_bind(): state of the average_delay stage (csrc/ntsc_avg.hip)
     ntscsim::ScanState *scan = nullptr;     // ntscsim_scan_bind(): state of the scanimate stage (csrc/ntsc_scan.hip)
+    ntscsim::LedState *led = nullptr;       // ntscsim_led_bind(): state of the vhsled stage (csrc/ntsc_led.hip)
 };
 ntscsim::CtxStageView ntscsim::ctx_stage_view(ntscsim_ctx *c)
 {
-    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan};
+    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan, &c->led};
 }
 static void submit_engine_destroy(ntscsim_ctx *c);
 static int sub_wait_ticket(ntscsim_ctx *c, uint64_t ticket);
@@ -468,6 +469,7 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     if (c->key) { ntscsim::key_state_destroy(c->key); c->key = nullptr; }
     if (c->avg) { ntscsim::avg_state_destroy(c->avg); c->avg = nullptr; }
     if (c->scan) { ntscsim::scan_state_destroy(c->scan); c->scan = nullptr; }
+    if (c->led) { ntscsim::led_state_destroy(c->led); c->led = nullptr; }
     for (Geometry *e : c->geoms) {
         e->lskip.release(); e->pskip.release(); e->jrow.release();
         delete e;

@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -771,6 +771,75 @@ class Scanimator:
         a, b = C.c_uint64(), C.c_uint64()
         self._call("debug_spill", C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
+
+
+class EdgeAligner:
+    """The vhsled stage (ntscsim_led_*): lines up the left edge of the picture of every scanline, as ffmpeg_vhsled does.
+    `flags` are the tool's switches (none of them changes a pixel); width / height: the frame size, 16 .. 3640 by
+    16 .. 65536.  sim: share the context of a FieldSimulator (its outputs can then be aligned on the same stream
+    without leaving device memory); otherwise a context of its own is created.  torch is used only for device memory
+    and streams.  Frames are uint8 [H, W, 4] with contiguous pixels and any row stride."""
+
+    def __init__(self, flags=(), width=None, height=None, sim=None, device=0, params=None):
+        self.params = params if params is not None else _capi.make_led_params(flags, width=width, height=height)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        try:
+            self._call("bind", C.byref(self.params))
+        except Exception:
+            self.close()
+            raise
+
+    def _call(self, what, *args):
+        name = "ntscsim_led_%s" % what
+        self.sim._chk(getattr(self._lib, name)(self.sim._h, *args), name)
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    @staticmethod
+    def _descs(jobs, ptr, linesize):
+        arr = (_capi.LedDesc * max(1, len(jobs)))()
+        for d, (dst, src) in zip(arr, jobs):
+            assert len(dst.shape) == 3 and dst.shape[2] == 4 and tuple(src.shape) == tuple(dst.shape)
+            d.src_dev, d.src_linesize, d.dst_dev, d.dst_linesize = ptr(src), linesize(src), ptr(dst), linesize(dst)
+            d.width, d.height = dst.shape[1], dst.shape[0]
+        return arr
+
+    def align_frames(self, jobs, stream=None):
+        """ntscsim_led_frames_device: jobs = [(dst, src), ...] of torch uint8 CUDA tensors [H, W, 4]; dst becomes src
+        with every row moved left by its smoothed edge.  One launch for all jobs that do not depend on each other.
+        Enqueues; does not synchronise."""
+        arr = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("frames_device", arr, len(jobs), C.c_void_p(stream))
+
+    def align_frames_host(self, jobs):
+        """ntscsim_led_frames_host: the same on numpy uint8 arrays.  Synchronous."""
+        arr = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self._call("frames_host", arr, len(jobs))
+
+    def debug_keep_edges(self, on=True):
+        self._call("debug_keep_edges", 1 if on else 0)
+
+    def edges(self, frame=0):
+        """(e, x): per row the edge the scan found and the shift after smoothing (numpy int32 [H]) of frame `frame` of
+        the last align_frames call; debug_keep_edges() first.  Synchronises."""
+        import numpy as np
+        h = int(self.params.height)
+        e, x = np.empty(h, np.int32), np.empty(h, np.int32)
+        self._call("debug_edges", int(frame), C.c_void_p(e.ctypes.data), C.c_void_p(x.ctypes.data))
+        return e, x
+
+    def last_kernels(self):
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
 
 
 class Pool:

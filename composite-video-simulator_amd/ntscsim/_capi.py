@@ -58,6 +58,8 @@ EXPORTS = (
     "ntscsim_scan_bind", "ntscsim_scan_frames_device", "ntscsim_scan_clip_device", "ntscsim_scan_frames_host",
     "ntscsim_scan_debug_keep_raster", "ntscsim_scan_debug_raster", "ntscsim_scan_debug_set_window_rows",
     "ntscsim_scan_debug_spill",
+    "ntscsim_led_params_init", "ntscsim_led_parse_argv", "ntscsim_led_bind", "ntscsim_led_frames_device",
+    "ntscsim_led_frames_host", "ntscsim_led_debug_keep_edges", "ntscsim_led_debug_edges",
 )
 
 
@@ -328,6 +330,20 @@ class ScanDesc(C.Structure):
     """struct ntscsim_scan_desc"""
     _fields_ = [("dst_dev", C.c_void_p), ("dst_linesize", C.c_int32), ("src_linesize", C.c_int32),
                 ("src_dev", C.c_void_p), ("src_width", C.c_int32), ("src_height", C.c_int32), ("fieldno", C.c_uint64)]
+
+
+class LedParams(C.Structure):
+    """struct ntscsim_led_params -- keep in lock-step with include/ntscsim.h."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("underscan", C.c_int32),
+                ("use_422_colorspace", C.c_int32), ("field_rate_num", C.c_int32), ("field_rate_den", C.c_int32),
+                ("_pad", C.c_int32), ("gamma_correction", C.c_double), ("input_path", C.c_char_p),
+                ("output_path", C.c_char_p)]
+
+
+class LedDesc(C.Structure):
+    """struct ntscsim_led_desc"""
+    _fields_ = [("src_dev", C.c_void_p), ("src_linesize", C.c_int32), ("dst_linesize", C.c_int32),
+                ("dst_dev", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
 
 _u8p = C.POINTER(C.c_uint8)
@@ -624,6 +640,20 @@ def lib():
     L.ntscsim_scan_debug_set_window_rows.restype = C.c_int
     L.ntscsim_scan_debug_spill.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.ntscsim_scan_debug_spill.restype = C.c_int
+    L.ntscsim_led_params_init.argtypes = [C.POINTER(LedParams)]
+    L.ntscsim_led_params_init.restype = None
+    L.ntscsim_led_parse_argv.argtypes = [C.POINTER(LedParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ntscsim_led_parse_argv.restype = C.c_int
+    L.ntscsim_led_bind.argtypes = [C.c_void_p, C.POINTER(LedParams)]
+    L.ntscsim_led_bind.restype = C.c_int
+    L.ntscsim_led_frames_device.argtypes = [C.c_void_p, C.POINTER(LedDesc), C.c_int, C.c_void_p]
+    L.ntscsim_led_frames_device.restype = C.c_int
+    L.ntscsim_led_frames_host.argtypes = [C.c_void_p, C.POINTER(LedDesc), C.c_int]
+    L.ntscsim_led_frames_host.restype = C.c_int
+    L.ntscsim_led_debug_keep_edges.argtypes = [C.c_void_p, C.c_int]
+    L.ntscsim_led_debug_keep_edges.restype = C.c_int
+    L.ntscsim_led_debug_edges.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.ntscsim_led_debug_edges.restype = C.c_int
     _lib = L
     return L
 
@@ -754,4 +784,24 @@ def make_scan_params(flags=(), require_io=False, width=None, height=None):
         p.output_width = int(width)
     if height is not None:
         p.output_height = int(height)
+    return p
+
+
+def make_led_params(flags=(), require_io=False, width=None, height=None):
+    """ntscsim_led_params from ffmpeg_vhsled's switches (ffmpeg_vhsled.cpp parse_argv :476).  width / height override
+    the frame size after parsing (the tool takes it from its input when the switches are absent).  The returned struct
+    keeps the argv strings alive (input_path / output_path point into them)."""
+    L = lib()
+    p = LedParams()
+    L.ntscsim_led_params_init(C.byref(p))
+    argv = [b"ffmpeg_vhsled"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    p._argv = arr
+    rc = L.ntscsim_led_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
+    if rc != OK:
+        raise NtscsimError(rc, "led parse_argv(%r)" % (list(flags),))
+    if width is not None:
+        p.width = int(width)
+    if height is not None:
+        p.height = int(height)
     return p

@@ -1278,6 +1278,90 @@ int  ntscsim_scan_debug_raster(ntscsim_ctx *ctx, uint32_t *out_host);
 int  ntscsim_scan_debug_set_window_rows(ntscsim_ctx *ctx, int rows);
 int  ntscsim_scan_debug_spill(ntscsim_ctx *ctx, uint64_t *workgroups, uint64_t *spilled);
 
+/* ---- vhsled: the scanline left-edge aligner (ffmpeg_vhsled.cpp) ----
+ * A capture whose scanlines start at wandering horizontal positions is lined up: the tool finds the left edge
+ * of the picture in every row (the first run of nine pixels that are not "blackish" against the row's first
+ * pixel), takes the mean of that edge over nine rows and moves every row left by the result.  Mapping:
+ *
+ *   globals :44-52 + preset_NTSC() :457-460 + parse_argv() :476-584     | ntscsim_led_params, _init(), _parse_argv()
+ *   blackish() :682-692, the row walk :869-898                          | k_led_frames, the scan of a row
+ *   the nine-row mean :900-906, the shifted copy :908-928               | k_led_frames, smoothing and shift
+ *   the three together, per frame                                       | ntscsim_led_frames_device() / _frames_host()
+ *
+ * Decoding, scaling (sws_scale), encoding and the audio pass-through stay with the caller.
+ * Frames are BGRA in device memory; a decoder's or the simulator's outputs can be handed over without a copy.
+ * A frame carries no state into the next one, so a clip is a list of descriptors and there is no clip call.
+ */
+typedef struct ntscsim_led_params {
+    uint32_t struct_size;            /* = sizeof(ntscsim_led_params)                                       */
+    int32_t  width, height;          /* :50-51  -1 x -1: the tool then takes the input's size; -width / -height */
+    int32_t  underscan;              /* :46  0 (-underscan, clamped to 0..99); recorded, not acted on       */
+    int32_t  use_422_colorspace;     /* :48  false (-422 / -420); recorded, not acted on                    */
+    int32_t  field_rate_num, field_rate_den;    /* 60000 / 1001 (preset_NTSC), -or                         */
+    int32_t  _pad;
+    double   gamma_correction;       /* :44  -1 (-gamma); recorded, not acted on                            */
+    const char *input_path;          /* the last -i (points into argv), NULL if none: the tool has one input */
+    const char *output_path;         /* -o                                                                  */
+} ntscsim_led_params;
+
+void ntscsim_led_params_init(ntscsim_led_params *p);
+/* Mirror of parse_argv() :476-584: -i -o -or -width -height -gamma -underscan -422 -420, -h / -help (any number of
+ * leading '-').  -width / -height go through strtoul with base 0 and the tool's cast to int, and a result below
+ * 32 is refused; -gamma takes a number (isdigit / atof), "vga" or "ntsc" (2.2), and any other word leaves the value
+ * alone; -underscan is atoi clamped to 0..99; -or is strtof, an optional : / \ denominator (strtoul base 10, at
+ * least 1), a floor of 5 per second, and num / den = round(n) / d for d > 1, round(n * 10000) / 10000 otherwise.
+ * The tool's pixel loop :866-931 reads none of gamma, underscan and 422: they are recorded here and change no byte.
+ * -fa is in the tool's help text but not in its parser: an unknown switch here too.  argv[0] is the program name.
+ * NTSCSIM_E_FLAG (the tool's "return 1") for an unknown switch, a bare word, a missing value and a size below 32;
+ * require_io != 0 applies the "No output file / No input files" checks (:574-581).  NTSCSIM_E_HELP for -h / -help. */
+int  ntscsim_led_parse_argv(ntscsim_led_params *p, int argc, const char *const *argv, int require_io);
+
+/* Snapshot the parameters on a ctx (any ntscsim_params it was created with).  Waits for vhsled work in flight on
+ * the ctx.  NTSCSIM_E_SIZE unless 16 <= width <= 3640 and 16 <= height <= 65536: the tool refuses a frame below
+ * 16 x 16 (:717), its loop bound `y < (int)height - 4` is an unsigned comparison that misbehaves for small heights,
+ * and its nine-row sum of edges, each up to width << 16, plus 5 must fit an int32 -- 9 * 3640 * 65536 + 5 does,
+ * 9 * 3641 * 65536 + 5 does not, and past that the tool's arithmetic is undefined. */
+int  ntscsim_led_bind(ntscsim_ctx *ctx, const ntscsim_led_params *p);
+
+typedef struct ntscsim_led_desc {
+    const void *src_dev;             /* device pointer, BGRA frame; never written                            */
+    int32_t     src_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    void       *dst_dev;             /* device pointer, BGRA frame; bytes of a row behind 4*width are not touched */
+    int32_t     width, height;       /* must be the bound params'                                            */
+} ntscsim_led_desc;
+/*
+ * The tool's frame body :866-931 for `n` frames.  With in[y][i] the source pixels as uint32_t:
+ *   e[y]    = the first x at which in[y][x .. x+8] are all not blackish, or width if there is none; a pixel is
+ *             not blackish when one of its three low bytes exceeds the LOW byte of in[y][0] by 16 or more (the
+ *             tool compares all three channels with the first pixel's blue; the top byte plays no part)
+ *   adj2[y] = (sum of e[y-4 .. y+4] << 16, plus 5) / 9 for 4 <= y < height - 4, e[y] << 16 for the other rows
+ *   x[y]    = (adj2[y] + 0x8000) >> 16
+ *   out[y][i] = in[y][i + x[y]] for i < width - x[y] when x[y] < width / 2, in[y][i] for every other pixel
+ * Pixels move as whole dwords.  All frame pointers are DEVICE pointers; `descs` is host memory and is consumed by the
+ * call.  Enqueued on hip_stream (NULL: the ctx's own stream), returns without synchronising.  Descriptors take
+ * effect in order: a later one that reads a frame an earlier one wrote sees the earlier result.
+ * Kernel: k_led_frames, one launch for all descriptors that do not depend on each other, grid (bands of 16 rows,
+ * frames).  A workgroup scans its rows and four rows above and below (one wavefront per row, the chunk's mask a
+ * 64-bit ballot, the first 128 pixels of all of a wave's rows requested before the first wait), keeps the edges
+ * on chip, smooths and moves its rows.  Destinations whose pointer and linesize are multiples of 16 are written as
+ * 16-byte vectors; any other, and the last width % 4 pixels of a row, as dwords.  Same bytes either way.
+ * NTSCSIM_E_SIZE: a size other than the bound params', a linesize below 4*width or not a multiple of 4, a pointer
+ * that is not a multiple of 4.  NTSCSIM_E_ARG: a NULL pointer, no ntscsim_led_bind() before, a source that overlaps
+ * its destination in any way -- rows are moved in parallel, which cannot be done in place, and the tool never does
+ * it either.
+ */
+int  ntscsim_led_frames_device(ntscsim_ctx *ctx, const ntscsim_led_desc *descs, int n, void *hip_stream);
+/* ntscsim_led_frames_device() on HOST frames, through pinned staging of the ctx.  Synchronous.  Same bytes as the
+ * device call: the bytes the device call leaves alone keep what the host frame held. */
+int  ntscsim_led_frames_host(ntscsim_ctx *ctx, const ntscsim_led_desc *descs, int n);
+/* Debug taps.  keep_edges(on): while on, every frames call also writes e[y] and x[y] of each of its frames to a
+ * plane of the ctx.  edges(frame, e_host, x_host): those of frame `frame` of the last frames call, `height` int32
+ * each (either pointer may be NULL), so that a test can tell a wrong scan from a wrong copy; synchronises;
+ * NTSCSIM_E_ARG when nothing was kept or `frame` is outside the last call.  Both require ntscsim_led_bind(). */
+int  ntscsim_led_debug_keep_edges(ntscsim_ctx *ctx, int on);
+int  ntscsim_led_debug_edges(ntscsim_ctx *ctx, int frame, int32_t *e_host, int32_t *x_host);
+
 #ifdef __cplusplus
 }
 #endif

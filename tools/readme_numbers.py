@@ -64,6 +64,26 @@ rows = [
         k(e.get("bgra_pinned", 0)), k(e.get("yuv420p_pinned", 0)), k(e.get("yuv420p_in_yuv420p_out_pinned", 0))), "`end_to_end.*_pinned`"),
     ("one process per GPU, C++ host over `rccl.h` (`host/rank_bench.cpp`), with the one rank this box has", "%s fields/s, checksums verified" % k(line["side"]["multi_gpu_cpp_host"]), "`side.multi_gpu_cpp_host`"),
 ]
+
+
+def led_row(path="profiles/led.json"):
+    """The vhsled stage's row, from tools/bench_led.py's file."""
+    c = json.load(open(path))
+    a, b, d7, d19 = (c["cases"][n] for n in ("720x486_capture", "1920x1080_capture", "720x486_all_dark", "1920x1080_all_dark"))
+    return ("the scanline left-edge aligner (`ffmpeg_vhsled`, `ntscsim_led_*`): 600 frames resident in HBM through one `ntscsim_led_frames_device` call, "
+            "a dark border of 8..40 pixels jittering per row (`tools/bench_led.py`)",
+            "720×486: **%s frames/s**, `frac_hbm` %.3f on 8·W·H bytes per frame, %.2f × the time of a device-to-device copy of the same traffic in the same run; "
+            "1920×1080: %s frames/s, `frac_hbm` %.3f, %.2f × the copy; all-dark frames (every scan reads its whole row): %s / %s frames/s, %.2f / %.2f × the copy; "
+            "the reference's loop on one CPU core of the build machine (not the GPU host): %.0f frames/s at 720×486" % (
+                k(a["frames_per_s"]), a["frac_hbm"], a["led_over_copy"], k(b["frames_per_s"]), b["frac_hbm"], b["led_over_copy"],
+                k(d7["frames_per_s"]), k(d19["frames_per_s"]), d7["led_over_copy"], d19["led_over_copy"], c["reference_cpu"]["frames_per_s"]),
+            "`profiles/led.json`, DESIGN.md §7i")
+
+
+try:
+    rows.append(led_row())
+except Exception:
+    pass
 tbl = "| what (1× MI355X, 720×486 unless said otherwise) | measured | where |\n|---|---|---|\n" + "\n".join("| %s | %s | %s |" % r for r in rows)
 s = open("README.md").read()
 a, b = s.index("<!-- numbers:begin -->"), s.index("<!-- numbers:end -->")
