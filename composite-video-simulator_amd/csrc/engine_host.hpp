@@ -296,3 +296,48 @@ inline void h422_delivery_ops(const H422Record &R, const uint8_t *st, const ntsc
         }
     }
 }
+
+// ---- TIGHT rows of the 4:2:2 engine: who wrote each field of a caller frame last, and into which device frame -----------
+// A batched iteration on tight rows (linesize[0] < width + 2) takes the two bytes behind each of its rows -- pixels 0, 1 of
+// the OTHER field's rows -- from the device frame that holds them as the in-order loop has them now: the one the last
+// iteration that wrote that field rendered into (ring slot `fslot`), while that slot has not been handed out again -- fewer
+// than ring - 2 iterations later.  Otherwise (nothing recorded: the first iterations of a frame, after a one-at-a-time
+// iteration, a DIRTY frame or a re-make of the rings) the bytes are the caller's own, snapshotted at submit.
+// Slots are positions in ONE allocation of the rings: reset() goes with every re-make (h422_release_rings), whatever the
+// new ring's size, geometry or caller frame -- a slot of the old allocation is nobody's in the new one, and lies behind its
+// end when the ring shrank.
+struct H422Writers {
+    struct Chain { int fslot; uint64_t ticket; };       // fslot < 0: none, take the snapshot
+    struct Entry {
+        const uint8_t *frame;
+        uint64_t ticket[2];         // per field: the iteration that wrote it last (0: not this engine, or not since a break)
+        int fslot[2];               // ... and the device frame it wrote
+        void dirty() { ticket[0] = ticket[1] = 0; }                 // the caller rewrote the frame
+        void serial() { ticket[0] = ticket[1] = 0; }                // the frame moves on in the caller's memory (mirror path)
+        void batched(unsigned field, uint64_t t, int slot) { ticket[field & 1u] = t; fslot[field & 1u] = slot; }
+        // iteration `t` of `field`, rings of `ring` slots: where the other field's rows are
+        Chain chain_for(unsigned field, uint64_t t, int ring) const
+        {
+            const unsigned other = (field & 1u) ^ 1u;
+            if (ticket[other] != 0 && t - ticket[other] + 2 < (uint64_t)ring) return {fslot[other], ticket[other]};
+            return {-1, 0};
+        }
+    };
+    static constexpr size_t MAX_FRAMES = 64;               // (a tool has one frame; keep the table bounded: the oldest goes)
+    std::vector<Entry> tab;
+
+    const Entry *find(const uint8_t *frame) const
+    {
+        for (const Entry &x : tab) if (x.frame == frame) return &x;
+        return nullptr;
+    }
+    // the frame's entry, made when there is none (valid until the next at() / reset())
+    Entry &at(const uint8_t *frame)
+    {
+        if (const Entry *x = find(frame)) return tab[(size_t)(x - tab.data())];
+        if (tab.size() >= MAX_FRAMES) tab.erase(tab.begin());
+        tab.push_back({frame, {0, 0}, {-1, -1}});
+        return tab.back();
+    }
+    void reset() { tab.clear(); }
+};

@@ -151,9 +151,8 @@ struct Host422Engine : LaunchQueue<Host422Item, NoLaunchExtra> {
 
     std::vector<Mirror *> mirrors;
 
-    // TIGHT rows: who wrote each field of a caller frame last, and into which device frame (see h422_submit)
-    struct Writer { const uint8_t *frame; uint64_t ticket[2]; int fslot[2]; };
-    std::vector<Writer> writers;
+    // TIGHT rows: who wrote each field of a caller frame last, and into which device frame (engine_host.hpp; see h422_submit)
+    H422Writers writers;
     hipEvent_t ev_up = nullptr;
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [0] submitted [1] launches [2] uploads [3] FAST [4] SERIAL [5] mirror uploads [6] iterations with a result written by the delivery kernels into pinned caller planes
 };
@@ -201,6 +200,7 @@ static void h422_release_rings(Host422Engine *e)
     e->W = e->H = 0; e->sbytes = 0; e->ring = 0; e->ring_want = 0;
     e->src_cur = -1;
     e->src_last_ticket.clear();
+    e->writers.reset();               // (device frames of the old allocation: the next tight iteration takes the snapshot)
 }
 
 static void host422_engine_destroy(ntscsim_ctx *c)
@@ -445,9 +445,11 @@ static int h422_launch(ntscsim_ctx *c)
         // caller's; the bytes were snapshotted at submit)
         PadRec422 &p = e->prec[it.slot];
         p.y = frm[0]; p.pad = e->pads + (size_t)2 * e->L * (size_t)it.slot; p.ls = fls[0]; p.W = W;
-        p.chain = (it.tight && it.chain_fslot >= 0) ? e->dfrm.p + e->fbytes * (size_t)it.chain_fslot + e->foff[0] : nullptr;
+        // (a slot that is not one of this allocation's is never turned into a pointer: the snapshot then)
+        const bool chained = it.tight && it.chain_fslot >= 0 && it.chain_fslot < e->ring;
+        p.chain = chained ? e->dfrm.p + e->fbytes * (size_t)it.chain_fslot + e->foff[0] : nullptr;
         p.chain_ls = e->lsd[0]; p.H = H; p.host_ls = L.frame.linesize[0]; p._pad = 0;
-        if (it.tight && it.chain_fslot >= 0 && it.chain_ticket >= b.first) two_pass = true;
+        if (chained && it.chain_ticket >= b.first) two_pass = true;
         any_chain = any_chain || p.chain != nullptr;
         p.field = (int32_t)L.field; p.nrows = it.serial ? 0 : nr;
         any_pad = any_pad || !it.serial;
@@ -688,21 +690,14 @@ static int h422_submit(ntscsim_ctx *c, const ntscsim_loop422 *L, uint32_t flags,
     it.it = *L;
     {
         // who wrote each field of this caller frame last (TIGHT rows chain on it; any iteration updates it)
-        Host422Engine::Writer *wr = nullptr;
-        for (auto &x : e->writers) if (x.frame == L->frame.data[0]) { wr = &x; break; }
-        if (!wr) {
-            if (e->writers.size() >= 64) e->writers.erase(e->writers.begin());
-            e->writers.push_back({L->frame.data[0], {0, 0}, {-1, -1}});
-            wr = &e->writers.back();
-        }
-        if (flags & NTSCSIM_SUBMIT422_DIRTY) { wr->ticket[0] = wr->ticket[1] = 0; }
-        const unsigned other = L->field ^ 1u;
+        H422Writers::Entry &wr = e->writers.at(L->frame.data[0]);
+        if (flags & NTSCSIM_SUBMIT422_DIRTY) wr.dirty();
         if (it.tight) {
-            // the other field's rows as the in-order loop has them now: written by iteration wr->ticket[other] into device
-            // frame wr->fslot[other] -- still there while fewer than ring - 2 iterations have passed -- or, when this
-            // engine has not written them (first iterations, after a one-at-a-time iteration or a DIRTY), the caller's
-            // own bytes, snapshotted below
-            if (wr->ticket[other] != 0 && t - wr->ticket[other] + 2 < (uint64_t)e->ring) { it.chain_fslot = wr->fslot[other]; it.chain_ticket = wr->ticket[other]; }
+            // the other field's rows as the in-order loop has them now: in the device frame of the iteration that wrote them
+            // last while that is still there, or, when this engine has not written them (first iterations, after a
+            // one-at-a-time iteration, a DIRTY or a re-make of the rings), the caller's own bytes, snapshotted below
+            const H422Writers::Chain ch = wr.chain_for(L->field, t, e->ring);
+            if (ch.fslot >= 0) { it.chain_fslot = ch.fslot; it.chain_ticket = ch.ticket; }
             else if (e->next_ticket - 1 > e->done_ticket) {
                 // snapshot of the caller's bytes: whatever is in flight lands in them first (start of a stream, after a
                 // one-at-a-time iteration; with alternating fields the chain never breaks afterwards)
@@ -710,8 +705,8 @@ static int h422_submit(ntscsim_ctx *c, const ntscsim_loop422 *L, uint32_t flags,
                 if (rc != NTSCSIM_OK) return rc;
             }
         }
-        if (serial) { wr->ticket[0] = wr->ticket[1] = 0; }      // the frame moves on in the caller's memory (mirror path)
-        else { wr->ticket[L->field] = t; wr->fslot[L->field] = fslot; }
+        if (serial) wr.serial();
+        else wr.batched(L->field, t, fslot);
     }
     // pinned caller frames: results are written in place by the delivery kernels
     (void)h422_pin_frame(c, e, L->frame, W, H, H, it.frm_dev);

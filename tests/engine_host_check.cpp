@@ -1,6 +1,7 @@
 // engine_host_check.cpp -- drives csrc/engine_host.hpp (what the host-frame engines decide without the GPU: the copy threads,
-// the row maps, the copy lists of staged results, the ranges of pinned memory) without a GPU: plain C++ with its own main,
-// compiled and run by tests/test_engine_host.py.  Prints one line per failed check and returns their count.
+// the row maps, the copy lists of staged results, the ranges of pinned memory, the writer table of tight rows) without a GPU:
+// plain C++ with its own main, compiled and run by tests/test_engine_host.py.  Prints one line per failed check and returns
+// their count.
 #include <cstdio>
 #include <map>
 #include <string>
@@ -312,6 +313,123 @@ static void pin_range_checks()
     CHECK(in_brk_heap((uintptr_t)&g_failed) && !in_brk_heap((uintptr_t)&pr));
 }
 
+// ---- the writer table of the 4:2:2 engine's TIGHT rows -----------------------------------------------------------------
+// A seeded random walk over what h422_submit / h422_release_rings do to the table -- batched writes with rising tickets into
+// slot t % ring, one-at-a-time iterations, DIRTY, re-makes of the rings to larger and smaller sizes, more caller frames than
+// the table holds -- beside a brute-force model that keeps the whole history and answers from it: "since the last re-make,
+// DIRTY, one-at-a-time iteration or eviction of this frame, which iteration wrote the other field last, and have fewer than
+// ring - 2 iterations passed since".  After every step every frame and field is asked.
+struct WriterEvent { enum Kind { WRITE, BREAK, GONE, RESET } kind; int frame; unsigned field; uint64_t t; };
+
+static H422Writers::Chain writers_model(const std::vector<WriterEvent> &log, int frame, unsigned field, uint64_t t, int ring)
+{
+    for (size_t i = log.size(); i-- > 0;) {
+        const WriterEvent &ev = log[i];
+        if (ev.kind == WriterEvent::RESET) break;
+        if (ev.frame != frame) continue;
+        if (ev.kind == WriterEvent::BREAK || ev.kind == WriterEvent::GONE) break;
+        if (ev.field == field) continue;                    // (this field's own last writer is of no interest)
+        const long long passed = (long long)(t - ev.t);
+        if (passed < (long long)ring - 2) return {(int)(ev.t % (uint64_t)ring), ev.t};
+        break;
+    }
+    return {-1, 0};
+}
+
+static void writers_checks()
+{
+    const int HOT = 4, FRAMES = 160, STEPS = 8000;
+    static const int RINGS[] = {2, 3, 4, 6, 10, 18, 34, 66, 130};
+    auto ptr = [](int id) { return reinterpret_cast<const uint8_t *>((uintptr_t)0x10000000 + (uintptr_t)id * 4096); };   // (never read)
+    uint64_t seed = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&](unsigned n) {                            // splitmix64: the same walk everywhere
+        uint64_t z = (seed += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return (unsigned)((z ^ (z >> 31)) % n);
+    };
+    H422Writers w;
+    std::vector<WriterEvent> log;
+    std::vector<int> live;                                  // the model's frames since the last re-make, oldest first
+    uint64_t next = 1, reset_t = 1;
+    int ring = 10, cold = HOT;
+    long chained = 0, evictions = 0, grew = 0, shrank = 0, shrank_below_live = 0;
+    long mismatches = 0, bad_size = 0, bad_slot = 0, bad_ticket = 0;            // (counted: a broken table fails at every step)
+
+    auto touch = [&](int f) {                               // what at() does to the table's population
+        if (std::find(live.begin(), live.end(), f) != live.end()) return;
+        if (live.size() >= 64) { log.push_back({WriterEvent::GONE, live.front(), 0, 0}); live.erase(live.begin()); evictions++; }
+        live.push_back(f);
+    };
+    auto pick = [&] {
+        if (rnd(100) < 50) return (int)rnd(HOT);
+        if (rnd(100) < 20) return (int)rnd(FRAMES);         // any frame again, evicted or not
+        cold = cold + 1 < FRAMES ? cold + 1 : HOT;          // ... or the next new one: this is what overflows the table
+        return cold;
+    };
+    for (int step = 0; step < STEPS; step++) {
+        const unsigned what = rnd(1000);
+        if (what < 620) {                                   // a batched iteration; the fields mostly alternate, as in the loop
+            const int f = pick();
+            const unsigned field = rnd(100) < 85 ? (unsigned)(next & 1) : rnd(2);
+            const uint64_t t = next++;
+            touch(f);
+            w.at(ptr(f)).batched(field, t, (int)(t % (uint64_t)ring));
+            log.push_back({WriterEvent::WRITE, f, field, t});
+        } else if (what < 760) {                            // one at a time, on the mirror
+            const int f = pick();
+            next++;
+            touch(f);
+            w.at(ptr(f)).serial();
+            log.push_back({WriterEvent::BREAK, f, 0, 0});
+        } else if (what < 860) {                            // the caller rewrote the frame
+            const int f = pick();
+            touch(f);
+            w.at(ptr(f)).dirty();
+            log.push_back({WriterEvent::BREAK, f, 0, 0});
+        } else if (what < 865) {                            // a re-make of the rings
+            const int nr = RINGS[rnd(sizeof(RINGS) / sizeof(RINGS[0]))];
+            bool below = false;                             // does the old table hold a live slot the new rings do not have?
+            for (int f = 0; f < FRAMES; f++)
+                for (unsigned field = 0; field < 2; field++) below = below || writers_model(log, f, field, next, ring).fslot >= nr;
+            if (nr > ring) grew++;
+            if (nr < ring) shrank++;
+            if (below) shrank_below_live++;
+            w.reset();
+            log.push_back({WriterEvent::RESET, -1, 0, 0});
+            live.clear();
+            ring = nr;
+            reset_t = next;
+        } else {                                            // time passes on other frames: iterations nobody records here
+            next += 1 + rnd(3);
+        }
+        if (w.tab.size() > H422Writers::MAX_FRAMES || w.tab.size() != live.size()) bad_size++;
+        for (int f = 0; f < FRAMES; f++)
+            for (unsigned field = 0; field < 2; field++) {
+                const H422Writers::Entry *x = w.find(ptr(f));
+                const H422Writers::Chain got = x ? x->chain_for(field, next, ring) : H422Writers::Chain{-1, 0};
+                const H422Writers::Chain want = writers_model(log, f, field, next, ring);
+                if (got.fslot != want.fslot || got.ticket != want.ticket) mismatches++;
+                if (got.fslot >= 0) {
+                    chained++;
+                    if (got.fslot >= ring) bad_slot++;                                  // a slot of THIS allocation
+                    if (got.ticket < reset_t || got.ticket >= next) bad_ticket++;       // ... written since it was made
+                }
+            }
+    }
+    if (mismatches || bad_size || bad_slot || bad_ticket)
+        std::printf("writer table: %ld answers differ from the model, %ld slots outside the ring, %ld tickets from before the re-make, "
+                    "%ld steps with a wrong table size\n", mismatches, bad_slot, bad_ticket, bad_size);
+    CHECK(mismatches == 0);
+    CHECK(bad_slot == 0 && bad_ticket == 0);
+    CHECK(bad_size == 0);
+    // the walk went where the table can go wrong
+    if (!(chained > 1000 && evictions > 64 && grew > 5 && shrank > 5))
+        std::printf("writer table walk: %ld chained answers, %ld evictions, %ld larger / %ld smaller re-makes\n", chained, evictions, grew, shrank);
+    CHECK(chained > 1000 && evictions > 64 && grew > 5 && shrank > 5);
+    CHECK(shrank_below_live > 0);                           // a re-make to fewer slots than a live fslot
+}
+
 int main()
 {
     delivery_checks("1", 1);
@@ -324,6 +442,7 @@ int main()
     dst_conflict_checks();
     h422_ops_checks();
     pin_range_checks();
+    writers_checks();
     if (g_failed) std::printf("%d check(s) failed\n", g_failed);
     return g_failed;
 }

@@ -231,6 +231,86 @@ def test_geometry_change_unaligned_rows_and_interlaced_source():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("pin", [False, True])
+def test_submit_configure_in_mid_stream_carries_nothing_across_the_re_make(pin):
+    """ntscsim_submit_configure() between two fields, with fields in flight: first to FEWER slots, then to more slots and
+    from three lanes to one.  Each configure falls between the two fields of a frame, so the second one's SUBMIT_SAME_SRC
+    meets rings that no longer hold its source (the engine uploads it again: two uploads more than there are frames).
+    Every field in a frame of its own; all of them == the oracle's loop, and so is the rand() position."""
+    w, h = (192, 96) if pin else (96, 33)       # (pinned in place: frames of at least 64 KiB)
+    n, cuts = 32, (11, 21)
+    p = L.make_params(["-vhs"], output_height=h)
+    frames = [L.noise_frame(w, h, 1500 + j) for j in range(n // 2)]
+    exp, exp_pos = reference_loop(p, frames, n, w, h, n, False)
+    sim = ntscsim.FieldSimulator(params=p)
+    sim.submit_configure(depth=4, slots=16, lanes=3, pin=pin, min_pin_bytes=0)
+    src = page_frame(h, w)
+    bufs = [page_frame(h, w, 0x5A) for _ in range(n)]
+    for k in range(n):
+        if k == cuts[0]:
+            sim.submit_configure(depth=2, slots=4, lanes=3, pin=pin, min_pin_bytes=0)
+        if k == cuts[1]:
+            sim.submit_configure(depth=4, slots=32, lanes=1, pin=pin, min_pin_bytes=0)
+        if (k & 1) == 0:
+            src[:] = frames[k // 2]
+        assert sim.submit(bufs[k], src, (k & 1) ^ 1, k, same_src=bool(k & 1)) == k + 1
+    sim.wait()
+    for k in range(n):
+        assert np.array_equal(bufs[k], exp[k]), "field %d" % k
+    assert sim.rng_pos == exp_pos
+    st = sim.submit_stats()
+    assert st["submitted"] == n and st["uploads"] == n // 2 + len(cuts), st
+    if pin:
+        assert st["delivered_direct"] == n and st["delivered_staged"] == 0, st
+    else:
+        assert st["delivered_staged"] == n and st["delivered_direct"] == 0, st
+    sim.host_unpin()
+    sim.close()
+
+
+@pytest.mark.gpu
+def test_geometry_change_that_comes_back_on_the_same_caller_arrays():
+    """96x32 -> 100x37 -> 96x32 on ONE ctx and the same caller memory (source and destination frames of every geometry
+    are views of the same two arrays), each change between the two fields of a frame: the second field's SUBMIT_SAME_SRC
+    comes right behind the re-make of the rings.  Whole memory == the oracle's loop on its own copy."""
+    p = L.make_params(["-vhs"])
+    sim = ntscsim.FieldSimulator(params=p)
+    sim.submit_configure(depth=3, slots=8, lanes=2)          # (default threshold: these small heap arrays are staged)
+    o = L.OracleStream(p)
+    size = 100 * 37 * 4
+    n_dst = 6
+    src_mem = np.zeros(size, np.uint8)
+    got_mem = np.full((n_dst, size), 0x5A, np.uint8)
+    exp_mem = got_mem.copy()
+
+    def view(mem, w, h):
+        return mem[:h * w * 4].reshape(h, w, 4)
+
+    # field k takes the second field of its frame when k is odd; the size changes in front of fields 7 and 15
+    plan = [(96, 32)] * 7 + [(100, 37)] * 8 + [(96, 32)] * 7
+    uploads, frame = 0, None
+    for k, (w, h) in enumerate(plan):
+        new = (k & 1) == 0
+        changed = k > 0 and plan[k - 1] != (w, h)
+        if changed:
+            sim.wait()                      # (the caller re-lays its memory at the new size: nothing may be in flight)
+            assert np.array_equal(got_mem, exp_mem), "before the change at field %d" % k
+        if new or changed:                  # (after a change src holds a frame of the new size: the flag promises no more)
+            frame = L.noise_frame(w, h, 1700 + k)
+            view(src_mem, w, h)[:] = frame
+            uploads += 1
+        o.field(view(exp_mem[k % n_dst], w, h), frame, (k & 1) ^ 1, k)
+        sim.submit(view(got_mem[k % n_dst], w, h), view(src_mem, w, h), (k & 1) ^ 1, k, same_src=not new)
+    k = len(plan)
+    sim.wait()
+    assert np.array_equal(got_mem, exp_mem)
+    assert sim.rng_pos == o.rng_pos
+    st = sim.submit_stats()
+    assert st["submitted"] == k and st["uploads"] == uploads, (st, uploads)
+    sim.close()
+
+
+@pytest.mark.gpu
 def test_submit_errors_consume_nothing_and_tickets_are_checked():
     w, h = 96, 32
     p = L.make_params([])
