@@ -456,12 +456,7 @@ int avg_launch(ntscsim_ctx *c, const ntscsim_avg_desc *descs, int n, const AvgCl
         if (general) hipLaunchKernelGGL(k_avg_general, grid, block, 0, st, recs_dev, k->cfg_dev, W, H, nl);
         else hipLaunchKernelGGL(k_avg_fast, grid, block, 0, st, recs_dev, cfg, W, H, nl);
     }
-    STAGECHK(v, hipGetLastError());
-    STAGECHK(v, hipEventRecord(s.done, st));
-    s.used = true;
-    if (!v.kernels->empty()) *v.kernels += ';';
-    *v.kernels += clip ? (general ? "k_avg_clip_general" : "k_avg_clip_fast<" + std::to_string(nl) + ">") : (general ? "k_avg_general" : "k_avg_fast");
-    return NTSCSIM_OK;
+    return stage_launched(v, &s, st, clip ? (general ? "k_avg_clip_general" : "k_avg_clip_fast<" + std::to_string(nl) + ">") : (general ? "k_avg_general" : "k_avg_fast"));
 }
 
 } // namespace

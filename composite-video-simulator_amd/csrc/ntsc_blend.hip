@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "ntscsim.h"
+#include "ntsc_frames.hpp"
 #include "ntsc_stage.hpp"
 
 namespace ntscsim {
@@ -241,15 +242,14 @@ int blend_launch(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, hipStre
         const ntscsim_blend_desc &d = descs[i];
         if (!d.dst_dev || d.n_taps < 0 || (d.n_taps > 0 && !d.taps)) return NTSCSIM_E_ARG;
         if (d.width <= 0 || d.height <= 0 || d.width > (1 << 16) || d.height > (1 << 16)) return NTSCSIM_E_SIZE;   // Q * H fits an int
-        if (d.dst_linesize < 4 * d.width || (d.dst_linesize & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_SIZE;
+        if (plane_check(d.dst_dev, d.dst_linesize, d.width, true)) return NTSCSIM_E_SIZE;
         uint64_t sum = 0;
-        const uintptr_t d0 = (uintptr_t)d.dst_dev, d1 = d0 + (size_t)d.dst_linesize * (size_t)d.height;
+        const Span ds = span_of(d.dst_dev, d.dst_linesize, d.height);
         for (int k = 0; k < d.n_taps; k++) {
             const ntscsim_blend_tap &t = d.taps[k];
             if (!t.src_dev) return NTSCSIM_E_ARG;
-            if (t.src_linesize < 4 * d.width || (t.src_linesize & 3) || ((uintptr_t)t.src_dev & 3)) return NTSCSIM_E_SIZE;
-            const uintptr_t s0 = (uintptr_t)t.src_dev, s1 = s0 + (size_t)t.src_linesize * (size_t)d.height;
-            if (s0 < d1 && d0 < s1) return NTSCSIM_E_ARG;                       // a destination that is also a source
+            if (plane_check(t.src_dev, t.src_linesize, d.width, true)) return NTSCSIM_E_SIZE;
+            if (overlaps(ds, span_of(t.src_dev, t.src_linesize, d.height))) return NTSCSIM_E_ARG;   // a destination that is also a source
             sum += t.weight16;
             if (sum >= (1ull << 38)) return NTSCSIM_E_ARG;
         }
@@ -302,14 +302,7 @@ int blend_launch(ntscsim_ctx *c, const ntscsim_blend_desc *descs, int n, hipStre
     const dim3 grid((unsigned)per, (unsigned)n);
     if (general) launch_form<true>(b->gamma, wide, grid, st, reinterpret_cast<const BlendRec *>(s.dev), b->dec_dev, b->enc_dev);
     else launch_form<false>(b->gamma, wide, grid, st, reinterpret_cast<const BlendRec *>(s.dev), b->dec_dev, b->enc_dev);
-    STAGECHK(v, hipGetLastError());
-    STAGECHK(v, hipEventRecord(s.done, st));
-    s.used = true;
-    if (!v.kernels->empty()) *v.kernels += ';';
-    *v.kernels += general ? "k_blend_general<" : "k_blend_fast<";
-    *v.kernels += b->gamma ? "true," : "false,";
-    *v.kernels += wide ? "true>" : "false>";
-    return NTSCSIM_OK;
+    return stage_launched(v, &s, st, std::string(general ? "k_blend_general<" : "k_blend_fast<") + (b->gamma ? "true," : "false,") + (wide ? "true>" : "false>"));
 }
 
 } // namespace
@@ -390,14 +383,14 @@ extern "C" int ntscsim_blend_frames_host(ntscsim_ctx *c, const ntscsim_blend_des
         for (int i = at; i < std::min(n, at + CHUNK); i++) {
             const ntscsim_blend_desc &d = descs[i];
             if (!d.dst_dev || d.n_taps < 0 || (d.n_taps > 0 && !d.taps)) return NTSCSIM_E_ARG;
-            if (d.width <= 0 || d.height <= 0 || d.width > (1 << 16) || d.height > (1 << 16) || d.dst_linesize < 4 * d.width) return NTSCSIM_E_SIZE;
+            if (d.width <= 0 || d.height <= 0 || d.width > (1 << 16) || d.height > (1 << 16) || plane_check(d.dst_dev, d.dst_linesize, d.width, false)) return NTSCSIM_E_SIZE;
             const size_t fb = pitch(d.width) * (size_t)d.height;
             frame_max = std::max(frame_max, fb);
             cb += fb;
             for (int k = 0; k < d.n_taps; k++) {
                 const ntscsim_blend_tap &t = d.taps[k];
                 if (!t.src_dev) return NTSCSIM_E_ARG;
-                if (t.src_linesize < 4 * d.width) return NTSCSIM_E_SIZE;
+                if (plane_check(t.src_dev, t.src_linesize, d.width, false)) return NTSCSIM_E_SIZE;
                 const Key key{t.src_dev, t.src_linesize, d.width, d.height};
                 if (where.emplace(key, src_bytes).second) { order.push_back(key); src_bytes += fb; }
             }
@@ -418,8 +411,7 @@ extern "C" int ntscsim_blend_frames_host(ntscsim_ctx *c, const ntscsim_blend_des
             const Key &k = order[j];
             const size_t pb = pitch(k.w), fb = pb * (size_t)k.h;
             if (fill + fb > fa.staging_cap) break;
-            for (int y = 0; y < k.h; y++)
-                std::memcpy(fa.staging + fill + (size_t)y * pb, static_cast<const uint8_t *>(k.p) + (size_t)y * (size_t)k.ls, (size_t)k.w * 4);
+            copy_rows(fa.staging + fill, pb, k.p, (size_t)k.ls, (size_t)k.w * 4, k.h);
             fill += fb;
         }
         STAGECHK(v, hipMemcpyAsync(fa.arena + run_at, fa.staging, fill, hipMemcpyHostToDevice, st));
@@ -458,8 +450,7 @@ extern "C" int ntscsim_blend_frames_host(ntscsim_ctx *c, const ntscsim_blend_des
         for (int i = 0; i < m; i++) {
             const ntscsim_blend_desc &d = descs[at + i];
             const size_t pb = pitch(d.width);
-            for (int y = 0; y < d.height; y++)
-                std::memcpy(static_cast<uint8_t *>(d.dst_dev) + (size_t)y * (size_t)d.dst_linesize, fa.staging + off + (size_t)y * pb, (size_t)d.width * 4);
+            copy_rows(d.dst_dev, (size_t)d.dst_linesize, fa.staging + off, pb, (size_t)d.width * 4, d.height);
             off += pb * (size_t)d.height;
         }
     }

@@ -589,9 +589,8 @@ int key_launch(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n, const KeyCl
             const dim3 grid((k->lanes + KEY_DRAW_THREADS - 1) / KEY_DRAW_THREADS, (unsigned)std::min<size_t>(65535, njobs - at));
             hipLaunchKernelGGL(k_key_draw, grid, dim3(KEY_DRAW_THREADS), 0, st, jobs_dev + at, k->polys_dev, k->lanes);
         }
-        STAGECHK(v, hipGetLastError());
-        if (!v.kernels->empty()) *v.kernels += ';';
-        *v.kernels += "k_key_draw";
+        const int drc = stage_launched(v, nullptr, st, "k_key_draw");                // the slot stays with the kernel below
+        if (drc != NTSCSIM_OK) return drc;
     }
 
     KeyCfg cfg;
@@ -633,15 +632,10 @@ int key_launch(ntscsim_ctx *c, const ntscsim_key_desc *descs, int n, const KeyCl
             else hipLaunchKernelGGL(k_key_fast<false>, grid, block, 0, st, recs_dev, cfg, W, H, nl);
         }
     }
-    STAGECHK(v, hipGetLastError());
-    STAGECHK(v, hipEventRecord(s.done, st));
-    s.used = true;
-    if (!v.kernels->empty()) *v.kernels += ';';
-    *v.kernels += clip ? (general ? "k_key_clip_general<" : "k_key_clip_fast<") : (general ? "k_key_general<" : "k_key_fast<");
-    *v.kernels += noise ? "true" : "false";
-    if (clip && !general) *v.kernels += "," + std::to_string(nl);
-    *v.kernels += ">";
-    return NTSCSIM_OK;
+    std::string name = clip ? (general ? "k_key_clip_general<" : "k_key_clip_fast<") : (general ? "k_key_general<" : "k_key_fast<");
+    name += noise ? "true" : "false";
+    if (clip && !general) name += "," + std::to_string(nl);
+    return stage_launched(v, &s, st, name + ">");
 }
 
 // frames a launch may carry: the hit bits of one launch stay below the limit (128 MiB), one frame at the least

@@ -1,7 +1,9 @@
-// ntsc_layer.hpp -- the host logic the layer stages share (colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip):
-// what a call may alias, where a run of descriptors has to be cut into launches, which host frames are one frame.
-// Templates over the stage's descriptor type: ntscsim_key_desc / ntscsim_avg_desc (and their _src) have the same fields
-// up to the last uint64_t, which nothing here touches.  No HIP in it: plain C++, so that it can be driven without a GPU.
+// ntsc_layer.hpp -- the host logic only the layer stages share (colorkey: csrc/ntsc_key.hip, average_delay:
+// csrc/ntsc_avg.hip): what a descriptor of bound layers must satisfy, a clip call's frames as descriptors, which host
+// frames are one frame.  Spans, the plane check, the in-order launch planner and the writes of a call are every stage's:
+// ntsc_frames.hpp.  Templates over the stage's descriptor type: ntscsim_key_desc / ntscsim_avg_desc (and their _src)
+// have the same fields up to the last uint64_t, which nothing here touches.  No HIP in it: plain C++, so that it can be
+// driven without a GPU.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -12,12 +14,9 @@
 #include <vector>
 
 #include "ntscsim.h"
+#include "ntsc_frames.hpp"
 
 namespace ntscsim {
-
-struct Span { uintptr_t a, b; };
-inline bool overlaps(const Span &x, const Span &y) { return x.a < y.b && y.a < x.b; }
-inline Span span_of(const void *p, int ls, int H) { return Span{(uintptr_t)p, (uintptr_t)p + (size_t)ls * (size_t)H}; }
 
 struct LayerGeom { int W, H, nl; };      // what the bound params fix for every descriptor
 
@@ -29,20 +28,19 @@ int check_desc(const LayerGeom &g, const Desc &d)
     const int W = g.W, H = g.H;
     if (!d.dst_dev || (d.n_layers > 0 && !d.layers)) return NTSCSIM_E_ARG;
     if (d.width != W || d.height != H || d.n_layers != g.nl) return NTSCSIM_E_SIZE;
-    if (d.dst_linesize < 4 * W || (d.dst_linesize & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_SIZE;
+    if (plane_check(d.dst_dev, d.dst_linesize, W, true)) return NTSCSIM_E_SIZE;
     const Span ds = span_of(d.dst_dev, d.dst_linesize, H);
     for (int l = 0; l < d.n_layers; l++) {
         const auto &s = d.layers[l];
         if (!s.src_dev) continue;
-        if (s.src_linesize < 4 * W || (s.src_linesize & 3) || ((uintptr_t)s.src_dev & 3)) return NTSCSIM_E_SIZE;
+        if (plane_check(s.src_dev, s.src_linesize, W, true)) return NTSCSIM_E_SIZE;
         if (overlaps(ds, span_of(s.src_dev, s.src_linesize, H))) return NTSCSIM_E_ARG;
     }
     return NTSCSIM_OK;
 }
 
 // *_frames_device(): every descriptor checked, then launch(first descriptor, count) for runs of at most `cap`
-// descriptors.  Descriptors take effect in order: a launch ends in front of the first descriptor that writes what the
-// launch reads or writes, or reads what it writes.
+// descriptors, cut where descriptors depend on each other (frames_in_order()).  An absent layer reads nothing.
 template <class Desc, class Launch>
 int layer_frames_in_order(const LayerGeom &g, const Desc *descs, int n, int cap, Launch &&launch)
 {
@@ -50,36 +48,12 @@ int layer_frames_in_order(const LayerGeom &g, const Desc *descs, int n, int cap,
         const int rc = check_desc(g, descs[i]);
         if (rc != NTSCSIM_OK) return rc;
     }
-    const int H = g.H;
-    std::vector<Span> wr, rd;
-    int first = 0;
-    for (int i = 0; i <= n; i++) {
-        bool cut = i == n || i - first >= cap;
-        if (!cut) {
-            const Desc &d = descs[i];
-            const Span ds = span_of(d.dst_dev, d.dst_linesize, H);
-            for (const Span &w : wr) if (overlaps(ds, w)) { cut = true; break; }
-            for (size_t j = 0; !cut && j < rd.size(); j++) cut = overlaps(ds, rd[j]);
-            for (int l = 0; !cut && l < d.n_layers; l++) {
-                if (!d.layers[l].src_dev) continue;
-                const Span ss = span_of(d.layers[l].src_dev, d.layers[l].src_linesize, H);
-                for (const Span &w : wr) if (overlaps(ss, w)) { cut = true; break; }
-            }
-        }
-        if (cut && i > first) {
-            const int rc = launch(descs + first, i - first);
-            if (rc != NTSCSIM_OK) return rc;
-            first = i;
-            wr.clear(); rd.clear();
-        }
-        if (i < n) {
-            const Desc &d = descs[i];
-            wr.push_back(span_of(d.dst_dev, d.dst_linesize, H));
-            for (int l = 0; l < d.n_layers; l++)
-                if (d.layers[l].src_dev) rd.push_back(span_of(d.layers[l].src_dev, d.layers[l].src_linesize, H));
-        }
-    }
-    return NTSCSIM_OK;
+    return frames_in_order(n, cap, [&](int i, std::vector<Span> &rd) {
+        const Desc &d = descs[i];
+        for (int l = 0; l < d.n_layers; l++)
+            if (d.layers[l].src_dev) rd.push_back(span_of(d.layers[l].src_dev, d.layers[l].src_linesize, g.H));
+        return span_of(d.dst_dev, d.dst_linesize, g.H);
+    }, [&](int first, int m) { return launch(descs + first, m); });
 }
 
 // *_clip_device(): what the call writes (ring, outputs) must be disjoint from itself and from every source; then the
@@ -92,25 +66,22 @@ int layer_clip_descs(const LayerGeom &g, int delay, void *const *ring_dev, int r
                      std::vector<Desc> &descs, std::vector<LayerSrcOf<Desc>> &lays)
 {
     const int W = g.W, H = g.H, nl = g.nl;
-    if (ring_linesize < 4 * W || (ring_linesize & 3) || out_linesize < 4 * W || (out_linesize & 3)) return NTSCSIM_E_SIZE;
-    std::vector<Span> wr;
+    if (plane_check(nullptr, ring_linesize, W, true) || plane_check(nullptr, out_linesize, W, true)) return NTSCSIM_E_SIZE;
+    CallWrites wr;
     for (int i = 0; i < delay; i++) {
         if (!ring_dev[i]) return NTSCSIM_E_ARG;
-        if ((uintptr_t)ring_dev[i] & 3) return NTSCSIM_E_SIZE;
-        wr.push_back(span_of(ring_dev[i], ring_linesize, H));
+        if (plane_check(ring_dev[i], ring_linesize, W, true)) return NTSCSIM_E_SIZE;
+        wr.add(span_of(ring_dev[i], ring_linesize, H));
     }
     for (int t = 0; t < T; t++) {
         if (!out_dev[t]) return NTSCSIM_E_ARG;
-        if ((uintptr_t)out_dev[t] & 3) return NTSCSIM_E_SIZE;
-        wr.push_back(span_of(out_dev[t], out_linesize, H));
+        if (plane_check(out_dev[t], out_linesize, W, true)) return NTSCSIM_E_SIZE;
+        wr.add(span_of(out_dev[t], out_linesize, H));
     }
-    const auto by_start = [](const Span &x, const Span &y) { return x.a < y.a; };
-    std::sort(wr.begin(), wr.end(), by_start);
-    for (size_t i = 1; i < wr.size(); i++)
-        if (wr[i].a < wr[i - 1].b) return NTSCSIM_E_ARG;
+    if (wr.sort() != NTSCSIM_OK) return NTSCSIM_E_ARG;
     if (every_linesize)
         for (int l = 0; l < nl; l++)
-            if (src_linesize[l] < 4 * W || (src_linesize[l] & 3)) return NTSCSIM_E_SIZE;
+            if (plane_check(nullptr, src_linesize[l], W, true)) return NTSCSIM_E_SIZE;
     descs.assign((size_t)T, Desc());
     lays.assign((size_t)T * (size_t)nl, LayerSrcOf<Desc>());
     for (int t = 0; t < T; t++) {
@@ -124,11 +95,8 @@ int layer_clip_descs(const LayerGeom &g, int delay, void *const *ring_dev, int r
             s._pad = 0;
             if (!s.src_dev) continue;
             // (with every_linesize the linesize has passed already: only the pointer can fail here)
-            if (s.src_linesize < 4 * W || (s.src_linesize & 3) || ((uintptr_t)s.src_dev & 3)) return NTSCSIM_E_SIZE;
-            const Span ss = span_of(s.src_dev, s.src_linesize, H);
-            auto it = std::upper_bound(wr.begin(), wr.end(), ss, by_start);
-            if (it != wr.end() && overlaps(ss, *it)) return NTSCSIM_E_ARG;
-            if (it != wr.begin() && overlaps(ss, *(it - 1))) return NTSCSIM_E_ARG;
+            if (plane_check(s.src_dev, s.src_linesize, W, true)) return NTSCSIM_E_SIZE;
+            if (wr.hits(span_of(s.src_dev, s.src_linesize, H))) return NTSCSIM_E_ARG;
         }
     }
     return NTSCSIM_OK;
@@ -152,14 +120,14 @@ int host_frames_plan(const LayerGeom &g, const Desc *descs, int n, HostFrames &p
     for (int i = 0; i < n; i++) {
         const Desc &d = descs[i];
         if (!d.dst_dev || (d.n_layers > 0 && !d.layers)) return NTSCSIM_E_ARG;
-        if (d.width != W || d.height != H || d.n_layers != g.nl || d.dst_linesize < 4 * W) return NTSCSIM_E_SIZE;
+        if (d.width != W || d.height != H || d.n_layers != g.nl || plane_check(d.dst_dev, d.dst_linesize, W, false)) return NTSCSIM_E_SIZE;
         const HostFrame dk(d.dst_dev, d.dst_linesize);
         if (p.where.emplace(dk, p.order.size() * p.fb).second) p.order.push_back(dk);
         if (std::find(p.dsts.begin(), p.dsts.end(), dk) == p.dsts.end()) p.dsts.push_back(dk);
         for (int l = 0; l < d.n_layers; l++) {
             const auto &s = d.layers[l];
             if (!s.src_dev) continue;
-            if (s.src_linesize < 4 * W) return NTSCSIM_E_SIZE;
+            if (plane_check(s.src_dev, s.src_linesize, W, false)) return NTSCSIM_E_SIZE;
             const HostFrame sk(s.src_dev, s.src_linesize);
             if (p.where.emplace(sk, p.order.size() * p.fb).second) p.order.push_back(sk);
         }

@@ -1,7 +1,6 @@
 // ntsc_layer_frames.hpp -- *_frames_host() of the layer stages (colorkey: csrc/ntsc_key.hip, average_delay:
 // csrc/ntsc_avg.hip): the plan of ntsc_layer.hpp carried out through the stage's FrameArena.
 #pragma once
-#include <cstring>
 #include <vector>
 
 #include "ntsc_layer.hpp"
@@ -23,8 +22,7 @@ int layer_frames_host(const CtxStageView &v, FrameArena &a, const LayerGeom &g, 
     const size_t row = (size_t)g.W * 4;
     hipStream_t st = v.stream;
     for (const HostFrame &f : p.order) {
-        for (int y = 0; y < g.H; y++)
-            std::memcpy(a.staging + (size_t)y * p.pitch, static_cast<const uint8_t *>(f.first) + (size_t)y * (size_t)f.second, row);
+        copy_rows(a.staging, p.pitch, f.first, (size_t)f.second, row, g.H);
         STAGECHK(v, hipMemcpyAsync(a.arena + p.where[f], a.staging, p.fb, hipMemcpyHostToDevice, st));
         STAGECHK(v, hipStreamSynchronize(st));
     }
@@ -36,8 +34,7 @@ int layer_frames_host(const CtxStageView &v, FrameArena &a, const LayerGeom &g, 
     for (const HostFrame &f : p.dsts) {
         STAGECHK(v, hipMemcpyAsync(a.staging, a.arena + p.where[f], p.fb, hipMemcpyDeviceToHost, st));
         STAGECHK(v, hipStreamSynchronize(st));
-        for (int y = 0; y < g.H; y++)
-            std::memcpy(static_cast<uint8_t *>(const_cast<void *>(f.first)) + (size_t)y * (size_t)f.second, a.staging + (size_t)y * p.pitch, row);
+        copy_rows(const_cast<void *>(f.first), (size_t)f.second, a.staging, p.pitch, row, g.H);
     }
     return NTSCSIM_OK;
 }

@@ -24,7 +24,7 @@
 
 #include "ntscsim.h"
 #include "led_run.hpp"
-#include "ntsc_layer.hpp"
+#include "ntsc_frames.hpp"
 #include "ntsc_px4.hpp"
 #include "ntsc_stage.hpp"
 
@@ -249,15 +249,23 @@ namespace {
 
 bool led_size_ok(int w, int h) { return w >= LED_MIN_SIZE && w <= LED_MAX_WIDTH && h >= LED_MIN_SIZE && h <= LED_MAX_HEIGHT; }
 
-int led_check_desc(const LedState *k, const ntscsim_led_desc &d)
+// aligned: a device call; a host frame may lie anywhere and have any linesize that holds a row
+int led_check_desc(const LedState *k, const ntscsim_led_desc &d, bool aligned)
 {
     const int W = k->prm.width, H = k->prm.height;
     if (!d.dst_dev || !d.src_dev) return NTSCSIM_E_ARG;
     if (d.width != W || d.height != H) return NTSCSIM_E_SIZE;
-    if (d.dst_linesize < 4 * W || (d.dst_linesize & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_SIZE;
-    if (d.src_linesize < 4 * W || (d.src_linesize & 3) || ((uintptr_t)d.src_dev & 3)) return NTSCSIM_E_SIZE;
+    if (plane_check(d.dst_dev, d.dst_linesize, W, aligned)) return NTSCSIM_E_SIZE;
+    if (plane_check(d.src_dev, d.src_linesize, W, aligned)) return NTSCSIM_E_SIZE;
     if (overlaps(span_of(d.dst_dev, d.dst_linesize, H), span_of(d.src_dev, d.src_linesize, H))) return NTSCSIM_E_ARG;
     return NTSCSIM_OK;
+}
+
+// what descriptor i touches, for frames_in_order()
+Span led_touch(const ntscsim_led_desc &d, int H, std::vector<Span> &rd)
+{
+    rd.push_back(span_of(d.src_dev, d.src_linesize, H));
+    return span_of(d.dst_dev, d.dst_linesize, H);
 }
 
 // one launch over descriptors that do not depend on each other; frame0: index of descs[0] in the call
@@ -287,23 +295,18 @@ int led_launch(ntscsim_ctx *c, const ntscsim_led_desc *descs, int m, int frame0,
     const dim3 grid((unsigned)((H + LED_BAND - 1) / LED_BAND), (unsigned)m), block(LED_THREADS);
     if (k->src_dwords) hipLaunchKernelGGL(k_led_frames<false>, grid, block, 0, st, recs_dev, W, H);
     else hipLaunchKernelGGL(k_led_frames<true>, grid, block, 0, st, recs_dev, W, H);
-    STAGECHK(v, hipGetLastError());
-    STAGECHK(v, hipEventRecord(s.done, st));
-    s.used = true;
-    if (!v.kernels->empty()) *v.kernels += ';';
-    *v.kernels += k->src_dwords ? "k_led_frames<dwords>" : "k_led_frames";
-    return NTSCSIM_OK;
+    return stage_launched(v, &s, st, k->src_dwords ? "k_led_frames<dwords>" : "k_led_frames");
 }
 
-// every descriptor checked, then launches of at most 65535 descriptors; a launch ends in front of the first
-// descriptor that writes what the launch reads or writes, or reads what it writes: descriptors take effect in order
+// every descriptor checked, then launches of at most 65535 descriptors, cut where descriptors depend on each other:
+// they take effect in order (frames_in_order())
 int led_frames(ntscsim_ctx *c, const ntscsim_led_desc *descs, int n, hipStream_t st)
 {
     CtxStageView v = ctx_stage_view(c);
     LedState *k = *v.led;
     const int H = k->prm.height;
     for (int i = 0; i < n; i++) {
-        const int rc = led_check_desc(k, descs[i]);
+        const int rc = led_check_desc(k, descs[i], true);
         if (rc != NTSCSIM_OK) return rc;
     }
     STAGECHK(v, hipSetDevice(v.device));
@@ -320,27 +323,9 @@ int led_frames(ntscsim_ctx *c, const ntscsim_led_desc *descs, int n, hipStream_t
         }
         k->edges_h = H;
     }
-    std::vector<Span> wr, rd;
-    int first = 0;
-    for (int i = 0; i <= n; i++) {
-        bool cut = i == n || i - first >= 65535;
-        if (!cut) {
-            const Span ds = span_of(descs[i].dst_dev, descs[i].dst_linesize, H);
-            const Span ss = span_of(descs[i].src_dev, descs[i].src_linesize, H);
-            for (const Span &w : wr) if (overlaps(ds, w) || overlaps(ss, w)) { cut = true; break; }
-            for (size_t j = 0; !cut && j < rd.size(); j++) cut = overlaps(ds, rd[j]);
-        }
-        if (cut && i > first) {
-            const int rc = led_launch(c, descs + first, i - first, first, st);
-            if (rc != NTSCSIM_OK) return rc;
-            first = i;
-            wr.clear(); rd.clear();
-        }
-        if (i < n) {
-            wr.push_back(span_of(descs[i].dst_dev, descs[i].dst_linesize, H));
-            rd.push_back(span_of(descs[i].src_dev, descs[i].src_linesize, H));
-        }
-    }
+    const int rc = frames_in_order(n, 65535, [&](int i, std::vector<Span> &rd) { return led_touch(descs[i], H, rd); },
+                                   [&](int first, int m) { return led_launch(c, descs + first, m, first, st); });
+    if (rc != NTSCSIM_OK) return rc;
     if (k->keep) k->edges_frames = n;
     return NTSCSIM_OK;
 }
@@ -386,11 +371,8 @@ extern "C" int ntscsim_led_frames_host(ntscsim_ctx *c, const ntscsim_led_desc *d
     if (!k) return NTSCSIM_E_ARG;
     const int W = k->prm.width, H = k->prm.height;
     for (int i = 0; i < n; i++) {
-        const ntscsim_led_desc &d = descs[i];
-        if (!d.dst_dev || !d.src_dev) return NTSCSIM_E_ARG;
-        if (d.width != W || d.height != H) return NTSCSIM_E_SIZE;
-        if (d.dst_linesize < 4 * W || (d.dst_linesize & 3) || d.src_linesize < 4 * W || (d.src_linesize & 3)) return NTSCSIM_E_SIZE;
-        if (overlaps(span_of(d.dst_dev, d.dst_linesize, H), span_of(d.src_dev, d.src_linesize, H))) return NTSCSIM_E_ARG;
+        const int rc = led_check_desc(k, descs[i], false);
+        if (rc != NTSCSIM_OK) return rc;
     }
     STAGECHK(v, hipSetDevice(v.device));
     v.kernels->clear();
@@ -399,52 +381,35 @@ extern "C" int ntscsim_led_frames_host(ntscsim_ctx *c, const ntscsim_led_desc *d
     // A batch ends in front of a descriptor that touches a frame an earlier one of the batch wrote, or writes one it
     // read: descriptors take effect in order, through host memory.
     hipStream_t st = v.stream;
-    const size_t pitch = ((size_t)W * 4 + 15) & ~(size_t)15, fbytes = pitch * (size_t)H;
+    const size_t row = (size_t)W * 4, pitch = (row + 15) & ~(size_t)15, fbytes = pitch * (size_t)H;
     const int cap = (int)std::max<size_t>(1, std::min<size_t>(65535, ((size_t)256 << 20) / (2 * fbytes)));
     std::string kernels;
-    std::vector<ntscsim_led_desc> dd;
-    std::vector<Span> wr, rd;
-    for (int first = 0; first < n;) {
-        int m = 0;
-        wr.clear(); rd.clear();
-        for (; first + m < n && m < cap; m++) {
-            const ntscsim_led_desc &d = descs[first + m];
-            const Span ds = span_of(d.dst_dev, d.dst_linesize, H), ss = span_of(d.src_dev, d.src_linesize, H);
-            bool cut = false;
-            for (const Span &w : wr) if (overlaps(ds, w) || overlaps(ss, w)) { cut = true; break; }
-            for (size_t j = 0; !cut && j < rd.size(); j++) cut = overlaps(ds, rd[j]);
-            if (cut) break;
-            wr.push_back(ds); rd.push_back(ss);
-        }
-        const int rc = k->frames.reserve(v, 2 * fbytes * (size_t)m, fbytes * (size_t)m);
-        if (rc != NTSCSIM_OK) return rc;
+    std::vector<ntscsim_led_desc> dev;
+    const auto touch = [&](int i, std::vector<Span> &rd) { return led_touch(descs[i], H, rd); };
+    const int rc = frames_in_order(n, cap, touch, [&](int first, int m) -> int {
+        const int arc = k->frames.reserve(v, 2 * fbytes * (size_t)m, fbytes * (size_t)m);
+        if (arc != NTSCSIM_OK) return arc;
         unsigned char *stage = k->frames.staging, *arena = k->frames.arena;
-        dd.assign(descs + first, descs + first + m);
+        dev.assign(descs + first, descs + first + m);
         for (int i = 0; i < m; i++) {
-            const uint8_t *hs = static_cast<const uint8_t *>(dd[(size_t)i].src_dev);
-            for (int y = 0; y < H; y++)
-                std::memcpy(stage + (size_t)i * fbytes + (size_t)y * pitch, hs + (size_t)y * (size_t)dd[(size_t)i].src_linesize, (size_t)W * 4);
+            ntscsim_led_desc &d = dev[(size_t)i];
+            copy_rows(stage + (size_t)i * fbytes, pitch, d.src_dev, (size_t)d.src_linesize, row, H);
+            d.src_dev = arena + (size_t)i * fbytes;
+            d.dst_dev = arena + (size_t)(m + i) * fbytes;
+            d.src_linesize = d.dst_linesize = (int)pitch;
         }
         STAGECHK(v, hipMemcpyAsync(arena, stage, fbytes * (size_t)m, hipMemcpyHostToDevice, st));
-        std::vector<ntscsim_led_desc> dev = dd;
-        for (int i = 0; i < m; i++) {
-            dev[(size_t)i].src_dev = arena + (size_t)i * fbytes;
-            dev[(size_t)i].dst_dev = arena + (size_t)(m + i) * fbytes;
-            dev[(size_t)i].src_linesize = dev[(size_t)i].dst_linesize = (int)pitch;
-        }
-        const int rc2 = led_frames(c, dev.data(), m, st);
-        if (rc2 != NTSCSIM_OK) return rc2;
+        const int frc = led_frames(c, dev.data(), m, st);
+        if (frc != NTSCSIM_OK) return frc;
         if (!kernels.empty()) kernels += ';';
         kernels += *v.kernels;
         STAGECHK(v, hipMemcpyAsync(stage, arena + (size_t)m * fbytes, fbytes * (size_t)m, hipMemcpyDeviceToHost, st));
         STAGECHK(v, hipStreamSynchronize(st));
-        for (int i = 0; i < m; i++) {
-            uint8_t *hd = static_cast<uint8_t *>(dd[(size_t)i].dst_dev);
-            for (int y = 0; y < H; y++)
-                std::memcpy(hd + (size_t)y * (size_t)dd[(size_t)i].dst_linesize, stage + (size_t)i * fbytes + (size_t)y * pitch, (size_t)W * 4);
-        }
-        first += m;
-    }
+        for (int i = 0; i < m; i++)
+            copy_rows(descs[first + i].dst_dev, (size_t)descs[first + i].dst_linesize, stage + (size_t)i * fbytes, pitch, row, H);
+        return NTSCSIM_OK;
+    });
+    if (rc != NTSCSIM_OK) return rc;
     *v.kernels = kernels;
     return NTSCSIM_OK;
 }

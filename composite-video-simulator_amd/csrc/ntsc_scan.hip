@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "ntscsim.h"
-#include "ntsc_layer.hpp"
+#include "ntsc_frames.hpp"
 #include "ntsc_px4.hpp"
 #include "ntsc_stage.hpp"
 
@@ -309,13 +309,14 @@ namespace {
 bool scan_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= (1 << 16) && h <= (1 << 16); }
 bool scan_src_ok(int w, int h) { return scan_size_ok(w, h) && 2ull * (uint64_t)w * (uint64_t)h < (1ull << 31); }
 
-int scan_check_desc(const ScanState *k, const ntscsim_scan_desc &d)
+// aligned: a device call; a host frame may lie anywhere and have any linesize that holds a row
+int scan_check_desc(const ScanState *k, const ntscsim_scan_desc &d, bool aligned)
 {
     const int W = k->prm.output_width, H = k->prm.output_height;
     if (!d.dst_dev || !d.src_dev) return NTSCSIM_E_ARG;
     if (!scan_src_ok(d.src_width, d.src_height)) return NTSCSIM_E_SIZE;
-    if (d.dst_linesize < 4 * W || (d.dst_linesize & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_SIZE;
-    if (d.src_linesize < 4 * d.src_width || (d.src_linesize & 3) || ((uintptr_t)d.src_dev & 3)) return NTSCSIM_E_SIZE;
+    if (plane_check(d.dst_dev, d.dst_linesize, W, aligned)) return NTSCSIM_E_SIZE;
+    if (plane_check(d.src_dev, d.src_linesize, d.src_width, aligned)) return NTSCSIM_E_SIZE;
     if (overlaps(span_of(d.dst_dev, d.dst_linesize, H), span_of(d.src_dev, d.src_linesize, d.src_height))) return NTSCSIM_E_ARG;
     return NTSCSIM_OK;
 }
@@ -466,25 +467,21 @@ int scan_launch(ntscsim_ctx *c, const ntscsim_scan_desc *descs, int m, bool zero
     const long long per = std::max(1LL, std::min((quads + SCAN_RESOLVE_THREADS - 1) / SCAN_RESOLVE_THREADS, (2048LL + m - 1) / m));
     hipLaunchKernelGGL(k_scan_resolve, dim3((unsigned)per, (unsigned)m), dim3(SCAN_RESOLVE_THREADS), 0, st, recs_dev, W, H);
     STAGECHK(v, hipGetLastError());
-    STAGECHK(v, hipEventRecord(s.done, st));
-    s.used = true;
-    STAGECHK(v, hipEventRecord(k->tail, st));
+    STAGECHK(v, hipEventRecord(k->tail, st));                                   // in front of the slot's: a failure of either leaves no name
     k->tail_used = true;
     k->tail_stream = st;
-    if (!v.kernels->empty()) *v.kernels += ';';
-    *v.kernels += "k_scan_splat;k_scan_resolve";
-    return NTSCSIM_OK;
+    return stage_launched(v, &s, st, "k_scan_splat;k_scan_resolve");
 }
 
-// every descriptor checked, then launches of at most SCAN_PLANES descriptors; a launch ends in front of the first
-// descriptor that writes what the launch reads or writes, or reads what it writes: descriptors take effect in order
+// every descriptor checked, then launches of at most SCAN_PLANES descriptors, cut where descriptors depend on each
+// other: they take effect in order (frames_in_order())
 int scan_frames(ntscsim_ctx *c, const ntscsim_scan_desc *descs, int n, bool zero_row0, hipStream_t st)
 {
     CtxStageView v = ctx_stage_view(c);
     ScanState *k = *v.scan;
     const int H = k->prm.output_height;
     for (int i = 0; i < n; i++) {
-        const int rc = scan_check_desc(k, descs[i]);
+        const int rc = scan_check_desc(k, descs[i], true);
         if (rc != NTSCSIM_OK) return rc;
     }
     STAGECHK(v, hipSetDevice(v.device));
@@ -495,28 +492,10 @@ int scan_frames(ntscsim_ctx *c, const ntscsim_scan_desc *descs, int n, bool zero
     int rc = scan_planes(v, k, 1);
     if (rc != NTSCSIM_OK) return rc;
     STAGECHK(v, hipMemsetAsync(k->counters, 0, 2 * sizeof(unsigned int), st));
-    std::vector<Span> wr, rd;
-    int first = 0;
-    for (int i = 0; i <= n; i++) {
-        bool cut = i == n || i - first >= SCAN_PLANES;
-        if (!cut) {
-            const Span ds = span_of(descs[i].dst_dev, descs[i].dst_linesize, H);
-            const Span ss = span_of(descs[i].src_dev, descs[i].src_linesize, descs[i].src_height);
-            for (const Span &w : wr) if (overlaps(ds, w) || overlaps(ss, w)) { cut = true; break; }
-            for (size_t j = 0; !cut && j < rd.size(); j++) cut = overlaps(ds, rd[j]);
-        }
-        if (cut && i > first) {
-            rc = scan_launch(c, descs + first, i - first, zero_row0, i == n, st);
-            if (rc != NTSCSIM_OK) return rc;
-            first = i;
-            wr.clear(); rd.clear();
-        }
-        if (i < n) {
-            wr.push_back(span_of(descs[i].dst_dev, descs[i].dst_linesize, H));
-            rd.push_back(span_of(descs[i].src_dev, descs[i].src_linesize, descs[i].src_height));
-        }
-    }
-    return NTSCSIM_OK;
+    return frames_in_order(n, SCAN_PLANES, [&](int i, std::vector<Span> &rd) {
+        rd.push_back(span_of(descs[i].src_dev, descs[i].src_linesize, descs[i].src_height));
+        return span_of(descs[i].dst_dev, descs[i].dst_linesize, H);
+    }, [&](int first, int m) { return scan_launch(c, descs + first, m, zero_row0, first + m == n, st); });
 }
 
 ScanState *scan_state(ntscsim_ctx *c) { return c ? *ctx_stage_view(c).scan : nullptr; }
@@ -564,27 +543,20 @@ extern "C" int ntscsim_scan_clip_device(ntscsim_ctx *c, const void *const *src_d
     if (T > (1 << 24)) return NTSCSIM_E_SIZE;
     const int H = k->prm.output_height;
     std::vector<ntscsim_scan_desc> descs((size_t)T);
-    std::vector<Span> wr;
+    CallWrites wr;
     for (int t = 0; t < T; t++) {
         ntscsim_scan_desc &d = descs[(size_t)t];
         d.dst_dev = out_dev[t]; d.dst_linesize = out_linesize;
         d.src_dev = src_dev[t]; d.src_linesize = src_linesize; d.src_width = src_w; d.src_height = src_h;
         d.fieldno = *fieldno + (uint64_t)t;
-        const int rc = scan_check_desc(k, d);
+        const int rc = scan_check_desc(k, d, true);
         if (rc != NTSCSIM_OK) return rc;
-        wr.push_back(span_of(d.dst_dev, d.dst_linesize, H));
+        wr.add(span_of(d.dst_dev, d.dst_linesize, H));
     }
     // the outputs must be disjoint from each other and from every source
-    const auto by_start = [](const Span &x, const Span &y) { return x.a < y.a; };
-    std::sort(wr.begin(), wr.end(), by_start);
-    for (size_t i = 1; i < wr.size(); i++)
-        if (wr[i].a < wr[i - 1].b) return NTSCSIM_E_ARG;
-    for (int t = 0; t < T; t++) {
-        const Span ss = span_of(src_dev[t], src_linesize, src_h);
-        auto it = std::upper_bound(wr.begin(), wr.end(), ss, by_start);
-        if (it != wr.end() && overlaps(ss, *it)) return NTSCSIM_E_ARG;
-        if (it != wr.begin() && overlaps(ss, *(it - 1))) return NTSCSIM_E_ARG;
-    }
+    if (wr.sort() != NTSCSIM_OK) return NTSCSIM_E_ARG;
+    for (int t = 0; t < T; t++)
+        if (wr.hits(span_of(src_dev[t], src_linesize, src_h))) return NTSCSIM_E_ARG;
     const int rc = scan_frames(c, descs.data(), T, true, hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream);
     if (rc != NTSCSIM_OK) return rc;
     *fieldno += (uint64_t)T;
@@ -599,27 +571,22 @@ extern "C" int ntscsim_scan_frames_host(ntscsim_ctx *c, const ntscsim_scan_desc 
     if (!k) return NTSCSIM_E_ARG;
     const int W = k->prm.output_width, H = k->prm.output_height;
     for (int i = 0; i < n; i++) {
-        const ntscsim_scan_desc &d = descs[i];
-        if (!d.dst_dev || !d.src_dev) return NTSCSIM_E_ARG;
-        if (!scan_src_ok(d.src_width, d.src_height) || d.dst_linesize < 4 * W || d.src_linesize < 4 * d.src_width) return NTSCSIM_E_SIZE;
-        if (overlaps(span_of(d.dst_dev, d.dst_linesize, H), span_of(d.src_dev, d.src_linesize, d.src_height))) return NTSCSIM_E_ARG;
+        const int rc = scan_check_desc(k, descs[i], false);
+        if (rc != NTSCSIM_OK) return rc;
     }
     STAGECHK(v, hipSetDevice(v.device));
     // one descriptor at a time through the arena: destination | source, rows packed to a 16-byte pitch, the
     // destination up as well as down because the device call leaves row 0 of a field == 1 frame alone
     hipStream_t st = v.stream;
-    const size_t dpitch = ((size_t)W * 4 + 15) & ~(size_t)15, dbytes = dpitch * (size_t)H;
+    const size_t drow = (size_t)W * 4, dpitch = (drow + 15) & ~(size_t)15, dbytes = dpitch * (size_t)H;
     for (int i = 0; i < n; i++) {
         const ntscsim_scan_desc &d = descs[i];
-        const size_t spitch = ((size_t)d.src_width * 4 + 15) & ~(size_t)15, sbytes = spitch * (size_t)d.src_height;
+        const size_t srow = (size_t)d.src_width * 4, spitch = (srow + 15) & ~(size_t)15, sbytes = spitch * (size_t)d.src_height;
         const int rc = k->frames.reserve(v, dbytes + sbytes, dbytes + sbytes);
         if (rc != NTSCSIM_OK) return rc;
         unsigned char *stage = k->frames.staging, *arena = k->frames.arena;
-        uint8_t *hd = static_cast<uint8_t *>(d.dst_dev);
-        const uint8_t *hs = static_cast<const uint8_t *>(d.src_dev);
-        for (int y = 0; y < H; y++) std::memcpy(stage + (size_t)y * dpitch, hd + (size_t)y * (size_t)d.dst_linesize, (size_t)W * 4);
-        for (int y = 0; y < d.src_height; y++)
-            std::memcpy(stage + dbytes + (size_t)y * spitch, hs + (size_t)y * (size_t)d.src_linesize, (size_t)d.src_width * 4);
+        copy_rows(stage, dpitch, d.dst_dev, (size_t)d.dst_linesize, drow, H);
+        copy_rows(stage + dbytes, spitch, d.src_dev, (size_t)d.src_linesize, srow, d.src_height);
         STAGECHK(v, hipMemcpyAsync(arena, stage, dbytes + sbytes, hipMemcpyHostToDevice, st));
         ntscsim_scan_desc dd = d;
         dd.dst_dev = arena; dd.dst_linesize = (int)dpitch;
@@ -628,7 +595,7 @@ extern "C" int ntscsim_scan_frames_host(ntscsim_ctx *c, const ntscsim_scan_desc 
         if (rc2 != NTSCSIM_OK) return rc2;
         STAGECHK(v, hipMemcpyAsync(stage, arena, dbytes, hipMemcpyDeviceToHost, st));
         STAGECHK(v, hipStreamSynchronize(st));
-        for (int y = 0; y < H; y++) std::memcpy(hd + (size_t)y * (size_t)d.dst_linesize, stage + (size_t)y * dpitch, (size_t)W * 4);
+        copy_rows(d.dst_dev, (size_t)d.dst_linesize, stage, dpitch, drow, H);
     }
     return NTSCSIM_OK;
 }

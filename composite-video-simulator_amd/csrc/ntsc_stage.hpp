@@ -1,8 +1,8 @@
 // ntsc_stage.hpp -- the host scaffold of the device stages that are translation units of their own (frameblend:
 // csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip): what they see of an ntscsim_ctx,
 // whose definition stays private to ntscsim_hip.hip, the pinned record slots their launches go up through, and the
-// arena their *_frames_host() calls copy host frames through.  What only the two layer stages share: ntsc_layer.hpp
-// (no HIP in it) and ntsc_layer_frames.hpp.
+// arena their *_frames_host() calls copy host frames through.  The host logic without HIP in it: ntsc_frames.hpp (every
+// stage's); what only the two layer stages share: ntsc_layer.hpp (no HIP in it either) and ntsc_layer_frames.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,6 +100,20 @@ struct RecordSlots {
         }
     }
 };
+
+// The tail of a *_launch(): the kernels just enqueued on st have been accepted, slot s (NULL: the kernels are not the
+// last that read it) is busy until they finish, and `name` joins ntscsim_debug_last_kernels().  A failure leaves no name.
+inline int stage_launched(const CtxStageView &v, RecordSlot *s, hipStream_t st, const std::string &name)
+{
+    STAGECHK(v, hipGetLastError());
+    if (s) {
+        STAGECHK(v, hipEventRecord(s->done, st));
+        s->used = true;
+    }
+    if (!v.kernels->empty()) *v.kernels += ';';
+    *v.kernels += name;
+    return NTSCSIM_OK;
+}
 
 struct FrameArena {                      // *_frames_host(): the call's frames in device memory, and pinned staging
     unsigned char *arena = nullptr, *staging = nullptr;

@@ -244,6 +244,24 @@ def test_host_frames_equal_device_call(rig):
         assert int((src[i][1] != frames[i]).sum()) == 0
 
 
+def test_host_call_whose_descriptors_depend_on_each_other(sim):
+    """b = aligned(a), c = aligned(b), d = aligned(c) in one ntscsim_led_frames_host call on host arrays: every
+    descriptor reads what the one before it wrote, so each is a batch of its own and a launch of its own."""
+    w, h = 96, 32
+    led = ntscsim.EdgeAligner(width=w, height=h, sim=sim)
+    frame = R.capture_frame(np.random.RandomState(9632), w, h)
+    a = frame.copy()
+    b, c, d = (np.full((h, w, 4), fill, np.uint8) for fill in (0x11, 0x22, 0x33))
+    led.align_frames_host([(b, a), (c, b), (d, c)])
+    assert led.last_kernels() == ["k_led_frames"] * 3
+    want = frame
+    for i, got in enumerate((b, c, d)):
+        before, want = want, R.align_frame(want)[0]
+        assert int((want != before).sum()) > 0                                    # every pass moves rows: the order shows
+        assert int((got != want).sum()) == 0, "the checker applied %d times" % (i + 1)
+    assert int((a != frame).sum()) == 0
+
+
 def test_simulator_output_is_aligned_without_leaving_the_device():
     """A few -vhs fields from ntscsim_fields_device stay in device memory and are the sources of the stage: the result
     is the checker applied to the simulator's downloaded output."""
