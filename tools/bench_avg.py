@@ -14,6 +14,11 @@ many bytes -- a copy of n bytes reads n and writes n, so the half-size copy is t
 `copy_same_bytes` moves all of them (the yardstick of profiles/blend.json).  `frames_form` is the same clip through
 ntscsim_avg_frames_device, one frame per call (reads the destination at every frame).
 
+Before a size's numbers are printed every case of it is verified against the checker (tools/bench_verify.py;
+--no-verify skips it).  The ring is zeroed in front of the last timed clip call, outside its two events, and what that
+call left is compared: the first 2 * delay + 3 output frames -- the whole clip and the ring where the checker's pace
+allows -- and the ring index and field number behind it.  `frames_verified` and `verify_s` say what was compared.
+
     python tools/bench_avg.py [--frames 600] [--reps 10] [--warmup 3] [--ref-cpu-fps X --ref-cpu-fps-2 Y] [--out profiles/avg.json]
 
 --ref-cpu-fps* record the reference's own loop as measured elsewhere (tests/golden/make_golden_avgdelay.py --bench on
@@ -27,6 +32,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "composite-video-simulator_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_verify as V  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 LEVELS = (128, 64)
@@ -52,6 +60,7 @@ def main():
     ap.add_argument("--ref-cpu-fps", type=float, default=None)
     ap.add_argument("--ref-cpu-fps-2", type=float, default=None)
     ap.add_argument("--out", default=None)
+    V.add_argument(ap)
     a = ap.parse_args()
 
     import torch
@@ -67,9 +76,12 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "frames": T, "reps": a.reps, "warmup": a.warmup,
               "hbm_bytes_per_s": HBM_BYTES_PER_S, "cases": {}}
 
-    def timed(fn):
+    def timed(fn, before_last=None):
+        """before_last: enqueued in front of the last run, outside its two events"""
         ms = []
         for i in range(a.warmup + a.reps):
+            if before_last is not None and i == a.warmup + a.reps - 1:
+                before_last()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             fn()
@@ -79,6 +91,8 @@ def main():
                 ms.append(e0.elapsed_time(e1))
         return statistics.median(ms), min(ms), max(ms)
 
+    if not a.no_verify:
+        import _avg_ref as RA
     sim = ntscsim.FieldSimulator(device=0)
     for size in a.sizes.split(","):
         w, h = (int(x) for x in size.split("x"))
@@ -121,11 +135,18 @@ def main():
                 op = (C.c_void_p * T)(*[out[t].data_ptr() for t in range(T)])
                 lib, hctx = av._lib, av.sim._h
 
+                behind = {}
+
                 def run_clip():
                     ri, field = C.c_int32(0), C.c_uint64(0)
                     rc = lib.ntscsim_avg_clip_device(hctx, rp, 4 * w, C.byref(ri), sp, ls, op, 4 * w, T, C.byref(field), sh)
                     if rc != 0:
                         raise RuntimeError("ntscsim_avg_clip_device: %d" % rc)
+                    behind["ri"], behind["field"] = ri.value, field.value
+
+                def zero_ring():
+                    with torch.cuda.stream(stream):
+                        ring.zero_()
 
                 descs = [av._descs([(ring[t % delay], [src[l, t] for l in range(nl)], t)], lambda x: x.data_ptr(), lambda x: x.stride(0))
                          for t in range(T)]
@@ -136,10 +157,21 @@ def main():
                         if rc != 0:
                             raise RuntimeError("ntscsim_avg_frames_device: %d" % rc)
 
-                k = timed(run_clip)
-                kernels = av.last_kernels()
-                f = timed(run_frames)
                 name = "%dx%d_d%d_l%d" % (w, h, delay, nl)
+                k = timed(run_clip, None if a.no_verify else zero_ring)
+                kernels = av.last_kernels()
+                verified = {}
+                if not a.no_verify:                                               # what the last timed call left, before the frames form writes the ring
+                    if behind["ri"] != T % delay or behind["field"] != T:
+                        V.mismatch("%s: ring index %d, field %d behind the clip (want %d, %d)"
+                                   % (name, behind["ri"], behind["field"], T % delay, T))
+
+                    def step(dst, t, nl=nl, delay=delay):
+                        RA.avg_frame(dst, [src[l, t].cpu().numpy() for l in range(nl)], LEVELS[:nl], t, delay)
+
+                    verified = V.verify_clip(T, delay, (h, w, 4), step, lambda t: out[t].cpu().numpy(),
+                                             lambda i: ring[i].cpu().numpy(), name)
+                f = timed(run_frames)
                 result["cases"][name] = {
                     "width": w, "height": h, "delay": delay, "layers": nl, "newlevels": list(LEVELS[:nl]), "kernels": kernels,
                     "algorithmic_bytes": nbytes,
@@ -148,6 +180,7 @@ def main():
                     "frac_hbm": nbytes / (k[0] * 1e-3) / HBM_BYTES_PER_S,
                     "frames_form_ms": f[0], "frames_form_over_clip": f[0] / k[0],
                 }
+                result["cases"][name].update(verified)
                 del ring, descs
         for nl in (1, 2):
             nbytes = 4 * w * h * (nl + 1) * T

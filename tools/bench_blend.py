@@ -13,6 +13,10 @@ that many bytes from the source clip into the output buffer (hipMemcpyAsync, dev
 than either buffer), and `copy_half` half of them -- a copy of n bytes reads n and writes n, so the half-size copy is
 the one with the kernel's memory traffic.
 
+Before a case's numbers are printed, output frames 0, 1, the middle one and the last are compared with the checker
+(tools/bench_verify.py; --no-verify skips it) as the last timed call left them, before the second copy overwrites them;
+`frames_verified` and `verify_s` say what was compared.
+
     python tools/bench_blend.py [--frames 600] [--reps 20] [--warmup 5] [--ref-cpu-fps X] [--out profiles/blend.json]
 
 --ref-cpu-fps records the reference's own pixel loop as measured elsewhere (tests/golden/make_golden_frameblend.py
@@ -26,6 +30,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "composite-video-simulator_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_verify as V  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 
@@ -48,6 +55,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--ref-cpu-fps", type=float, default=None)
     ap.add_argument("--out", default=None)
+    V.add_argument(ap)
     a = ap.parse_args()
 
     import torch
@@ -112,6 +120,12 @@ def main():
         c0 = timed(copier(nbytes))
         k = timed(run_blend)
         kernels = fb.last_kernels()
+        verified = {}
+        if not a.no_verify:                                                       # what the timed calls left, before the copy overwrites it
+            import _blend_ref as RB
+            verified = V.verify_frames(a.frames, lambda k: RB.blend_frame((h, w), [src[i].cpu().numpy() for i in plan[k][0]], plan[k][1],
+                                                                          2.2 if flags else None),
+                                       lambda k: out[k].cpu().numpy(), name)
         c1 = timed(copier(nbytes))
         ch = timed(copier(nbytes // 2))
         copy_ms = 0.5 * (c0[0] + c1[0])
@@ -128,6 +142,7 @@ def main():
             "blend_over_copy": k[0] / copy_ms,
             "blend_over_copy_half": k[0] / ch[0],
         }
+        case.update(verified)
         result["cases"][name] = case
         print(name, json.dumps(case), flush=True)
         fb.close()

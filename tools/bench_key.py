@@ -14,6 +14,10 @@ copy of n bytes reads n and writes n, so the half-size copy is the one with the 
 moves all of them (the yardstick of profiles/blend.json).  `frames_form` is the same clip through
 ntscsim_key_frames_device, one frame per call (reads the destination at every frame).  `noise_overhead_share` of a
 noisy case is 1 - plain / noisy of the event times: everything noise adds, k_key_draw and the pixel kernel's bit reads.
+Before a size's numbers are printed every case of it is verified against the checker (tools/bench_verify.py;
+--no-verify skips it).  The ring is zeroed in front of the last timed clip call, outside its two events, and what that
+call left is compared: the first 2 * delay + 3 output frames -- the whole clip and the ring where the checker's pace
+allows -- and the ring index and rand() position behind it.  `frames_verified` and `verify_s` say what was compared.
 `draw_kernel_share` is the share of a noisy run spent in k_key_draw itself, by the kernels' own durations: it comes from
 a kernel trace of this tool, taken in a run of its own and folded into the result afterwards:
 
@@ -33,6 +37,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "composite-video-simulator_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_verify as V  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 
@@ -98,6 +105,7 @@ def main():
     ap.add_argument("--ref-cpu-fps", type=float, default=None)
     ap.add_argument("--ref-cpu-fps-noise", type=float, default=None)
     ap.add_argument("--out", default=None)
+    V.add_argument(ap)
     a = ap.parse_args()
     if a.fold_trace:
         if not a.out:
@@ -117,9 +125,12 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "frames": T, "layers": 2, "reps": a.reps, "warmup": a.warmup,
               "hbm_bytes_per_s": HBM_BYTES_PER_S, "cases": {}}
 
-    def timed(fn):
+    def timed(fn, before_last=None):
+        """before_last: enqueued in front of the last run, outside its two events"""
         ms = []
         for i in range(a.warmup + a.reps):
+            if before_last is not None and i == a.warmup + a.reps - 1:
+                before_last()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             fn()
@@ -129,6 +140,9 @@ def main():
                 ms.append(e0.elapsed_time(e1))
         return statistics.median(ms), min(ms), max(ms)
 
+    if not a.no_verify:
+        import _key_ref as RK
+        RK.RAND = V.block_rand(RK.GlibcRand)                                      # the same stream, cheap at these positions
     sim = ntscsim.FieldSimulator(device=0)
     for size in a.sizes.split(","):
         w, h = (int(x) for x in size.split("x"))
@@ -169,11 +183,18 @@ def main():
                 op = (C.c_void_p * T)(*[out[t].data_ptr() for t in range(T)])
                 lib, hctx = ck._lib, ck.sim._h
 
+                behind = {}
+
                 def run_clip():
                     ri, pos = C.c_int32(0), C.c_uint64(0)
                     rc = lib.ntscsim_key_clip_device(hctx, rp, 4 * w, C.byref(ri), sp, ls, op, 4 * w, T, C.byref(pos), sh)
                     if rc != 0:
                         raise RuntimeError("ntscsim_key_clip_device: %d" % rc)
+                    behind["ri"], behind["pos"] = ri.value, pos.value
+
+                def zero_ring():
+                    with torch.cuda.stream(stream):
+                        ring.zero_()
 
                 descs = []
                 pos = 0
@@ -188,10 +209,24 @@ def main():
                         if rc != 0:
                             raise RuntimeError("ntscsim_key_frames_device: %d" % rc)
 
-                k = timed(run_clip)
-                kernels = ck.last_kernels()
-                f = timed(run_frames)
                 name = "%dx%d_d%d_%s" % (w, h, delay, "noise" if noise else "plain")
+                k = timed(run_clip, None if a.no_verify else zero_ring)
+                kernels = ck.last_kernels()
+                verified = {}
+                if not a.no_verify:                                               # what the last timed call left, before the frames form writes the ring
+                    layers = [RK.layer(color=L.color, threshhold=L.threshhold, fade=L.fade, xdivr=L.xdivr, invert=L.invert,
+                                       noisekey=L.noisekey) for L in ck.params.layers[:ck.n_layers]]   # as the switches were parsed
+                    if behind["ri"] != T % delay or behind["pos"] != pos:
+                        V.mismatch("%s: ring index %d, position %d behind the clip (want %d, %d)"
+                                   % (name, behind["ri"], behind["pos"], T % delay, pos))
+                    at = [0]
+
+                    def step(dst, t):
+                        at[0] = RK.key_frame(dst, [src[0, t].cpu().numpy(), src[1, t].cpu().numpy()], layers, at[0])
+
+                    verified = V.verify_clip(T, delay, (h, w, 4), step, lambda t: out[t].cpu().numpy(),
+                                             lambda i: ring[i].cpu().numpy(), name)
+                f = timed(run_frames)
                 case = {
                     "width": w, "height": h, "delay": delay, "noisekey": noise, "kernels": kernels,
                     "algorithmic_bytes": nbytes,
@@ -200,6 +235,7 @@ def main():
                     "frac_hbm": nbytes / (k[0] * 1e-3) / HBM_BYTES_PER_S,
                     "frames_form_ms": f[0], "frames_form_over_clip": f[0] / k[0],
                 }
+                case.update(verified)
                 if noise:
                     case["noise_overhead_share"] = 1.0 - plain_ms[delay] / k[0]
                 else:

@@ -14,6 +14,11 @@ clip -- a copy of n bytes reads n and writes n, so that is the stage's floor tra
 forms of its source loads (16-byte loads from dword-aligned addresses, the default; four dword loads,
 NTSCSIM_LED_SRC_DWORDS=1), alternating, between two runs of the copy.
 
+Before a case's numbers are printed, output frames 0, 1, the middle one and the last are compared with the checker
+(tools/bench_verify.py; --no-verify skips it) as the first timed runs of each form of the source loads left them; the
+output is cleared between the two.  `frames_verified` and `verify_s` of the case are the default form's, those of its
+`src_dwords` entry the dword form's.
+
     python tools/bench_led.py [--frames 600] [--reps 10] [--warmup 3] [--ref-cpu-fps X] [--out profiles/led.json]
 
 --ref-cpu-fps records the reference's own loop (ffmpeg_vhsled.cpp:866-931) as measured elsewhere: one thread, 720x486,
@@ -27,6 +32,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "composite-video-simulator_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_verify as V  # noqa: E402
 
 HBM_BYTES_PER_S = 8.0e12
 
@@ -73,6 +81,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--ref-cpu-fps", type=float, default=None)
     ap.add_argument("--out", default=None)
+    V.add_argument(ap)
     a = ap.parse_args()
 
     import torch
@@ -129,10 +138,26 @@ def main():
 
             # the copies first and last, the kernels between them: drift of the clock shows as a difference of the two
             c0 = timed(copy)
+            name = "%dx%d_%s" % (w, h, kind)
+
+            def verify(what):
+                """the output as the timed runs before this point left it; cleared behind the compare"""
+                if a.no_verify:
+                    return {}
+                import _led_ref as RL
+                stream.synchronize()
+                v = V.verify_frames(a.frames, lambda k: RL.align_frame(src[k].cpu().numpy())[0], lambda k: out[k].cpu().numpy(), what)
+                with torch.cuda.stream(stream):
+                    out.zero_()
+                stream.synchronize()
+                return v
+
             k0 = timed(runner(wide))
             kernels = wide.last_kernels()
+            verified = verify(name + ", 16-byte loads")
             n0 = timed(runner(narrow))
             kernels_narrow = narrow.last_kernels()
+            verified_narrow = verify(name + ", dword loads")
             k1 = timed(runner(wide))
             n1 = timed(runner(narrow))
             c1 = timed(copy)
@@ -154,8 +179,10 @@ def main():
                 "src_dwords": {"kernels": kernels_narrow, "led_ms": narrow_ms, "led_ms_runs": [n0[0], n1[0]],
                                "frames_per_s": a.frames / (narrow_ms * 1e-3), "over_default": narrow_ms / led_ms},
             }
-            result["cases"]["%dx%d_%s" % (w, h, kind)] = case
-            print("%dx%d_%s" % (w, h, kind), json.dumps(case), flush=True)
+            case.update(verified)
+            case["src_dwords"].update(verified_narrow)
+            result["cases"][name] = case
+            print(name, json.dumps(case), flush=True)
             del src, out, jobs, arr
             torch.cuda.empty_cache()
         wide.close()

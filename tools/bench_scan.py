@@ -13,6 +13,11 @@ directly (spilled) instead of through the on-chip window.  For the first configu
 the window switched off (ntscsim_scan_debug_set_window_rows(0): every add goes to the plane): the A/B the window has
 to justify itself with.
 
+Before a configuration's numbers are printed, output fields 0, 1, the middle one and the last are compared with the
+checker (tools/bench_verify.py; --no-verify skips it) as the timed calls left them: behind the whole-clip and per-effect
+runs, which all use the window, and -- first configuration -- once more behind the all-spill run, before the window is
+switched back on.  `frames_verified` and `verify_s` of the case and of its `all_spill` entry say what was compared.
+
     python tools/bench_scan.py [--frames 600] [--reps 3] [--warmup 1] [--ref-cpu-fps X] [--out profiles/scan.json]
 
 --ref-cpu-fps records the reference's own loop as measured elsewhere (ffmpeg_scanimate.cpp:817-974 compiled -O2, one
@@ -26,6 +31,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "composite-video-simulator_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_verify as V  # noqa: E402
 
 CONFIGS = [("600x800_to_720x480", [], 720, 480), ("inntsc_480x480_to_720x480", ["-inntsc"], 720, 480),
            ("inntsc_480x480_to_1920x1080", ["-inntsc", "-tvstd", "1080p60"], 1920, 1080)]
@@ -41,6 +49,7 @@ def main():
     ap.add_argument("--ref-cpu-fps", type=float, default=None)
     ap.add_argument("--ref-cpu-host", default="the build machine's CPU, not the GPU host: a different machine")
     ap.add_argument("--out", default=None)
+    V.add_argument(ap)
     a = ap.parse_args()
 
     import torch
@@ -95,16 +104,40 @@ def main():
             return {"fields": last - first, "ms": k[0], "ms_min_max": [k[1], k[2]], "fields_per_s": (last - first) / (k[0] * 1e-3),
                     "workgroups": wgs, "spilled_share": (spilled / wgs) if wgs else 0.0}
 
+        wanted = {}
+
+        def want(k, w=w, h=h, flags=flags):
+            if k not in wanted:
+                import _scan_ref as RS
+                f = RS.scan_field(src[k].cpu().numpy(), w, h, 1 if "-inntsc" in flags else 0, k)[1]
+                f[:RS.field_of(k)] = 0                                            # the clip form zeroes row 0 of a field == 1 output
+                wanted[k] = f
+            return wanted[k]
+
+        def verify(what):
+            """the output buffer as the timed calls before this point left it; cleared behind the compare, so that a
+            later compare cannot pass on these bytes"""
+            stream.synchronize()
+            v = V.verify_frames(T, want, lambda k: out[k].cpu().numpy(), what)
+            with torch.cuda.stream(stream):
+                out.zero_()
+            stream.synchronize()
+            return v
+
         case = {"flags": flags, "src": [sw, sh], "dst": [w, h], "overall": measure(0, T), "kernels": sc.last_kernels()[:2],
                 "effects": {}}
         for e, ename in enumerate(EFFECTS):
             first, last = min(T, 180 * e), min(T, 180 * (e + 1))
             if last > first:
                 case["effects"][ename] = measure(first, last)
+        if not a.no_verify:
+            case.update(verify(name))                                             # every run so far used the window
         if name == CONFIGS[0][0]:
             sc.debug_set_window_rows(0)
             case["all_spill"] = measure(0, T)
             case["all_spill"]["kernels"] = sc.last_kernels()[:2]
+            if not a.no_verify:
+                case["all_spill"].update(verify(name + ", all-spill form"))
             sc.debug_set_window_rows(-1)
             case["window_over_all_spill"] = case["all_spill"]["ms"] / case["overall"]["ms"]
         result["cases"][name] = case
