@@ -39,7 +39,8 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 // 128-byte lines, 16 pixels per iteration; as plain stores the halves wait in the L2 for each other, crowd out the
 // composite samples the VCR's luma path re-reads 5 + d positions behind the chroma path, and a fifth of them is
 // written back twice.  As streaming (nt) stores: WRITE_SIZE of k_decode_fast 1.28 -> 1.05 x the output, FETCH_SIZE
-// -11 %, and -17 % with the re-read itself marked nt (its line is dead afterwards).
+// -11 %, and -17 % with the re-read itself marked nt (its line is dead afterwards).  (Round 10: the grouped rows at tape
+// speed SP no longer re-read at all, see luma_take.)
 #ifdef NTSC_PLAIN_OUT_STORES        /* A/B: the round-3 stores */
 #define NTSC_OUT_STORE(p, v) (*(p) = (v))
 #else
@@ -303,9 +304,10 @@ struct DemodS {
     // -- for odd xi one position later than for xi - 1, i.e. out of the OTHER parity stream, the newest one being this
     // step's own sample -- and the half-cycle flip :1539-1542 leaves it positive iff (xe + 2 xi) & 2: the even-phase sign
     // (NEG) inverted on odd lanes (`mo`: -1 where xi is odd).
+    // Returns the box value yb of this position (the VCR's luma path takes the first separator's from the delay ring).
     template <bool PICK, bool NEG, bool LUMA, bool BK = false, bool MASK = false, bool ANY = false>
-    DEV void push(int ct, bool hi, int dm, int &Yo, int &Io, int &Qo, unsigned bmul = 0, unsigned bshift = 0,
-                  bool odd = false, int mo = 0)
+    DEV int push(int ct, bool hi, int dm, int &Yo, int &Io, int &Qo, unsigned bmul = 0, unsigned bshift = 0,
+                 bool odd = false, int mo = 0)
     {
         const int p = ct + c1;
         const int yb = sdiv4s(p + pB);
@@ -335,6 +337,7 @@ struct DemodS {
             Io = ieN; Qo = qeN;
             ieP = ieN; qeP = qeN;
         }
+        return yb;
     }
 };
 
@@ -364,6 +367,7 @@ struct Const {
     static constexpr bool fullout = FO;
     static constexpr int SH = FO ? 3 : 0;
     RT a_oi, a_oq;            // FO: alphas of the I / Q output filters
+    uint32_t *yr;             // this lane's column of the luma delay ring (rows that run it: rowend::luma_ring)
     uint32_t *xs;             // FO: this lane's column of 12 LDS slots -- luma, raw U, raw V of position p at slot (p & 3) (+4, +8)
     static constexpr bool wraps = WR;
     static constexpr bool back = BK;
@@ -446,8 +450,9 @@ DEV uint32_t yiq_to_bgra(int Yo, RT fU, RT fV)
     // the lower clamp is the conversion's own: v_cvt_u32 saturates (negative -> 0, too large -> 2^32 - 1), so
     // clamp((int)x >> 8, 0, 255) == min((unsigned)x >> 8, 255) for every x -- a full-rate v_min_u32 per channel in
     // place of a half-rate v_med3_i32 (C's conversion of a negative double to unsigned is undefined, hence the asm)
-    // The shift and the pack are one step (ntsc_pack.hpp): clamp to 0xFFFF, then two v_perm_b32 gather byte 1 of the
-    // three words -- 5 VALU per pixel where shift, clamp and shift / or took 8.
+    // The shift and the pack are one step (ntsc_pack.hpp): clamp to 0xFFFF -- R and G together in one saturating
+    // v_cvt_pk_u16_u32 -- then one v_perm_b32 gathers byte 1 of each channel: 3 VALU per pixel where shift, clamp and
+    // shift / or took 8.
     const uint32_t r = cvt_sat_u32((y + (RT(0.956) * fU)) + (RT(0.621) * fV));
     const uint32_t g = cvt_sat_u32((y + (RT(-0.272) * fU)) + (RT(-0.647) * fV));
     const uint32_t b = cvt_sat_u32((y + (RT(-1.106) * fU)) + (RT(1.703) * fV));
@@ -471,6 +476,7 @@ struct Steady {
     DemodS D1, D2;
     int lc1, lpA, lpB;          // VHS luma stream: c(t-1) and the pair sums (as DemodS)
     uint32_t *rb;               // this lane's column of the iteration's first ring slot
+    uint32_t *yw, *yn;          // luma delay ring: this lane's column of the iteration's first slot and of the next one's
     bool rb0;                   // that slot is slot 0 (its copy behind slot 31 is written too)
     int yd[4];                  // FO: luma of the last four positions, slot J rewritten at unrolled position J
     int ud[2];                  // FO: filtered I of the last two positions (already truncated: kept as integers)
@@ -478,14 +484,26 @@ struct Steady {
 
 // DPH = the first separator's position phase: x1 = t - 7 = DPH + J (mod 4) -- odd positions pick, x1 = 3 (mod 4)
 // negates (a compile-time property of the unrolled position since round 4: one instantiation per chroma delay mod 4).
-template <int DPH, int J, class RT, class CT>
+// LR: the luma path takes its box value from the delay ring (luma_take) where the first separator left it LOFF = 14
+// positions ago, instead of filtering `pl`, the re-read sample.
+template <int J>
+DEV int luma_take(Steady &T, int yb_now)
+{
+    // position t + J - 14 sits at slot (b + J + 2) & 15, b = the iteration's first slot (a multiple of 4): this
+    // iteration's quad for J < 2, the next one's for J >= 2; position t + J goes to slot b + J
+    const int yb = (int)(J < 2 ? T.yw[(J + 2) * 64] : T.yn[(J - 2) * 64]);
+    T.yw[J * 64] = (uint32_t)yb_now;
+    return yb;
+}
+
+template <int DPH, int J, class RT, class CT, bool LR = false>
 DEV int vcr_step(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C,
                  int pc, int pl, int &Yv, int &Uv, int &Vv)
 {
     constexpr bool pick1 = ((DPH + J) & 1) != 0;
     constexpr bool neg1 = ((DPH + J) & 3) == 3;
     int Yd, U, V;
-    T.D1.template push<pick1, neg1, false, CT::back, false, CT::anyxi>(pc, C.hi, -1, Yd, U, V, C.bmul, C.bshift, C.odd, C.mo);
+    const int yb1 = T.D1.template push<pick1, neg1, false, CT::back, false, CT::anyxi>(pc, C.hi, -1, Yd, U, V, C.bmul, C.bshift, C.odd, C.mo);
     // chroma noise :1719-1735
     U += S.nU; V += S.nV;
     S.nU = noise_next(S.nU, S.rng.template draw<2 * J>(T.rb, T.rb0), P.m_cnoise, P.cnoise_k);
@@ -499,9 +517,14 @@ DEV int vcr_step(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C,
     const int fU = (int)S.vcU.push(Ud, C.a_vc);
     const int fV = (int)S.vcV.push(Vd, C.a_vc);
     // luma at x2: box -> low-pass + emphasis :1793-1812 -> sharpen :1866-1883
-    const int lp = pl + T.lc1;
-    const int yb = sdiv4s(lp + T.lpB);
-    T.lc1 = pl; T.lpB = T.lpA; T.lpA = lp;
+    int yb;
+    if constexpr (LR) {
+        yb = luma_take<J>(T, yb1);
+    } else {
+        const int lp = pl + T.lc1;
+        yb = sdiv4s(lp + T.lpB);
+        T.lc1 = pl; T.lpB = T.lpA; T.lpA = lp;
+    }
     RT m2;
     RT s = S.vl.push((RT)yb, C.a_vl, m2);
     s += S.vpre.hp(s, m2, C.a_vl) * RT(1.6);
@@ -531,7 +554,7 @@ DEV int vcr_step(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C,
 //   re-modulation                 x2 = x3 + 7     = 4n + J (mod 4) -> U for even J, sign by J & 2
 //   first demodulator             x1 = t - 7      = DPH + J (mod 4)
 // Non-VHS form: x3 = x1 = t - 7 = 4n + J + 1 (SKT = 8), one demodulator.
-template <bool VHS, int DPH, int J, class RT, class CT>
+template <bool VHS, int DPH, int J, class RT, class CT, bool LR = false>
 DEV uint32_t step(const DevParams &P, State<VHS, RT> &S, Steady &T, const CT &C, int pc, int pl)
 {
     int Y, U, V;
@@ -542,7 +565,7 @@ DEV uint32_t step(const DevParams &P, State<VHS, RT> &S, Steady &T, const CT &C,
         T.D1.template push<pick3, neg3, true, CT::back, true, CT::anyxi>(pc, C.hi, C.dm, Y, U, V, C.bmul, C.bshift, C.odd, C.mo);
     } else {
         int Yv, Uv, Vv;
-        const int c2 = vcr_step<DPH, J, RT, CT>(P, S, T, C, pc, pl, Yv, Uv, Vv);
+        const int c2 = vcr_step<DPH, J, RT, CT, LR>(P, S, T, C, pc, pl, Yv, Uv, Vv);
         if constexpr (CT::svideo) {
             Y = Yv; U = Uv & C.dm; V = Vv & C.dm;  // -vhs-svideo: the components go on as they are :1885; dropout :1891
         } else {
@@ -701,7 +724,8 @@ DEV bool edge_step(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t 
 // the row.  T = the separators and the luma box in their steady form, pc / pl = the composite samples of positions
 // t .. t+3 (requested by the caller), sbase = ring slot of the first draw (a multiple of 8).  On return pc / pl hold what
 // was requested for the four positions behind the last iteration (a position at or beyond W: not to be used).
-template <bool VHS, int DPH, class RT, class CT>
+// LR: the luma delay ring replaces the pl stream (grouped rows of rowend::luma_ring; pl is neither used nor requested).
+template <bool VHS, int DPH, class RT, class CT, bool LR = false>
 DEV int steady_run(const DevParams &P, State<VHS, RT> &S, Steady &T, const CT &C, uint32_t *ring,
                    uint32_t *ostage, const unsigned long long *orow, uint32_t *drow, bool is_out, int t, int t_end,
                    int (&pc)[4], int (&pl)[4], int &sbase)
@@ -763,11 +787,15 @@ DEV int steady_run(const DevParams &P, State<VHS, RT> &S, Steady &T, const CT &C
         T.rb = ring + sbase * 64 + lane;
         T.rb0 = sbase == 0;
         sbase = (sbase + 8) & 31;
+        if constexpr (LR) {
+            T.yw = C.yr + ((t - SKT) & 15) * 64;
+            T.yn = C.yr + ((t - SKT + 4) & 15) * 64;
+        }
 #define NTSC_FAST_STEP(J)                                                                         \
-        o[J] = step<VHS, DPH, J, RT, CT>(P, S, T, C, pc[J % PD], pl[J % PD]);                     \
+        o[J] = step<VHS, DPH, J, RT, CT, LR>(P, S, T, C, pc[J % PD], pl[J % PD]);                 \
         if (!PFTOP) {                                                                             \
             pc[J % PD] = cs_load(C, t + PD + J);                                                  \
-            if (VHS) pl[J % PD] = cs_load<NTSC_COMP_LOAD2_AUX>(C, t + PD + J - LOFF);                                  \
+            if (VHS && !LR) pl[J % PD] = cs_load<NTSC_COMP_LOAD2_AUX>(C, t + PD + J - LOFF);      \
         }                                                                                         \
         NTSC_STEP_SCHED_BARRIER();
         NTSC_FAST_STEP(0)
@@ -829,11 +857,11 @@ DEV int steady(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t *rin
     int pc[PD], pl[PD];
 #pragma unroll
     for (int j = 0; j < PD; j++) { pc[j] = cs_load(C, t + j); pl[j] = VHS ? cs_load<NTSC_COMP_LOAD2_AUX>(C, t + j - LOFF) : 0; }
-    // (The VCR's luma path reads every composite sample a second time, LOFF = 5 + d positions behind the chroma path.
-    //  Tried in round 4: an LDS ring of 20 + 3 slots that keeps each sample until the luma path wants it -- the second
-    //  pass over the plane disappears from the L2's memory side, but the ring takes the workgroup from 14 to 20 KB of
-    //  LDS, eight decoder workgroups then fill a CU's 160 KB, and the encoder waves of the neighbouring steps no longer
-    //  fit beside them: kernel 0.766 -> 0.776 ms, four steps in flight 769k -> 755k fields/s.  Not shipped.)
+    // (On this path -- rows too narrow for the groups, and the forms that do not run them -- the VCR's luma path reads
+    //  every composite sample a second time, LOFF = 5 + d positions behind the chroma path, and filters it again.
+    //  Round 4 tried an LDS ring of 20 + 3 slots holding the RAW samples for every tape speed: no VALU less, 14 -> 20 KB
+    //  of LDS per workgroup, kernel 0.766 -> 0.776 ms, not shipped.  Round 10 keeps the FILTERED value instead, 16 slots,
+    //  SP only, grouped rows only: rowend::luma_ring, luma_take.)
     t = steady_run<VHS, DPH, RT, CT>(P, S, T, C, ring, ostage, orow, drow, is_out, t, t_end, pc, pl, sbase);
     // back to the guarded steps' layout (t has advanced by a multiple of 4: the same position phases as at the entry)
     T.D1.to(S.D1, VHS ? (DPH & 1) != 0 : pick3_next);
@@ -863,7 +891,7 @@ DEV int steady(const DevParams &P, State<VHS, RT> &S, const CT &C, uint32_t *rin
 // the x >= xe zeroing :1553 of the separators, the raw chroma tail :1830, the TV filter's last sample :1419).
 // Forms: the composite -vhs forms with an even scanline phase and the TV output filter (plain, WR, BK).  The S-Video, XA,
 // FO and non-VHS forms keep the one-position form (decode_fast_body says so where it chooses).
-template <int DPH, int J, bool END, class RT, class CT>
+template <int DPH, int J, bool END, class RT, class CT, bool LR = false>
 DEV uint32_t group_step(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C, const rowend::Pos &q,
                         int t, int pc, int pl)
 {
@@ -872,6 +900,7 @@ DEV uint32_t group_step(const DevParams &P, State<true, RT> &S, Steady &T, const
     constexpr bool pick3 = ((J + 1) & 1) != 0, neg3 = ((J + 1) & 3) == 3;
     int Yd, U = 0, V = 0;
     int fU = 0, fV = 0;
+    int yb1 = 0;
     // A delay line renames only where its push is unconditional: a branch around a push turns every shift into a v_mov
     // again (the skipped path keeps the old assignment).  So the separators and the luma box push at EVERY position of
     // the fill and -- the first separator apart, whose state is dead for the drain's last 8 + d positions -- of the
@@ -883,10 +912,10 @@ DEV uint32_t group_step(const DevParams &P, State<true, RT> &S, Steady &T, const
             // m guard: the pick at odd x1 stands iff x1 + 2 + xi < W (xi = 0 / 2 per lane); everything from xe on is zeroed
             const int x1 = t - 7;
             const int mg = pick1 ? ((x1 + 2 - W + (C.mL & 2)) >> 31) : -1;
-            T.D1.template push<pick1, neg1, false, CT::back, true, false>(pc, C.hi, mg, Yd, U, V, C.bmul, C.bshift);
+            yb1 = T.D1.template push<pick1, neg1, false, CT::back, true, false>(pc, C.hi, mg, Yd, U, V, C.bmul, C.bshift);
             if (x1 >= C.xe) { U = 0; V = 0; }
         } else {
-            T.D1.template push<pick1, neg1, false, CT::back, false, false>(pc, C.hi, -1, Yd, U, V, C.bmul, C.bshift);
+            yb1 = T.D1.template push<pick1, neg1, false, CT::back, false, false>(pc, C.hi, -1, Yd, U, V, C.bmul, C.bshift);
         }
     }
     if (q.in1) {
@@ -905,7 +934,13 @@ DEV uint32_t group_step(const DevParams &P, State<true, RT> &S, Steady &T, const
         }
     }
     int yb;
-    {
+    if constexpr (LR) {
+        // The ring holds what the first separator pushed: zeros before the row (the ring starts zeroed and the fill pushes
+        // zeros), the box's tail behind it (the separator goes on pushing the zeros its input reads until x1 = W - 1,
+        // t = W + 6; the luma path's last live read, at x2 = W - 1, is position W + 1).  Behind that the separator stops,
+        // the slot written is stale and so is what is read: q.in2 is false there and yb is dead.
+        yb = luma_take<J>(T, yb1);
+    } else {
         const int lp = pl + T.lc1;
         yb = sdiv4s(lp + T.lpB);
         T.lc1 = pl; T.lpB = T.lpA; T.lpA = lp;
@@ -959,7 +994,7 @@ DEV uint32_t group_step(const DevParams &P, State<true, RT> &S, Steady &T, const
 
 // the groups [t0, t_stop) (t0 = SKT mod 4).  pc / pl: the samples of the first group on entry (positions outside the row
 // hold 0), of the group at t_stop on return.
-template <int DPH, bool END, class RT, class CT>
+template <int DPH, bool END, class RT, class CT, bool LR = false>
 DEV void group_run(const DevParams &P, State<true, RT> &S, Steady &T, const CT &C, const rowend::Plan &RP,
                    uint32_t *ring, uint32_t *ostage, uint32_t *drow, bool is_out, int t0, int t_stop,
                    int (&pc)[4], int (&pl)[4], int &sbase)
@@ -969,18 +1004,22 @@ DEV void group_run(const DevParams &P, State<true, RT> &S, Steady &T, const CT &
         T.rb = ring + sbase * 64 + lane;
         T.rb0 = sbase == 0;
         sbase = (sbase + 8) & 31;
+        if constexpr (LR) {
+            T.yw = C.yr + ((t0 - RP.SKT) & 15) * 64;
+            T.yn = C.yr + ((t0 - RP.SKT + 4) & 15) * 64;
+        }
         uint32_t o[4] = {0u, 0u, 0u, 0u};
         bool burst = false, rest = false;
 #define NTSC_GROUP_STEP(J)                                                                        \
         {                                                                                         \
             const int tj = t0 + J;          /* (a partial group's positions outside the row: nothing is live) */ \
             const rowend::Pos q = rowend::position(RP, tj);                                       \
-            o[J] = group_step<DPH, J, END, RT, CT>(P, S, T, C, q, tj, pc[J], pl[J]);              \
+            o[J] = group_step<DPH, J, END, RT, CT, LR>(P, S, T, C, q, tj, pc[J], pl[J]);          \
             burst = burst || q.burst; rest = rest || q.rest;                                      \
             const int tn = tj + 4;          /* the next group's samples, where the schedule has them inside the row */ \
             const rowend::Pos qn = rowend::position(RP, tn);                                      \
             pc[J] = qn.load_c ? cs_load(C, tn) : 0;                                               \
-            pl[J] = qn.load_l ? cs_load<NTSC_COMP_LOAD2_AUX>(C, tn - RP.LOFF) : 0;                \
+            pl[J] = (!LR && qn.load_l) ? cs_load<NTSC_COMP_LOAD2_AUX>(C, tn - RP.LOFF) : 0;       \
             NTSC_STEP_SCHED_BARRIER();                                                            \
         }
         NTSC_GROUP_STEP(0)
@@ -1015,7 +1054,7 @@ DEV void group_run(const DevParams &P, State<true, RT> &S, Steady &T, const CT &
 
 
 // one row, fill to drain, in groups (rowend::grouped rows only).  DPH = d mod 4, as for steady().
-template <int DPH, class RT, class CT>
+template <int DPH, class RT, class CT, bool LR = false>
 DEV void grouped_row(const DevParams &P, State<true, RT> &S, const CT &C, const rowend::Plan &RP, uint32_t *ring,
                      uint32_t *ostage, const unsigned long long *orow, uint32_t *drow, bool is_out)
 {
@@ -1029,12 +1068,16 @@ DEV void grouped_row(const DevParams &P, State<true, RT> &S, const CT &C, const 
         pc[j] = rowend::position(RP, RP.g0 + j).load_c ? cs_load(C, RP.g0 + j) : 0;
         pl[j] = 0;
     }
-    group_run<DPH, false, RT, CT>(P, S, T, C, RP, ring, ostage, drow, is_out, RP.g0, RP.st0, pc, pl, sbase);
-    const int t = steady_run<true, DPH, RT, CT>(P, S, T, C, ring, ostage, orow, drow, is_out, RP.st0, RP.t_end, pc, pl, sbase);
+    if constexpr (LR) {
+#pragma unroll
+        for (int q = 0; q < rowend::LUMA_RING_SLOTS; q++) C.yr[q * 64] = 0u;
+    }
+    group_run<DPH, false, RT, CT, LR>(P, S, T, C, RP, ring, ostage, drow, is_out, RP.g0, RP.st0, pc, pl, sbase);
+    const int t = steady_run<true, DPH, RT, CT, LR>(P, S, T, C, ring, ostage, orow, drow, is_out, RP.st0, RP.t_end, pc, pl, sbase);
     // (the steady loop's last requests may lie behind the row: those read 0)
 #pragma unroll
     for (int j = 0; j < 4; j++) pc[j] = rowend::position(RP, t + j).load_c ? pc[j] : 0;
-    group_run<DPH, true, RT, CT>(P, S, T, C, RP, ring, ostage, drow, is_out, t, RP.glast + 4, pc, pl, sbase);
+    group_run<DPH, true, RT, CT, LR>(P, S, T, C, RP, ring, ostage, drow, is_out, t, RP.glast + 4, pc, pl, sbase);
 }
 
 } // namespace fastdec
@@ -1072,6 +1115,9 @@ DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *
     __shared__ uint32_t lring[FO ? 12 * 64 : 64]; // FO: luma and raw chroma of the last four positions (Const::xs)
     __shared__ __attribute__((aligned(16))) uint32_t ostage[64 * 20];
     __shared__ unsigned long long orow[64];       // every lane's output row (0 = none), for the cooperative stores
+    // the luma delay ring, [16][64] words: dynamic, so that only a launch whose rows run it pays for it (the launcher
+    // passes rowend::LUMA_RING_BYTES exactly where rowend::luma_ring holds, the condition tested below)
+    extern __shared__ uint32_t yring[];
 
     const int lane = threadIdx.x;
     const int gidx = blockIdx.x * 63 + lane - 1;          // lane 0 = halo (row above)
@@ -1152,6 +1198,7 @@ DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *
     else { S.oU.reset(0, C.a_tv); S.oV.reset(0, C.a_tv); }
     S.Yprev = S.Uraw = S.Vraw = 0;
     C.xs = lring + lane;
+    C.yr = yring + lane;
     if (CT::fullout)
         for (int q = 0; q < 12; q++) C.xs[q * 64] = 0;
     S.Uf2[0] = S.Uf2[1] = 0;
@@ -1171,13 +1218,20 @@ DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *
 #else
     constexpr bool GROUPS = VHS && !SV && !XA && !FO;
 #endif
+#ifdef NTSC_LUMA_REREAD            /* A/B: the luma path re-reads and re-filters its samples everywhere, as in round 9 */
+    constexpr bool LRING = false;
+#else
+    constexpr bool LRING = true;
+#endif
     if constexpr (GROUPS) {
         // (one instantiation per position phase of the first separator, d mod 4, as for steady(); the tape speeds give
         //  d = 9, 12, 14 -- a delay of 3 mod 4 has no grouped code and takes the one-position form)
-        if (rowend::grouped(RP) && (C.d & 3) != 3) {
+        // The delay class of SP (d = 9, LOFF = 14) runs the luma delay ring; its grouped code exists in that form only, so
+        // another delay of 1 mod 4 would take the one-position form.
+        if (rowend::grouped(RP) && (C.d & 3) != 3 && (!LRING || (C.d & 3) != 1 || rowend::luma_ring(RP))) {
             switch (C.d & 3) {
                 case 0: grouped_row<0, RT, CT>(P, S, C, RP, ring, ostage, orow, drow, is_out); break;
-                case 1: grouped_row<1, RT, CT>(P, S, C, RP, ring, ostage, orow, drow, is_out); break;
+                case 1: grouped_row<1, RT, CT, LRING>(P, S, C, RP, ring, ostage, orow, drow, is_out); break;
                 default: grouped_row<2, RT, CT>(P, S, C, RP, ring, ostage, orow, drow, is_out); break;
             }
             return;

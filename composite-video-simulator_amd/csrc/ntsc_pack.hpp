@@ -1,7 +1,7 @@
 // ntsc_pack.hpp -- the last step of YIQ_to_RGB (ffmpeg_ntsc.cpp:1385-1396): three channel values, each 256 x the channel
 // and already through the saturating unsigned conversion (v_cvt_u32_f64 / _f32: negative -> 0, too large -> 2^32 - 1),
-// become one BGRA pixel.  Plain integer code, so the same text runs on the host: tests/pack_check.cpp sweeps it with g++
-// (there v_perm_b32 is the model below).
+// become one BGRA pixel.  Plain integer code, so the same text runs on the host: tests/pack_check.cpp and
+// tests/pack_sat_check.cpp sweep it with g++ (there v_perm_b32 and v_cvt_pk_u16_u32 are the models below).
 #pragma once
 #include <stdint.h>
 
@@ -49,12 +49,38 @@ NTSC_PACK_FN uint32_t pack_bgra_perm(uint32_t r, uint32_t g, uint32_t b)
     return perm_b32(r, gb, 0x0c050100u);                      // byte 2 = r[1]
 }
 
+// v_cvt_pk_u16_u32: each 32-bit unsigned source saturates to 16 bits, a in the low half, b in the high half
+NTSC_PACK_FN uint32_t cvt_pk_u16(uint32_t a, uint32_t b)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    union { u16x2 v; uint32_t u; } c;
+    c.v = __builtin_amdgcn_cvt_pk_u16(a, b);
+    return c.u;
+#else
+    a = a < 0xFFFFu ? a : 0xFFFFu; b = b < 0xFFFFu ? b : 0xFFFFu;
+    return a | (b << 16);
+#endif
+}
+
+// The round-10 form: the saturating pack is the clamp of two channels at once, so R and G go through one
+// v_cvt_pk_u16_u32 (bytes r[0] r[1] g[0] g[1]), B through one v_min_u32, and a single v_perm_b32 gathers
+// b[1], g[1] (byte 3 of the pair), r[1] (byte 1 of the pair): 3 VALU per pixel.  Alpha stays 0.
+NTSC_PACK_FN uint32_t pack_bgra_sat(uint32_t r, uint32_t g, uint32_t b)
+{
+    const uint32_t rg = cvt_pk_u16(r, g);
+    b = b < 0xFFFFu ? b : 0xFFFFu;
+    return perm_b32(rg, b, 0x0c050701u);
+}
+
 NTSC_PACK_FN uint32_t pack_bgra(uint32_t r, uint32_t g, uint32_t b)
 {
-#ifdef NTSC_PACK_SHIFT      /* A/B: the round-4 pack */
+#if defined(NTSC_PACK_SHIFT)    /* A/B: the round-4 pack */
     return pack_bgra_shift(r, g, b);
-#else
+#elif defined(NTSC_PACK_PERM)   /* A/B: the round-7 pack */
     return pack_bgra_perm(r, g, b);
+#else
+    return pack_bgra_sat(r, g, b);
 #endif
 }
 

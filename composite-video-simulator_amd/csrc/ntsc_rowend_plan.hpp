@@ -95,6 +95,23 @@ NTSC_PLAN_FN Pos position(const Plan &p, int t)
     return q;
 }
 
+// The luma delay ring (round 10): the first separator's box value yb(t) is the very value the VCR's luma path wants LOFF
+// positions later, so a grouped row keeps it in LDS -- 16 slots per lane, position t at slot (t - SKT) & 15, every
+// group's first slot a multiple of 4 -- instead of loading and filtering the samples a second time.  The static slot
+// offsets are written for LOFF = 14 (SP); LP and EP (LOFF = 17, 19 > 16 slots) and the one-position rows keep the
+// re-read, and a launch without ring rows allocates no LDS for it (the launcher asks this same function).
+constexpr int LUMA_RING_SLOTS = 16;
+constexpr int LUMA_RING_BYTES = LUMA_RING_SLOTS * 64 * 4;
+NTSC_PLAN_FN bool luma_ring(const Plan &p)
+{
+#ifdef NTSC_LUMA_REREAD           /* A/B: the round-9 form everywhere */
+    (void)p;
+    return false;
+#else
+    return p.vhs && !p.sv && !p.fo && p.LOFF == 14 && grouped(p);
+#endif
+}
+
 // rand() ring (LaneRand32): slot of the first draw of the group that starts at t0, given the slot of the row's first
 // draw (at t = 7, two draws per position).  The window is placed so that the steady loop's first draw is on a multiple
 // of 8 (LaneRand32::init), and every group starts a multiple of 4 positions from it: a multiple of 8 as well.

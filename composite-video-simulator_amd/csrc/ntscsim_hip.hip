@@ -147,6 +147,7 @@ struct ntscsim_ctx {
 
     // kernel forms enqueued by the last launch (ntscsim_debug_last_kernels)
     std::string kernels;
+    unsigned dec_lds = 0;            // dynamic LDS of the last decoder launch (ntscsim_debug_last_decoder_lds)
     // last batch (debug tap)
     int last_n = 0, last_W = 0, last_H = 0, last_Rpad = 0, last_Lslot = 0;
 
@@ -588,6 +589,11 @@ extern "C" int ntscsim_debug_last_kernels(const ntscsim_ctx *c, char *out, size_
     std::memcpy(out, kernels.data(), n);
     out[n] = 0;
     return (int)kernels.size();
+}
+
+extern "C" int ntscsim_debug_last_decoder_lds(const ntscsim_ctx *c)
+{
+    return c ? (int)c->dec_lds : NTSCSIM_E_ARG;
 }
 
 extern "C" void ntscsim_debug_set_warmup(ntscsim_ctx *c, int luma_draws, int chroma_draws)
@@ -1043,19 +1049,23 @@ static int launch_records(ntscsim_ctx *c, const DevParams &D, const FieldDev *fi
     // the same family with scanline phases of either parity: its own form (any head-switch displacement)
     const bool dec_fast_xi = dec_base && back50 && !c->no_fast_decode && D.dst_al16 && !even_phase && D.vhs && !D.svideo &&
                              D.cnoise_k && D.pnoise_k && fast_plane_ok((size_t)D.Rpad, W, D.hs ? 2 : 0);
+    // the luma delay ring of the composite -vhs forms (SP, rows wide enough for the groups): dynamic LDS, asked for only
+    // where the kernel will run it -- rowend::luma_ring is the kernel's own condition
+    c->dec_lds = 0;
+    const unsigned lring_lds = rowend::luma_ring(rowend::make_plan(W, D.cdelay, D.vhs != 0, false, false)) ? (unsigned)rowend::LUMA_RING_BYTES : 0u;
 #define NTSC_LAUNCH_FAST(VHS, RT)                                                                \
-    do { note_kernel(c, "k_decode_fast<" #VHS "," #RT ">");                                      \
-    hipLaunchKernelGGL((k_decode_fast<VHS, RT>), dgrid, dim3(64), 0, st, D, G, fields_dev, dec_in, \
+    do { note_kernel(c, "k_decode_fast<" #VHS "," #RT ">"); c->dec_lds = (VHS) ? lring_lds : 0u;  \
+    hipLaunchKernelGGL((k_decode_fast<VHS, RT>), dgrid, dim3(64), (VHS) ? lring_lds : 0u, st, D, G, fields_dev, dec_in, \
                        c->rs_chroma.p, c->n0_u.p, c->n0_v.p, c->hs_shift.p, c->pn_noise.p,       \
                        c->dropout.p, c->tails.p); } while (0)
 #define NTSC_LAUNCH_FAST_BK(VHS, RT)                                                             \
-    do { note_kernel(c, "k_decode_fast_bk<" #VHS "," #RT ">");                                   \
-    hipLaunchKernelGGL((k_decode_fast_bk<VHS, RT>), dgrid, dim3(64), 0, st, D, G, fields_dev, dec_in, \
+    do { note_kernel(c, "k_decode_fast_bk<" #VHS "," #RT ">"); c->dec_lds = (VHS) ? lring_lds : 0u; \
+    hipLaunchKernelGGL((k_decode_fast_bk<VHS, RT>), dgrid, dim3(64), (VHS) ? lring_lds : 0u, st, D, G, fields_dev, dec_in, \
                        c->rs_chroma.p, c->n0_u.p, c->n0_v.p, c->hs_shift.p, c->pn_noise.p,       \
                        c->dropout.p, c->tails.p); } while (0)
 #define NTSC_LAUNCH_FAST_WR(RT)                                                                  \
-    do { note_kernel(c, "k_decode_fast<true," #RT ",true>");                                     \
-    hipLaunchKernelGGL((k_decode_fast<true, RT, true>), dgrid, dim3(64), 0, st, D, G, fields_dev, dec_in, \
+    do { note_kernel(c, "k_decode_fast<true," #RT ",true>"); c->dec_lds = lring_lds;            \
+    hipLaunchKernelGGL((k_decode_fast<true, RT, true>), dgrid, dim3(64), lring_lds, st, D, G, fields_dev, dec_in, \
                        c->rs_chroma.p, c->n0_u.p, c->n0_v.p, c->hs_shift.p, c->pn_noise.p,       \
                        c->dropout.p, c->tails.p); } while (0)
     if (pipe_form || pipe_tv || pipe_tv_catv) {

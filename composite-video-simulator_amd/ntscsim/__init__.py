@@ -380,6 +380,13 @@ class FieldSimulator:
             raise RuntimeError("ntscsim_debug_last_kernels: %d" % n)
         return [k for k in buf.value.decode().split(";") if k]
 
+    def last_decoder_lds(self):
+        """Bytes of dynamic LDS of the last decoder launch: the luma delay ring (4096), or 0 where the luma path re-reads."""
+        n = self._lib.ntscsim_debug_last_decoder_lds(self._h)
+        if n < 0:
+            raise RuntimeError("ntscsim_debug_last_decoder_lds: %d" % n)
+        return n
+
     def debug_set_warmup(self, luma_draws, chroma_draws):
         self._lib.ntscsim_debug_set_warmup(self._h, int(luma_draws), int(chroma_draws))
 

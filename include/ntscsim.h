@@ -714,6 +714,12 @@ void ntscsim_debug_no_fast_decode(ntscsim_ctx *ctx, int on);
  * SYNCHRONISES it (hipDeviceSynchronize) before it copies the counter back; otherwise it touches no device. */
 int ntscsim_debug_last_kernels(const ntscsim_ctx *ctx, char *out, size_t cap);
 
+/* Test hook: bytes of dynamic LDS the last ntscsim_fields_device() / batch run on this ctx asked for with its decoder
+ * launch -- the luma delay ring of the composite -vhs forms at tape speed SP (csrc/ntsc_rowend_plan.hpp: luma_ring),
+ * 4096, or 0 where the decoder re-reads its luma samples (LP, EP, rows too narrow for the grouped row ends, every other
+ * form).  NTSCSIM_E_ARG without a ctx.  Touches no device. */
+int ntscsim_debug_last_decoder_lds(const ntscsim_ctx *ctx);
+
 /* Test hook (pure host arithmetic, no ctx): 1 when a batch of n_fields fields of width x height may take
  * the hand-tuned kernels as far as the size of its composite plane is concerned -- they address the
  * plane with 32-bit buffer offsets, and the displaced index of the head switch must not wrap around
