@@ -1,5 +1,7 @@
 // led_params.cpp -- host half of the vhsled stage (include/ntscsim.h: ntscsim_led_*): the tool's switches.  Plain
-// C++: no HIP, usable without a GPU.  Line numbers refer to ffmpeg_vhsled.cpp of the reference.
+// C++: no HIP, usable without a GPU.  Line numbers refer to ffmpeg_vhsled.cpp of the reference.  filmac.cpp has the
+// same globals and the same parse_argv(), text for text, at the same lines, so ntscsim_filmac_params_init() and
+// _parse_argv() at the end of this file are these functions under the other stage's name.
 #include <cctype>
 #include <cmath>
 #include <cstdlib>
@@ -87,4 +89,11 @@ extern "C" int ntscsim_led_parse_argv(ntscsim_led_params *p, int argc, const cha
     if (require_io && (!p->output_path || !*p->output_path)) return NTSCSIM_E_FLAG;   // :574-581
     if (require_io && (!p->input_path || !*p->input_path)) return NTSCSIM_E_FLAG;
     return NTSCSIM_OK;
+}
+
+extern "C" void ntscsim_filmac_params_init(ntscsim_filmac_params *p) { ntscsim_led_params_init(p); }
+
+extern "C" int ntscsim_filmac_parse_argv(ntscsim_filmac_params *p, int argc, const char *const *argv, int require_io)
+{
+    return ntscsim_led_parse_argv(p, argc, argv, require_io);
 }

@@ -223,10 +223,11 @@ struct ntscsim_ctx {
     ntscsim::AvgState *avg = nullptr;       // ntscsim_avg_bind(): state of the average_delay stage (csrc/ntsc_avg.hip)
     ntscsim::ScanState *scan = nullptr;     // ntscsim_scan_bind(): state of the scanimate stage (csrc/ntsc_scan.hip)
     ntscsim::LedState *led = nullptr;       // ntscsim_led_bind(): state of the vhsled stage (csrc/ntsc_led.hip)
+    ntscsim::FilmacState *filmac = nullptr; // ntscsim_filmac_bind(): state of the filmac stage (csrc/ntsc_filmac.hip)
 };
 ntscsim::CtxStageView ntscsim::ctx_stage_view(ntscsim_ctx *c)
 {
-    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan, &c->led};
+    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan, &c->led, &c->filmac};
 }
 static void submit_engine_destroy(ntscsim_ctx *c);
 static int sub_wait_ticket(ntscsim_ctx *c, uint64_t ticket);
@@ -471,6 +472,7 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     if (c->avg) { ntscsim::avg_state_destroy(c->avg); c->avg = nullptr; }
     if (c->scan) { ntscsim::scan_state_destroy(c->scan); c->scan = nullptr; }
     if (c->led) { ntscsim::led_state_destroy(c->led); c->led = nullptr; }
+    if (c->filmac) { ntscsim::filmac_state_destroy(c->filmac); c->filmac = nullptr; }
     for (Geometry *e : c->geoms) {
         e->lskip.release(); e->pskip.release(); e->jrow.release();
         delete e;

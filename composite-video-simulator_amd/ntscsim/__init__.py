@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "AutoContrast", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -841,6 +841,103 @@ class EdgeAligner:
         e, x = np.empty(h, np.int32), np.empty(h, np.int32)
         self._call("debug_edges", int(frame), C.c_void_p(e.ctypes.data), C.c_void_p(x.ctypes.data))
         return e, x
+
+    def last_kernels(self):
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
+
+
+class AutoContrast:
+    """The filmac stage (ntscsim_filmac_*): stretches the levels of every frame to full range, following the darkest
+    block mean and the brightest pixel from frame to frame, as filmac does.  `flags` are the tool's switches; -gamma
+    is the one that changes a byte (levels are then measured and stretched in linear light).  width / height: the
+    frame size, 16 .. 16384 each.  sim: share the context of a FieldSimulator; otherwise a context of its own is
+    created.  The level state lives on the device and carries from frame to frame and from call to call; calls must
+    be ordered by the caller (one stream).  Frames are uint8 [H, W, 4] with contiguous pixels and any row stride."""
+
+    def __init__(self, flags=(), width=None, height=None, sim=None, device=0, params=None):
+        self.params = params if params is not None else _capi.make_filmac_params(flags, width=width, height=height)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        try:
+            self._call("bind", C.byref(self.params))
+        except Exception:
+            self.close()
+            raise
+
+    def _call(self, what, *args):
+        name = "ntscsim_filmac_%s" % what
+        self.sim._chk(getattr(self._lib, name)(self.sim._h, *args), name)
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    @staticmethod
+    def _descs(jobs, ptr, linesize):
+        arr = (_capi.FilmacDesc * max(1, len(jobs)))()
+        for d, (dst, src) in zip(arr, jobs):
+            assert len(dst.shape) == 3 and dst.shape[2] == 4 and tuple(src.shape) == tuple(dst.shape)
+            d.src, d.src_linesize, d.dst, d.dst_linesize = ptr(src), linesize(src), ptr(dst), linesize(dst)
+        return arr
+
+    def _check_size(self, jobs):
+        for dst, _ in jobs:
+            if (dst.shape[0], dst.shape[1]) != (self.params.height, self.params.width):
+                raise NtscsimError(_capi.E_SIZE, "a frame of %dx%d on a stage bound to %dx%d"
+                                   % (dst.shape[1], dst.shape[0], self.params.width, self.params.height))
+
+    def stretch_frames(self, jobs, stream=None):
+        """ntscsim_filmac_frames_device: jobs = [(dst, src), ...] of torch uint8 CUDA tensors [H, W, 4], in clip order;
+        dst may be src.  Five launches for all jobs that do not depend on each other.  Enqueues; does not synchronise."""
+        self._check_size(jobs)
+        arr = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("frames_device", arr, len(jobs), C.c_void_p(stream))
+
+    def stretch_frames_host(self, jobs):
+        """ntscsim_filmac_frames_host: the same on numpy uint8 arrays.  Synchronous."""
+        self._check_size(jobs)
+        arr = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self._call("frames_host", arr, len(jobs))
+
+    def reset(self):
+        """The tool's start: the next frame sets the levels.  Synchronises."""
+        self._call("reset")
+
+    @property
+    def state(self):
+        """(init, final_minv, final_maxv).  Reading and writing synchronise."""
+        s = _capi.FilmacState()
+        self._call("get_state", C.byref(s))
+        return bool(s.init), int(s.final_minv), int(s.final_maxv)
+
+    @state.setter
+    def state(self, value):
+        s = _capi.FilmacState()
+        s.init, s.final_minv, s.final_maxv = int(bool(value[0])), int(value[1]), int(value[2])
+        self._call("set_state", C.byref(s))
+
+    def levels(self, frame=0):
+        """(minv, maxv, final_minv, final_maxv) of frame `frame` of the last stretch_frames call.  Synchronises."""
+        out = (C.c_int64 * 4)()
+        self._call("debug_levels", int(frame), out)
+        return tuple(int(v) for v in out)
+
+    def debug_time_kernels(self, on=True):
+        self._call("debug_time_kernels", 1 if on else 0)
+
+    def kernel_ms(self):
+        """(k_filmac_stats, k_filmac_frame_levels, k_filmac_levels, k_filmac_tables, k_filmac_apply) milliseconds of the
+        last stretch_frames call; debug_time_kernels() first.  Synchronises."""
+        out = (C.c_float * 5)()
+        self._call("debug_kernel_ms", out)
+        return tuple(float(v) for v in out)
 
     def last_kernels(self):
         return self.sim.last_kernels()

@@ -60,6 +60,9 @@ EXPORTS = (
     "ntscsim_scan_debug_spill",
     "ntscsim_led_params_init", "ntscsim_led_parse_argv", "ntscsim_led_bind", "ntscsim_led_frames_device",
     "ntscsim_led_frames_host", "ntscsim_led_debug_keep_edges", "ntscsim_led_debug_edges",
+    "ntscsim_filmac_params_init", "ntscsim_filmac_parse_argv", "ntscsim_filmac_bind", "ntscsim_filmac_frames_device",
+    "ntscsim_filmac_frames_host", "ntscsim_filmac_reset", "ntscsim_filmac_get_state", "ntscsim_filmac_set_state",
+    "ntscsim_filmac_debug_levels", "ntscsim_filmac_debug_time_kernels", "ntscsim_filmac_debug_kernel_ms",
 )
 
 
@@ -344,6 +347,20 @@ class LedDesc(C.Structure):
     """struct ntscsim_led_desc"""
     _fields_ = [("src_dev", C.c_void_p), ("src_linesize", C.c_int32), ("dst_linesize", C.c_int32),
                 ("dst_dev", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+FilmacParams = LedParams                   # typedef ntscsim_led_params ntscsim_filmac_params
+
+
+class FilmacDesc(C.Structure):
+    """struct ntscsim_filmac_desc"""
+    _fields_ = [("src", C.c_void_p), ("src_linesize", C.c_int32), ("_pad0", C.c_int32),
+                ("dst", C.c_void_p), ("dst_linesize", C.c_int32), ("_pad1", C.c_int32)]
+
+
+class FilmacState(C.Structure):
+    """struct ntscsim_filmac_state"""
+    _fields_ = [("init", C.c_int32), ("_pad", C.c_int32), ("final_minv", C.c_int64), ("final_maxv", C.c_int64)]
 
 
 _u8p = C.POINTER(C.c_uint8)
@@ -656,6 +673,28 @@ def lib():
     L.ntscsim_led_debug_keep_edges.restype = C.c_int
     L.ntscsim_led_debug_edges.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.ntscsim_led_debug_edges.restype = C.c_int
+    L.ntscsim_filmac_params_init.argtypes = [C.POINTER(FilmacParams)]
+    L.ntscsim_filmac_params_init.restype = None
+    L.ntscsim_filmac_parse_argv.argtypes = [C.POINTER(FilmacParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ntscsim_filmac_parse_argv.restype = C.c_int
+    L.ntscsim_filmac_bind.argtypes = [C.c_void_p, C.POINTER(FilmacParams)]
+    L.ntscsim_filmac_bind.restype = C.c_int
+    L.ntscsim_filmac_frames_device.argtypes = [C.c_void_p, C.POINTER(FilmacDesc), C.c_int, C.c_void_p]
+    L.ntscsim_filmac_frames_device.restype = C.c_int
+    L.ntscsim_filmac_frames_host.argtypes = [C.c_void_p, C.POINTER(FilmacDesc), C.c_int]
+    L.ntscsim_filmac_frames_host.restype = C.c_int
+    L.ntscsim_filmac_reset.argtypes = [C.c_void_p]
+    L.ntscsim_filmac_reset.restype = C.c_int
+    L.ntscsim_filmac_get_state.argtypes = [C.c_void_p, C.POINTER(FilmacState)]
+    L.ntscsim_filmac_get_state.restype = C.c_int
+    L.ntscsim_filmac_set_state.argtypes = [C.c_void_p, C.POINTER(FilmacState)]
+    L.ntscsim_filmac_set_state.restype = C.c_int
+    L.ntscsim_filmac_debug_levels.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.ntscsim_filmac_debug_levels.restype = C.c_int
+    L.ntscsim_filmac_debug_time_kernels.argtypes = [C.c_void_p, C.c_int]
+    L.ntscsim_filmac_debug_time_kernels.restype = C.c_int
+    L.ntscsim_filmac_debug_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.ntscsim_filmac_debug_kernel_ms.restype = C.c_int
     _lib = L
     return L
 
@@ -802,6 +841,25 @@ def make_led_params(flags=(), require_io=False, width=None, height=None):
     rc = L.ntscsim_led_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
     if rc != OK:
         raise NtscsimError(rc, "led parse_argv(%r)" % (list(flags),))
+    if width is not None:
+        p.width = int(width)
+    if height is not None:
+        p.height = int(height)
+    return p
+
+
+def make_filmac_params(flags=(), require_io=False, width=None, height=None):
+    """ntscsim_filmac_params from filmac's switches (filmac.cpp parse_argv :476, the same text as ffmpeg_vhsled's).
+    width / height override the frame size after parsing.  The returned struct keeps the argv strings alive."""
+    L = lib()
+    p = FilmacParams()
+    L.ntscsim_filmac_params_init(C.byref(p))
+    argv = [b"filmac"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    p._argv = arr
+    rc = L.ntscsim_filmac_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
+    if rc != OK:
+        raise NtscsimError(rc, "filmac parse_argv(%r)" % (list(flags),))
     if width is not None:
         p.width = int(width)
     if height is not None:

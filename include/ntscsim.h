@@ -1368,6 +1368,98 @@ int  ntscsim_led_frames_host(ntscsim_ctx *ctx, const ntscsim_led_desc *descs, in
 int  ntscsim_led_debug_keep_edges(ntscsim_ctx *ctx, int on);
 int  ntscsim_led_debug_edges(ntscsim_ctx *ctx, int frame, int32_t *e_host, int32_t *x_host);
 
+/* ---- filmac: the film auto-contrast (filmac.cpp) ----
+ * A film transfer whose levels drift is stretched to full range frame by frame: the tool measures the darkest 128 x 128
+ * block mean and the brightest pixel of the picture's middle, follows both from frame to frame with a recurrence that
+ * opens the range fast and closes it slowly, and maps every B, G, R value linearly so that the followed range fills
+ * the output, in linear light with -gamma.  Every decoded frame gives one output frame.  Mapping:
+ *
+ *   globals :40-56 + preset_NTSC() + parse_argv() :476-584              | ntscsim_filmac_params, _init(), _parse_argv()
+ *   gamma16_do_init() :672-680                                          | ntscsim_blend_tables()    (the same text)
+ *   the widening :857-884, the block statistics :886-923                | k_filmac_stats
+ *   the frame levels of the blocks :887-925                             | k_filmac_frame_levels
+ *   the recurrence :927-942                                             | k_filmac_levels (state in device memory)
+ *   the stretch :946-954, the packing :979-1006                         | k_filmac_tables (a byte table per frame), k_filmac_apply
+ *   all of it, per frame                                                | ntscsim_filmac_frames_device() / _frames_host()
+ *
+ * Decoding, scaling, encoding and the audio pass-through stay with the caller.  Frames are BGRA
+ * in device memory.  The arithmetic is csrc/filmac_levels.hpp, one statement of it for the kernels and the host.
+ */
+/* The tool's switches are, text for text, ffmpeg_vhsled's (:40-56, :476-584), so the parameters are that struct and
+ * the parser is that parser.  The one difference: filmac acts on gamma_correction -- above 1 the levels are measured
+ * and stretched in linear light (:859, :886, :979). */
+typedef ntscsim_led_params ntscsim_filmac_params;
+void ntscsim_filmac_params_init(ntscsim_filmac_params *p);
+int  ntscsim_filmac_parse_argv(ntscsim_filmac_params *p, int argc, const char *const *argv, int require_io);
+
+/* Snapshot the parameters on a ctx, build the gamma tables when gamma_correction > 1, and reset the level state (the
+ * tool's final_init = false).  Waits for filmac work in flight on the ctx.  NTSCSIM_E_SIZE unless 16 <= width, height
+ * <= 16384: the tool refuses a frame below 16 x 16 (:705), and a block's sum stays inside 32 bits. */
+int  ntscsim_filmac_bind(ntscsim_ctx *ctx, const ntscsim_filmac_params *p);
+
+typedef struct ntscsim_filmac_desc {
+    const void *src;                 /* device pointer, BGRA frame of the bound size                          */
+    int32_t     src_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    int32_t     _pad0;
+    void       *dst;                 /* device pointer; bytes of a row behind 4*width are not touched; may be src */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    int32_t     _pad1;
+} ntscsim_filmac_desc;
+/*
+ * The tool's frame body :857-1006 for `n` frames, in order.  With S = 0x10000 * 8192 and L(c) = gamma_dec16(c) << 16
+ * with gamma, S = 0x10000 * 256 and L(c) = c << 16 without:
+ *   blocks    start at x = width*15/100, +128, ... < width*90/100 and y = 0, +128, ... < height (unsigned), are
+ *             128 x 128 and clipped by the frame alone: the last block of a row runs past width*90/100
+ *   maxv      = max(S*4/10, L of every B, G, R of every pixel of every block)
+ *   minv      = min(S*6/10, per block: (sum of min(L_b, L_g, L_r) + count/2) / count);  minv == maxv: maxv++
+ *   state     first frame: final_minv = minv, final_maxv = maxv.  Then final_maxv = (final_maxv + maxv) / 2 when it
+ *             is below maxv, (4 final_maxv + maxv) / 5 otherwise; final_minv = (final_minv + minv) / 2 when it is
+ *             above minv, (4 final_minv + minv) / 5 otherwise
+ *   out       v = (L - final_minv) * S / (final_maxv - final_minv) in 64 bits, truncating; clamped to +-0x7FFFFFFF;
+ *             t = max(0, v >> 16); the byte is gamma_enc16(min(t, 8192)) with gamma, min(t, 255) without; alpha 0xFF
+ * The state lives in device memory and carries from descriptor to descriptor and from call to call without a host
+ * round trip; calls on one ctx must be ordered by the caller (one stream, or events between streams).  final_maxv
+ * stays above final_minv for every sequence of frames; after ntscsim_filmac_set_state() it may
+ * not, and then a denominator of 0 counts as 1 and a negative one divides as the tool's signed division does.
+ * All frame pointers are DEVICE pointers; `descs` is host memory and is consumed by the call.  Enqueued on hip_stream
+ * (NULL: the ctx's own stream), returns without synchronising.  A later descriptor that reads a frame an earlier one
+ * wrote sees the earlier result: it goes into a later launch group.  dst == src with equal linesizes (in place) is
+ * allowed: the map reads a pixel before it writes it.
+ * Kernels, per launch group: k_filmac_stats, grid (blocks, frames), a workgroup per block; k_filmac_frame_levels,
+ * a wavefront per frame; k_filmac_levels, one workgroup, the recurrence by one lane; k_filmac_tables, grid (frames), a
+ * 256-entry byte table per frame; k_filmac_apply, grid (bands of 8 rows, frames), the table in LDS.  Destinations whose pointer and linesize are
+ * multiples of 16 are written as 16-byte vectors, any other, and the last width % 4 pixels of a row, as dwords; whole
+ * quads of a source are read with one 16-byte load from their dword-aligned address.  Same bytes either way.
+ * NTSCSIM_E_SIZE: a linesize below 4*width or not a multiple of 4, a pointer that is not a multiple of 4.
+ * NTSCSIM_E_ARG: a NULL pointer, no ntscsim_filmac_bind() before, a source that overlaps its destination in any way
+ * but in place.
+ */
+int  ntscsim_filmac_frames_device(ntscsim_ctx *ctx, const ntscsim_filmac_desc *descs, int n, void *hip_stream);
+/* ntscsim_filmac_frames_device() on HOST frames, through pinned staging of the ctx.  Synchronous.  Same bytes as the
+ * device call: the bytes the device call leaves alone keep what the host frame held. */
+int  ntscsim_filmac_frames_host(ntscsim_ctx *ctx, const ntscsim_filmac_desc *descs, int n);
+
+typedef struct ntscsim_filmac_state {
+    int32_t init;                    /* final_init :829: 0 before the first frame                            */
+    int32_t _pad;
+    int64_t final_minv, final_maxv;  /* :828; meaningless while init is 0                                     */
+} ntscsim_filmac_state;
+/* The level state: reset() is the tool's start (bind does it too); get / set for a clip that is processed in pieces
+ * or resumed.  All three wait for the device.  set: NTSCSIM_E_PARAM for a value outside +-2^32, which the stretch's
+ * 64-bit product would not hold.  All require ntscsim_filmac_bind(). */
+int  ntscsim_filmac_reset(ntscsim_ctx *ctx);
+int  ntscsim_filmac_get_state(ntscsim_ctx *ctx, ntscsim_filmac_state *out);
+int  ntscsim_filmac_set_state(ntscsim_ctx *ctx, const ntscsim_filmac_state *in);
+/* Debug tap: minv, maxv, final_minv, final_maxv (in this order) of frame `frame` of the last frames call, so that a
+ * test can tell wrong statistics from a wrong recurrence from a wrong map; the kernels pass these values through device
+ * memory anyway, so nothing has to be switched on.  Synchronises.  NTSCSIM_E_ARG when `frame` is outside the last call. */
+int  ntscsim_filmac_debug_levels(ntscsim_ctx *ctx, int frame, int64_t out[4]);
+/* Developer timing (tools/bench_filmac.py).  time_kernels(on): while on, every frames call records events between its
+ * kernels.  kernel_ms(): the time of k_filmac_stats, k_filmac_frame_levels, k_filmac_levels, k_filmac_tables and
+ * k_filmac_apply of the last frames_device call, summed over its launch groups; synchronises; NTSCSIM_E_ARG when nothing was timed. */
+int  ntscsim_filmac_debug_time_kernels(ntscsim_ctx *ctx, int on);
+int  ntscsim_filmac_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[5]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,10 +80,28 @@ def led_row(path="profiles/led.json"):
             "`profiles/led.json`, DESIGN.md §7i")
 
 
-try:
-    rows.append(led_row())
-except Exception:
-    pass
+def filmac_row(path="profiles/filmac.json"):
+    """The filmac stage's row, from tools/bench_filmac.py's file."""
+    c = json.load(open(path))
+    a, ag, b, bg = (c["cases"][n] for n in ("720x486_plain", "720x486_gamma", "1920x1080_plain", "1920x1080_gamma"))
+    km = b["kernel_ms"]
+    return ("the film auto-contrast (`filmac`, `ntscsim_filmac_*`): 600 frames of drifting noise resident in HBM through one `ntscsim_filmac_frames_device` call, "
+            "the level state on the device throughout (`tools/bench_filmac.py`)",
+            "720×486: **%s frames/s** (%s with `-gamma ntsc`), %.2f × the time of a device-to-device copy of 8·W·H bytes per frame and %.2f × that of 12·W·H in the same run; "
+            "1920×1080: %s frames/s (%s), %.2f × / %.2f × the copies; the five kernels at 1920×1080: statistics %.2f, frame levels %.3f, recurrence %.2f, tables %.3f, map %.2f ms; "
+            "the reference's loop on one CPU core of the build machine (not the GPU host): %.0f frames/s at 720×486, %.0f with `-gamma 2.2`" % (
+                k(a["frames_per_s"]), k(ag["frames_per_s"]), a["filmac_over_copy_8wh"], a["filmac_over_copy_12wh"],
+                k(b["frames_per_s"]), k(bg["frames_per_s"]), b["filmac_over_copy_8wh"], b["filmac_over_copy_12wh"],
+                km["k_filmac_stats"], km["k_filmac_frame_levels"], km["k_filmac_levels"], km["k_filmac_tables"], km["k_filmac_apply"],
+                c["reference_cpu"]["frames_per_s"], c["reference_cpu"]["frames_per_s_gamma"]),
+            "`profiles/filmac.json`, DESIGN.md §7j")
+
+
+for row in (led_row, filmac_row):
+    try:
+        rows.append(row())
+    except Exception:
+        pass
 tbl = "| what (1× MI355X, 720×486 unless said otherwise) | measured | where |\n|---|---|---|\n" + "\n".join("| %s | %s | %s |" % r for r in rows)
 s = open("README.md").read()
 a, b = s.index("<!-- numbers:begin -->"), s.index("<!-- numbers:end -->")
