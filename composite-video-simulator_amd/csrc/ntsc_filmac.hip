@@ -55,10 +55,6 @@ struct FilmacRec {                       // one frame
 
 struct FilmacTap { int64_t minv, maxv, final_minv, final_maxv; };   // ntscsim_filmac_debug_levels()
 
-// 16 bytes from an address that is only a multiple of 4
-typedef px4_u4 filmac_u4a __attribute__((aligned(4)));
-FDEV px4_u4 gld4a(const void *p) { return *(const PX4_GLOBAL filmac_u4a *)p; }
-
 FDEV uint32_t min3(uint32_t p) { return min(min(p & 0xFFu, (p >> 8) & 0xFFu), (p >> 16) & 0xFFu); }
 FDEV uint32_t max3(uint32_t p) { return max(max(p & 0xFFu, (p >> 8) & 0xFFu), (p >> 16) & 0xFFu); }
 

@@ -1,5 +1,5 @@
 // ntsc_frames.hpp -- the host logic every device stage shares (frameblend: csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip,
-// average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip, filmac: csrc/ntsc_filmac.hip): the bytes a frame covers,
+// average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip, filmac: csrc/ntsc_filmac.hip, posterize and colormap: csrc/ntsc_pixmap.hip): the bytes a frame covers,
 // what a plane of pixels must satisfy, where a run of descriptors has to be cut into launches, what a call writes, and
 // the copy between two row pitches.  No HIP in it: plain C++, so that it can be driven without a GPU
 // (tests/frames_host_check.cpp).

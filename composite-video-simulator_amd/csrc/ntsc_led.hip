@@ -52,10 +52,6 @@ struct LedRec {                          // one frame
     uint32_t _pad;
 };
 
-// 16 bytes from an address that is only a multiple of 4: the source side of a shifted row
-typedef px4_u4 led_u4a __attribute__((aligned(4)));
-LDEV px4_u4 gld4a(const void *p) { return *(const PX4_GLOBAL led_u4a *)p; }
-
 // e of one row whose probe has come back: p[c] is the lane's pixel of chunk c (anything where the pixel lies behind
 // the row's end).  The masks and everything decided on them are wave-uniform.
 LDEV int led_row_edge(const uint8_t *row, const uint32_t (&p)[LED_PROBE], int W, int lane)

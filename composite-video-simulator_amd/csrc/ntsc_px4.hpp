@@ -1,4 +1,5 @@
-// ntsc_px4.hpp -- how the kernels of the layer stages (csrc/ntsc_key.hip, csrc/ntsc_avg.hip) reach their pixels: dwords
+// ntsc_px4.hpp -- how the kernels of the stages (csrc/ntsc_key.hip, csrc/ntsc_avg.hip, csrc/ntsc_led.hip,
+// csrc/ntsc_filmac.hip, csrc/ntsc_pixmap.hip) reach their pixels: dwords
 // and quads of BGRA pixels through the global address space.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +17,9 @@ namespace ntscsim {
 typedef uint32_t px4_u4 __attribute__((ext_vector_type(4)));
 PX4_DEV uint32_t gld(const void *p) { return *(const PX4_GLOBAL uint32_t *)p; }
 PX4_DEV px4_u4 gld4(const void *p) { return *(const PX4_GLOBAL px4_u4 *)p; }
+// 16 bytes from an address that is only a multiple of 4
+typedef px4_u4 px4_u4a __attribute__((aligned(4)));
+PX4_DEV px4_u4 gld4a(const void *p) { return *(const PX4_GLOBAL px4_u4a *)p; }
 PX4_DEV void gst(void *p, uint32_t v) { *(PX4_GLOBAL uint32_t *)p = v; }
 PX4_DEV void gst4(void *p, px4_u4 v) { *(PX4_GLOBAL px4_u4 *)p = v; }
 

@@ -224,10 +224,12 @@ struct ntscsim_ctx {
     ntscsim::ScanState *scan = nullptr;     // ntscsim_scan_bind(): state of the scanimate stage (csrc/ntsc_scan.hip)
     ntscsim::LedState *led = nullptr;       // ntscsim_led_bind(): state of the vhsled stage (csrc/ntsc_led.hip)
     ntscsim::FilmacState *filmac = nullptr; // ntscsim_filmac_bind(): state of the filmac stage (csrc/ntsc_filmac.hip)
+    ntscsim::PostState *post = nullptr;     // ntscsim_post_bind(): state of the posterize stage (csrc/ntsc_pixmap.hip)
+    ntscsim::CmapState *cmap = nullptr;     // ntscsim_cmap_bind(): state of the colormap stage (csrc/ntsc_pixmap.hip)
 };
 ntscsim::CtxStageView ntscsim::ctx_stage_view(ntscsim_ctx *c)
 {
-    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan, &c->led, &c->filmac};
+    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan, &c->led, &c->filmac, &c->post, &c->cmap};
 }
 static void submit_engine_destroy(ntscsim_ctx *c);
 static int sub_wait_ticket(ntscsim_ctx *c, uint64_t ticket);
@@ -473,6 +475,8 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     if (c->scan) { ntscsim::scan_state_destroy(c->scan); c->scan = nullptr; }
     if (c->led) { ntscsim::led_state_destroy(c->led); c->led = nullptr; }
     if (c->filmac) { ntscsim::filmac_state_destroy(c->filmac); c->filmac = nullptr; }
+    if (c->post) { ntscsim::post_state_destroy(c->post); c->post = nullptr; }
+    if (c->cmap) { ntscsim::cmap_state_destroy(c->cmap); c->cmap = nullptr; }
     for (Geometry *e : c->geoms) {
         e->lskip.release(); e->pskip.release(); e->jrow.release();
         delete e;

@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "AutoContrast", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "AutoContrast", "Posterizer", "ColorMapper", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -944,6 +944,114 @@ class AutoContrast:
 
     def sync(self):
         self.sim.sync()
+
+
+class _PixelMapStage:
+    """What Posterizer and ColorMapper share: the bound context, the descriptor arrays and the two frame calls.
+    `flags` are the tool's switches.  width / height: the frame size, 1 .. 16384 each (the tools have no -height).
+    sim: share the context of a FieldSimulator; otherwise a context of its own is created.  Frames are uint8
+    [H, W, 4] with contiguous pixels and any row stride; a job is a tuple of frames in the order of _FRAMES."""
+    _STAGE = None                           # "post" / "cmap": ntscsim_<stage>_*
+    _DESC = None
+    _FRAMES = ("dst", "src")
+
+    def __init__(self, flags=(), width=None, height=None, sim=None, device=0, params=None):
+        self.params = params if params is not None else _capi.make_pixmap_params(self._STAGE, flags, width=width, height=height)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        try:
+            self._call("bind", C.byref(self.params))
+        except Exception:
+            self.close()
+            raise
+
+    def _call(self, what, *args):
+        name = "ntscsim_%s_%s" % (self._STAGE, what)
+        self.sim._chk(getattr(self._lib, name)(self.sim._h, *args), name)
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    def _fill(self, d, job, ptr, linesize):
+        """one descriptor from one job; the frames named in _FRAMES are set here, a stage adds the rest"""
+        for name, t in zip(self._FRAMES, job):
+            if t is None:
+                continue
+            if len(t.shape) != 3 or t.shape[2] != 4 or (t.shape[0], t.shape[1]) != (self.params.height, self.params.width):
+                raise NtscsimError(_capi.E_SIZE, "a frame of shape %r on a stage bound to %dx%d"
+                                   % (tuple(t.shape), self.params.width, self.params.height))
+            setattr(d, name, ptr(t))
+            setattr(d, name + "_linesize", linesize(t))
+
+    def _descs(self, jobs, ptr, linesize):
+        arr = (self._DESC * max(1, len(jobs)))()
+        for d, job in zip(arr, jobs):
+            self._fill(d, job, ptr, linesize)
+        return arr
+
+    def frames(self, jobs, stream=None):
+        """ntscsim_<stage>_frames_device on torch uint8 CUDA tensors, in order; dst may be src.  One launch group for
+        all jobs that do not depend on each other.  Enqueues; does not synchronise."""
+        arr = self._descs(jobs, lambda t: t.data_ptr(), lambda t: t.stride(0))
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("frames_device", arr, len(jobs), C.c_void_p(stream))
+
+    def frames_host(self, jobs):
+        """ntscsim_<stage>_frames_host: the same on numpy uint8 arrays.  Synchronous."""
+        arr = self._descs(jobs, lambda a: a.ctypes.data, lambda a: a.strides[0])
+        self._call("frames_host", arr, len(jobs))
+
+    def last_kernels(self):
+        return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
+
+
+class Posterizer(_PixelMapStage):
+    """The posterize stage (ntscsim_post_*): every byte of a pixel, alpha included, keeps the `-threshhold` high bits
+    of the input it came from, as ffmpeg_posterize does.  jobs = [(dst, src, layer), ...] or [(dst, src), ...]; layer
+    is an index into the -i list of `flags` (default: the last input, whose frame is the tool's output)."""
+    _STAGE = "post"
+    _DESC = _capi.PostDesc
+
+    def _fill(self, d, job, ptr, linesize):
+        super()._fill(d, job, ptr, linesize)
+        d.layer = int(job[2]) if len(job) > 2 else self.params.n_layers - 1
+
+
+class ColorMapper(_PixelMapStage):
+    """The colormap stage (ntscsim_cmap_*): the green byte of a pixel selects the output pixel from a 256-entry table,
+    which is taken from the middle row of a map frame, as ffmpeg_colormap does with its second input.  jobs =
+    [(dst, src, map), ...] in clip order; map None: there is no second input, the table stays as it is.  The table
+    lives on the device and carries from job to job and from call to call; calls must be ordered by the caller (one
+    stream)."""
+    _STAGE = "cmap"
+    _DESC = _capi.CmapDesc
+    _FRAMES = ("dst", "src", "map")
+
+    def reset(self):
+        """The tool's start: table[i] = i * 0x01010101.  Synchronises."""
+        self._call("reset")
+
+    @property
+    def table(self):
+        """The 256 pixels of the table as a numpy uint32 array.  Reading and writing synchronise."""
+        import numpy as np
+        out = (C.c_uint32 * 256)()
+        self._call("get_table", out)
+        return np.frombuffer(out, dtype=np.uint32).copy()
+
+    @table.setter
+    def table(self, value):
+        vals = [int(x) for x in value]
+        if len(vals) != 256:
+            raise NtscsimError(_capi.E_ARG, "a table of %d entries" % len(vals))
+        self._call("set_table", (C.c_uint32 * 256)(*vals))
 
 
 class Pool:

@@ -63,6 +63,12 @@ EXPORTS = (
     "ntscsim_filmac_params_init", "ntscsim_filmac_parse_argv", "ntscsim_filmac_bind", "ntscsim_filmac_frames_device",
     "ntscsim_filmac_frames_host", "ntscsim_filmac_reset", "ntscsim_filmac_get_state", "ntscsim_filmac_set_state",
     "ntscsim_filmac_debug_levels", "ntscsim_filmac_debug_time_kernels", "ntscsim_filmac_debug_kernel_ms",
+    "ntscsim_pixmap_params_init", "ntscsim_pixmap_params_free", "ntscsim_pixmap_parse_argv",
+    "ntscsim_post_params_init", "ntscsim_post_params_free", "ntscsim_post_parse_argv", "ntscsim_post_bind",
+    "ntscsim_post_frames_device", "ntscsim_post_frames_host",
+    "ntscsim_cmap_params_init", "ntscsim_cmap_params_free", "ntscsim_cmap_parse_argv", "ntscsim_cmap_bind",
+    "ntscsim_cmap_frames_device", "ntscsim_cmap_frames_host", "ntscsim_cmap_reset", "ntscsim_cmap_get_table",
+    "ntscsim_cmap_set_table",
 )
 
 
@@ -361,6 +367,43 @@ class FilmacDesc(C.Structure):
 class FilmacState(C.Structure):
     """struct ntscsim_filmac_state"""
     _fields_ = [("init", C.c_int32), ("_pad", C.c_int32), ("final_minv", C.c_int64), ("final_maxv", C.c_int64)]
+
+
+class PixmapLayer(C.Structure):
+    """struct ntscsim_pixmap_layer"""
+    _fields_ = [("path", C.c_char_p), ("threshhold", C.c_int32), ("_pad", C.c_int32)]
+
+
+class PixmapParams(C.Structure):
+    """struct ntscsim_pixmap_params: the switches of ffmpeg_posterize and of ffmpeg_colormap"""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("use_422_colorspace", C.c_int32),
+                ("field_rate_num", C.c_int32), ("field_rate_den", C.c_int32), ("output_pal", C.c_int32),
+                ("n_layers", C.c_int32), ("layers_cap", C.c_int32), ("_pad", C.c_int32),
+                ("layers", C.POINTER(PixmapLayer)), ("output_path", C.c_char_p)]
+
+    def __del__(self):                      # the input list is a heap block of the library's
+        try:
+            if _lib is not None and self.layers:
+                _lib.ntscsim_pixmap_params_free(C.byref(self))
+        except Exception:
+            pass
+
+
+PostParams = PixmapParams                  # typedef ntscsim_pixmap_params ntscsim_post_params
+CmapParams = PixmapParams                  # typedef ntscsim_pixmap_params ntscsim_cmap_params
+
+
+class PostDesc(C.Structure):
+    """struct ntscsim_post_desc"""
+    _fields_ = [("src", C.c_void_p), ("src_linesize", C.c_int32), ("_pad0", C.c_int32),
+                ("dst", C.c_void_p), ("dst_linesize", C.c_int32), ("layer", C.c_int32)]
+
+
+class CmapDesc(C.Structure):
+    """struct ntscsim_cmap_desc"""
+    _fields_ = [("src", C.c_void_p), ("src_linesize", C.c_int32), ("_pad0", C.c_int32),
+                ("dst", C.c_void_p), ("dst_linesize", C.c_int32), ("_pad1", C.c_int32),
+                ("map", C.c_void_p), ("map_linesize", C.c_int32), ("_pad2", C.c_int32)]
 
 
 _u8p = C.POINTER(C.c_uint8)
@@ -695,6 +738,32 @@ def lib():
     L.ntscsim_filmac_debug_time_kernels.restype = C.c_int
     L.ntscsim_filmac_debug_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.ntscsim_filmac_debug_kernel_ms.restype = C.c_int
+    L.ntscsim_pixmap_params_init.argtypes = [C.POINTER(PixmapParams)]
+    L.ntscsim_pixmap_params_init.restype = None
+    L.ntscsim_pixmap_params_free.argtypes = [C.POINTER(PixmapParams)]
+    L.ntscsim_pixmap_params_free.restype = None
+    L.ntscsim_pixmap_parse_argv.argtypes = [C.POINTER(PixmapParams), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int]
+    L.ntscsim_pixmap_parse_argv.restype = C.c_int
+    for stage, desc in (("post", PostDesc), ("cmap", CmapDesc)):
+        fn = lambda what: getattr(L, "ntscsim_%s_%s" % (stage, what))
+        fn("params_init").argtypes = [C.POINTER(PixmapParams)]
+        fn("params_init").restype = None
+        fn("params_free").argtypes = [C.POINTER(PixmapParams)]
+        fn("params_free").restype = None
+        fn("parse_argv").argtypes = [C.POINTER(PixmapParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+        fn("parse_argv").restype = C.c_int
+        fn("bind").argtypes = [C.c_void_p, C.POINTER(PixmapParams)]
+        fn("bind").restype = C.c_int
+        fn("frames_device").argtypes = [C.c_void_p, C.POINTER(desc), C.c_int, C.c_void_p]
+        fn("frames_device").restype = C.c_int
+        fn("frames_host").argtypes = [C.c_void_p, C.POINTER(desc), C.c_int]
+        fn("frames_host").restype = C.c_int
+    L.ntscsim_cmap_reset.argtypes = [C.c_void_p]
+    L.ntscsim_cmap_reset.restype = C.c_int
+    L.ntscsim_cmap_get_table.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    L.ntscsim_cmap_get_table.restype = C.c_int
+    L.ntscsim_cmap_set_table.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    L.ntscsim_cmap_set_table.restype = C.c_int
     _lib = L
     return L
 
@@ -860,6 +929,27 @@ def make_filmac_params(flags=(), require_io=False, width=None, height=None):
     rc = L.ntscsim_filmac_parse_argv(C.byref(p), len(argv), arr, int(bool(require_io)))
     if rc != OK:
         raise NtscsimError(rc, "filmac parse_argv(%r)" % (list(flags),))
+    if width is not None:
+        p.width = int(width)
+    if height is not None:
+        p.height = int(height)
+    return p
+
+
+def make_pixmap_params(stage, flags=(), require_io=False, width=None, height=None):
+    """ntscsim_post_params (stage "post": ffmpeg_posterize.cpp parse_argv :620) or ntscsim_cmap_params (stage "cmap":
+    ffmpeg_colormap.cpp parse_argv :622) from the tool's switches.  width / height override the frame size after parsing
+    (the tools have no -height).  The returned struct keeps the argv strings alive (the inputs' paths and output_path
+    point into them) and frees its input list when it is collected."""
+    L = lib()
+    p = PixmapParams()
+    getattr(L, "ntscsim_%s_params_init" % stage)(C.byref(p))
+    argv = [stage.encode()] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    p._argv = arr
+    rc = getattr(L, "ntscsim_%s_parse_argv" % stage)(C.byref(p), len(argv), arr, int(bool(require_io)))
+    if rc != OK:
+        raise NtscsimError(rc, "%s parse_argv(%r)" % (stage, list(flags)))
     if width is not None:
         p.width = int(width)
     if height is not None:

@@ -1460,6 +1460,158 @@ int  ntscsim_filmac_debug_levels(ntscsim_ctx *ctx, int frame, int64_t out[4]);
 int  ntscsim_filmac_debug_time_kernels(ntscsim_ctx *ctx, int on);
 int  ntscsim_filmac_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[5]);
 
+/* ---- the switches of the two pixel-map tools (ffmpeg_posterize.cpp, ffmpeg_colormap.cpp) ----
+ * The two tools have the same globals, the same InputFile list and the same parse_argv() (posterize :620-696,
+ * colormap :622-693) but for one switch: posterize has -threshhold, a number that belongs to the current input.  One
+ * struct and one parser serve both; the stages' own names below are typedefs and thin wrappers, as filmac's are on
+ * vhsled's.
+ */
+typedef struct ntscsim_pixmap_layer {
+    const char *path;                /* the -i that opened the input (points into argv), may be NULL          */
+    int32_t  threshhold;             /* posterize :71  3 (-threshhold): bits kept of every byte; an int, any value */
+    int32_t  _pad;
+} ntscsim_pixmap_layer;
+
+typedef struct ntscsim_pixmap_params {
+    uint32_t struct_size;            /* = sizeof(ntscsim_pixmap_params)                                     */
+    int32_t  width, height;          /* 720 x 480 (preset_NTSC), 720 x 576 (-tvstd pal), -width             */
+    int32_t  use_422_colorspace;     /* false (-422 / -420); recorded, not acted on                         */
+    int32_t  field_rate_num, field_rate_den;    /* 60000 / 1001 (preset_NTSC), 50 / 1 (-tvstd pal)          */
+    int32_t  output_pal;             /* 0 NTSC, 1 PAL (-tvstd)                                              */
+    int32_t  n_layers;               /* inputs so far, in order; no upper limit                             */
+    int32_t  layers_cap;             /* allocated entries of `layers`                                       */
+    int32_t  _pad;
+    ntscsim_pixmap_layer *layers;    /* heap block owned by the struct: ntscsim_pixmap_params_free()        */
+    const char *output_path;         /* -o                                                                  */
+} ntscsim_pixmap_params;
+
+void ntscsim_pixmap_params_init(ntscsim_pixmap_params *p);
+/* Releases the input list (the struct itself is the caller's). */
+void ntscsim_pixmap_params_free(ntscsim_pixmap_params *p);
+/* Mirror of both parse_argv(): -i -o -width -422 -420 -tvstd pal|ntsc, -h / -help (any number of leading '-'), and
+ * -threshhold when with_threshhold != 0 (otherwise it is an unknown switch, as in ffmpeg_colormap).  -width and
+ * -threshhold go through strtoul with base 0 and the tool's cast to int; a width below 32 is refused.  Every -i
+ * appends an input that copies the threshhold of the one before (new_input_file(); 3 for the first), and -threshhold
+ * sets that of the last input so far; before any -i the tool throws (current_input_file()): NTSCSIM_E_FLAG.  A value
+ * outside 0..8 is recorded as the tool records it and refused by ntscsim_post_bind().  argv[0] is the program name.
+ * NTSCSIM_E_FLAG (the tool's "return 1") for an unknown switch, a bare word, a missing value (-tvstd's too, which the
+ * tool hands to strcmp as NULL), an unknown tv standard; require_io != 0 applies the "No output file / No input files"
+ * checks.  NTSCSIM_E_HELP for -h / -help. */
+int  ntscsim_pixmap_parse_argv(ntscsim_pixmap_params *p, int argc, const char *const *argv, int require_io, int with_threshhold);
+
+/* ---- posterize: the bit-mask posteriser (ffmpeg_posterize.cpp) ----
+ * Every byte of every pixel, alpha included, keeps its `threshhold` high bits.  Mapping:
+ *
+ *   globals + InputFile :71 + preset_NTSC() :604-611 + parse_argv() :620-696 | ntscsim_post_params, _init(), _free(), _parse_argv()
+ *   composite_layer() :789-813                                          | k_post_frames
+ *   the call site :1061, one layer of one frame                         | a descriptor of ntscsim_post_frames_device() / _frames_host()
+ *
+ * Decoding, scaling, encoding and the audio pass-through stay with the caller.  Frames are BGRA
+ * in device memory.  A frame carries no state into the next one.
+ */
+typedef ntscsim_pixmap_params ntscsim_post_params;
+void ntscsim_post_params_init(ntscsim_post_params *p);
+void ntscsim_post_params_free(ntscsim_post_params *p);
+int  ntscsim_post_parse_argv(ntscsim_post_params *p, int argc, const char *const *argv, int require_io);
+
+/* Snapshot the parameters and the input list on a ctx.  Waits for posterize work in flight on the ctx.
+ * NTSCSIM_E_SIZE unless 1 <= width, height <= 16384.  NTSCSIM_E_PARAM for an input whose threshhold is outside 0..8:
+ * the tool's `0xFF << (8 - threshhold)` then shifts by a count that C leaves undefined.  The parameters are checked
+ * before the ctx is looked at (a NULL ctx: NTSCSIM_E_ARG), so a host without a device can validate a command line. */
+int  ntscsim_post_bind(ntscsim_ctx *ctx, const ntscsim_post_params *p);
+
+typedef struct ntscsim_post_desc {
+    const void *src;                 /* device pointer, BGRA frame of the bound size                          */
+    int32_t     src_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    int32_t     _pad0;
+    void       *dst;                 /* device pointer; bytes of a row behind 4*width are not touched; may be src */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    int32_t     layer;               /* index into the bound input list: whose threshhold masks the frame     */
+} ntscsim_post_desc;
+/*
+ * composite_layer() :789-813 for `n` (frame, input) pairs, in order:
+ *   mask = ((0xFF << (8 - threshhold)) & 0xFF) * 0x01010101;  out = in & mask
+ * so threshhold 8 copies and threshhold 0 clears.  The tool's loop :1035-1062 calls this for every input in turn on
+ * one output frame, each call overwriting all of it: a caller that wants the tool's frame passes the last input that
+ * has a frame (or all of them, in order, with one dst: each goes into a launch group of its own).
+ * All frame pointers are DEVICE pointers; `descs` is host memory and is consumed by the call.  Enqueued on hip_stream
+ * (NULL: the ctx's own stream), returns without synchronising.  Descriptors take effect in order.  dst == src with
+ * equal linesizes (in place) is allowed: a lane reads a pixel before it writes it.
+ * Kernel: k_post_frames, one launch for all descriptors that do not depend on each other, grid (bands of 8 rows,
+ * frames).  Destinations whose pointer and linesize are multiples of 16 are written as 16-byte vectors, any other, and
+ * the last width % 4 pixels of a row, as dwords; whole quads of a source are read with one 16-byte load from their
+ * dword-aligned address.  Same bytes either way.
+ * NTSCSIM_E_SIZE: a linesize below 4*width or not a multiple of 4, a pointer that is not a multiple of 4.
+ * NTSCSIM_E_ARG: a NULL pointer, no ntscsim_post_bind() before, a layer outside the bound list, a source that overlaps
+ * its destination in any way but in place.
+ */
+int  ntscsim_post_frames_device(ntscsim_ctx *ctx, const ntscsim_post_desc *descs, int n, void *hip_stream);
+/* ntscsim_post_frames_device() on HOST frames, through pinned staging of the ctx.  Synchronous.  Same bytes as the
+ * device call: the bytes the device call leaves alone keep what the host frame held. */
+int  ntscsim_post_frames_host(ntscsim_ctx *ctx, const ntscsim_post_desc *descs, int n);
+
+/* ---- colormap: false colour through a table taken from a second picture (ffmpeg_colormap.cpp) ----
+ * A 256-entry table of pixels is taken, before every output frame, from the middle scanline of the second input; the
+ * first input's green byte then selects the output pixel from it.  Mapping:
+ *
+ *   globals + preset_NTSC() + parse_argv() :622-693                     | ntscsim_cmap_params, _init(), _free(), _parse_argv()
+ *   colormap[256] :58, its start value :833                             | device memory of the ctx; ntscsim_cmap_reset(), _get_table(), _set_table()
+ *   take_colormap() :785-799                                            | the table fill of k_cmap_frames; k_cmap_take
+ *   composite_layer() :802-822                                          | k_cmap_frames
+ *   the call site :1072-1075, one output frame                          | a descriptor of ntscsim_cmap_frames_device() / _frames_host()
+ *
+ * Decoding, scaling, encoding and the audio pass-through stay with the caller.
+ */
+typedef ntscsim_pixmap_params ntscsim_cmap_params;
+void ntscsim_cmap_params_init(ntscsim_cmap_params *p);
+void ntscsim_cmap_params_free(ntscsim_cmap_params *p);
+int  ntscsim_cmap_parse_argv(ntscsim_cmap_params *p, int argc, const char *const *argv, int require_io);
+
+/* Snapshot the parameters on a ctx and reset the table to the tool's start, colormap[i] = i * 0x01010101 (:833).
+ * Waits for colormap work in flight on the ctx.  NTSCSIM_E_SIZE unless 1 <= width, height <= 16384. */
+int  ntscsim_cmap_bind(ntscsim_ctx *ctx, const ntscsim_cmap_params *p);
+
+typedef struct ntscsim_cmap_desc {
+    const void *src;                 /* device pointer, BGRA frame of the bound size: the first input         */
+    int32_t     src_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    int32_t     _pad0;
+    void       *dst;                 /* device pointer; bytes of a row behind 4*width are not touched; may be src */
+    int32_t     dst_linesize;        /* bytes, >= 4*width, multiple of 4                                     */
+    int32_t     _pad1;
+    const void *map;                 /* device pointer, BGRA frame of the bound size: the second input; NULL when
+                                      * there is none (no second -i, or a file without video): the table stays    */
+    int32_t     map_linesize;        /* bytes, >= 4*width, multiple of 4; ignored when map is NULL             */
+    int32_t     _pad2;
+} ntscsim_cmap_desc;
+/*
+ * The tool's :1072-1075 for `n` output frames, in order.  With the pixels as uint32_t (B | G<<8 | R<<16 | A<<24):
+ *   map != NULL:  table[i] = map[height / 2][(i * width) / 256] for i < 256, whole dwords, unsigned and truncating
+ *   out[y][x]   = table[(src[y][x] >> 8) & 0xFF]
+ * A second input that has not decoded a frame yet is an all-zero frame in the tool (:198), not an absent one: pass
+ * zeros.  The table lives in device memory and carries from descriptor to descriptor and from call to call without a
+ * host round trip; calls on one ctx must be ordered by the caller (one stream, or events between streams).
+ * All frame pointers are DEVICE pointers; `descs` is host memory and is consumed by the call.  Enqueued on hip_stream
+ * (NULL: the ctx's own stream), returns without synchronising.  Descriptors take effect in order: a later one that
+ * reads a frame (a map's middle row too) an earlier one wrote goes into a later launch group.  dst == src with equal
+ * linesizes (in place) is allowed.
+ * Kernels, per launch group: k_cmap_frames, grid (bands of 8 rows, frames): every workgroup fills a 256-dword table in
+ * LDS from the middle row of the nearest map at or before its descriptor in the group, or from the ctx's table when
+ * there is none, and gathers from it; then k_cmap_take, 256 lanes, which writes the ctx's table from the group's last
+ * map (not launched when the group has none).  Vector and dword forms as for posterize.
+ * NTSCSIM_E_SIZE: a linesize below 4*width or not a multiple of 4, a pointer that is not a multiple of 4.
+ * NTSCSIM_E_ARG: a NULL src or dst, no ntscsim_cmap_bind() before, a source that overlaps its destination in any way
+ * but in place, a destination that overlaps the middle row of its own map.
+ */
+int  ntscsim_cmap_frames_device(ntscsim_ctx *ctx, const ntscsim_cmap_desc *descs, int n, void *hip_stream);
+/* ntscsim_cmap_frames_device() on HOST frames, through pinned staging of the ctx.  Synchronous.  Same bytes as the
+ * device call; of a map only the middle row travels. */
+int  ntscsim_cmap_frames_host(ntscsim_ctx *ctx, const ntscsim_cmap_desc *descs, int n);
+/* The table: reset() is the tool's start (bind does it too); get / set for a clip that is processed in pieces, and
+ * for a test to tell a wrong table from a wrong gather.  All three wait for the device and require ntscsim_cmap_bind(). */
+int  ntscsim_cmap_reset(ntscsim_ctx *ctx);
+int  ntscsim_cmap_get_table(ntscsim_ctx *ctx, uint32_t out[256]);
+int  ntscsim_cmap_set_table(ntscsim_ctx *ctx, const uint32_t in[256]);
+
 #ifdef __cplusplus
 }
 #endif

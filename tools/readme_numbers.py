@@ -97,11 +97,43 @@ def filmac_row(path="profiles/filmac.json"):
             "`profiles/filmac.json`, DESIGN.md §7j")
 
 
+def pixmap_rows(path="profiles/pixmap.json"):
+    """The posterize and the colormap stage's rows, from tools/bench_pixmap.py's file."""
+    j = json.load(open(path))
+    c = j["cases"]
+
+    def cell(stage, size):
+        g, r = c["%s_gradient_%s" % (size, stage)], c["%s_random_green_%s" % (size, stage)]
+        return k(g["frames_per_s"]), k(r["frames_per_s"]), g["frac_hbm"], g["over_copy"], r["over_copy"]
+
+    p7, p19 = cell("post", "720x486"), cell("post", "1920x1080")
+    n7, n19, m7, m19 = (cell(st, sz) for st in ("cmap_nomap", "cmap_map") for sz in ("720x486", "1920x1080"))
+    ref = j["reference_cpu"]
+    what = "600 frames resident in HBM through one `ntscsim_%s_frames_device` call, smooth gradients / uniform random green (`tools/bench_pixmap.py`)"
+    return [("the bit-mask posteriser (`ffmpeg_posterize`, `ntscsim_post_*`): " + what % "post",
+             "720×486: **%s / %s frames/s**, `frac_hbm` %.3f on 8·W·H bytes per frame, %.2f / %.2f × the time of a device-to-device copy of the same traffic in the same run; "
+             "1920×1080: %s / %s frames/s, `frac_hbm` %.3f, %.2f / %.2f × the copy; "
+             "the reference's loop on one CPU core of the build machine (not the GPU host): %.0f frames/s at 720×486" % (p7 + p19 + (ref["frames_per_s_post"],)),
+             "`profiles/pixmap.json`, DESIGN.md §7k"),
+            ("the false-colour table stage (`ffmpeg_colormap`, `ntscsim_cmap_*`): " + what % "cmap" + ", the table on the device throughout",
+             "no map in any descriptor, 720×486: **%s / %s frames/s**, %.2f / %.2f × the copy, %.2f / %.2f × `k_post_frames` (the random-green figure is the LDS bank-conflict test: no table replication); "
+             "1920×1080: %s / %s frames/s, %.2f / %.2f × the copy; a map in every descriptor (table filled from the map's row, plus `k_cmap_take`): "
+             "720×486 %s / %s frames/s, %.2f / %.2f × the copy; 1920×1080 %s / %s, %.2f / %.2f ×; "
+             "the reference's loops on one CPU core of the build machine: %.0f frames/s at 720×486" % (
+                 n7[0], n7[1], n7[3], n7[4], c["720x486_gradient_cmap_nomap"]["over_post"], c["720x486_random_green_cmap_nomap"]["over_post"],
+                 n19[0], n19[1], n19[3], n19[4], m7[0], m7[1], m7[3], m7[4], m19[0], m19[1], m19[3], m19[4], ref["frames_per_s_cmap"]),
+             "`profiles/pixmap.json`, DESIGN.md §7k")]
+
+
 for row in (led_row, filmac_row):
     try:
         rows.append(row())
     except Exception:
         pass
+try:
+    rows.extend(pixmap_rows())
+except Exception:
+    pass
 tbl = "| what (1× MI355X, 720×486 unless said otherwise) | measured | where |\n|---|---|---|\n" + "\n".join("| %s | %s | %s |" % r for r in rows)
 s = open("README.md").read()
 a, b = s.index("<!-- numbers:begin -->"), s.index("<!-- numbers:end -->")
