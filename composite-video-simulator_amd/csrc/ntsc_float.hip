@@ -16,6 +16,11 @@
 //     and dropout come from the same setup kernels as in the exact mode;
 //   * dropping a truncation of a positive signal moves its mean by +1/2 (of 1/256 of an output step): the luma
 //     path's five dropped truncations are compensated by ONE constant in the output matrix (NTSC_FP_LUMA_BIAS).
+// DESIGN.md 3b states the same definition as one table (the chain with every quantisation of the signal removed, in real
+// numbers); tests/test_float_model_gpu.py holds these kernels to an fp64 evaluation of it within the evaluation noise of
+// fp32 (0.000892 of an output step).  The three decoders below have different loop conditions, each with widths of its
+// own in that test: steady() of k_decode_fp<true> in launches of 130 fields, vcr_steady() of k_decode_fp2 in launches of 6;
+// k_decode_fp<false>'s and the TV role's loops are always entered (no width below 16 is accepted).
 // Same execution model as the exact kernels (ntsc_kernels.hip): one lane = one scanline, everything streamed in x,
 // the transposed composite plane comp[x][row] between encoder and decoder (head switching needs random access in x).
 // Same row-start / row-end semantics (filter resets, raw tails of the delayed filters, zero fill) as the reference:
