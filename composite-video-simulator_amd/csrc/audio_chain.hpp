@@ -1,0 +1,255 @@
+// audio_chain.hpp -- the tools' VHS audio chain, composite_audio_process() (ffmpeg_ntsc.cpp:889-970 with the filters of
+// :74-203 and their set-up :2031-2067; ffmpeg_to_composite.cpp:558-627 is the same text), stated once for the kernels
+// (csrc/ntsc_audio.hip), the host checker (tests/audio_chain_check.cpp) and the command line host's fallback
+// (host/vhsaudio_cli.cpp).  No HIP in it.  Built with -ffp-contract=off like everything exact here: every product and
+// every sum below is rounded on its own, in the reference's order.
+//
+// Also here: the PLAN that cuts a call's frames into segments which start early from a zero state, and
+// run / verify / repair over that plan, so that a host program executes what the device executes.
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define AUDIO_HD __host__ __device__ inline
+#else
+#define AUDIO_HD inline
+#endif
+
+namespace ntscsim {
+
+constexpr int AUDIO_PASSES = 6;          // audio_hilopass.setPasses(6) :2035
+constexpr int AUDIO_STATE_VALUES = 30;   // 2 * 12 band-pass, 2 pre, 2 post, 2 boost
+constexpr int AUDIO_OVERSAMPLE = 16;     // :927
+
+// what the chain reads of the tool's globals, with every alpha computed by the host (audio_alpha())
+struct AudioCfg {
+    int enabled;                         // enable_audio_emulation :799 (-nocomp clears it: a copy that draws nothing)
+    int channels;                        // output_audio_channels
+    int hifi;                            // output_vhs_hifi
+    int pre, post;                       // emulating_preemphasis / emulating_deemphasis
+    int hiss_level;                      // output_audio_hiss_level :1267
+    int vsync_lines, vpulse_end;         // :905-906
+    double rate;                         // output_audio_rate
+    double highpass_hz;                  // the slowest pole: sets the default warm-up
+    double hsync_hz, hpulse_end;         // :904, :907
+    double buzz;                         // dBFS(output_audio_linear_buzz) :903
+    double boost_gain;                   // vhs_linear_high_boost
+    double a_lo, a_hi, a_pre, a_post, a_boost;
+};
+
+// v[c*12 + i]: low-pass i of channel c, v[c*12 + 6 + i]: its high-pass; v[24 + i]: pre-emphasis filter i, v[26 + i]:
+// de-emphasis filter i (both shared by the channels), v[28 + c]: boost of channel c.  count: audio_proc_count :889
+struct AudioState {
+    double v[AUDIO_STATE_VALUES];
+    uint64_t count;
+};
+
+// LowpassFilter::setFilter :78-86
+inline double audio_alpha(double rate, double hz)
+{
+    const double timeInterval = 1.0 / rate;
+    const double tau = 1 / (hz * 2 * 3.14159265358979323846);
+    return timeInterval / (tau + timeInterval);
+}
+
+// LowpassFilter::lowpass :90-94 -- highpass :95-99 is x minus this
+AUDIO_HD double audio_pole(double &prev, double x, double alpha)
+{
+    const double stage1 = x * alpha;
+    const double stage2 = prev - (prev * alpha);
+    return (prev = (stage1 + stage2));
+}
+
+AUDIO_HD bool audio_buzz_on(const AudioCfg &c) { return !c.hifi && c.buzz > 0.000000001; }
+AUDIO_HD bool audio_boost_on(const AudioCfg &c) { return !c.hifi && c.boost_gain > 0; }
+
+// How many of the 16 oversample points of frame `count` lie in a sync pulse (:927-941).  fmod(t, 1.0) of a t >= 0 is
+// t - floor(t), exactly; floor(...) is a whole number >= 0, so its fmod by vsync_lines / 2.0 is half the remainder of
+// twice it by vsync_lines, and the (int) of that drops the half.
+AUDIO_HD int audio_pulse_count(const AudioCfg &c, uint64_t count)
+{
+    int n = 0;
+    for (int oi = 0; oi < AUDIO_OVERSAMPLE; oi++) {
+        const double t = ((((double)count * AUDIO_OVERSAMPLE) + oi) * c.hsync_hz) / c.rate / AUDIO_OVERSAMPLE;
+        const double whole = (double)(uint64_t)t;
+        const double hpos = t - whole;
+        const double line = (double)(uint64_t)(t + 0.0001 - hpos);       // floor of a value >= 0
+        const int vline = (int)((((uint64_t)line * 2u) % (uint64_t)c.vsync_lines) >> 1);
+        if (hpos < c.hpulse_end || vline < c.vpulse_end) n++;
+    }
+    return n;
+}
+
+// the numerator of the hiss term :952 for the draw r
+AUDIO_HD int audio_hiss_num(uint32_t r, int level) { return (int)(r % (uint32_t)((level * 2) + 1)) - level; }
+
+AUDIO_HD int audio_clips16(int x) { return x < -32768 ? -32768 : (x > 32767 ? 32767 : x); }
+
+// (int)(s * 32768) of :965 is undefined in C++ outside int's range; the chain cannot leave it while the boost gain is
+// sane, and a gain that makes it do so saturates here as x86's conversion followed by clips16 would not -- stated, not
+// reproduced
+AUDIO_HD int16_t audio_pack(double s)
+{
+    const double v = s * 32768;
+    if (!(v > -2147483648.0)) return -32768;
+    if (!(v < 2147483647.0)) return 32767;
+    return (int16_t)audio_clips16((int)v);
+}
+
+// One channel-sample: `in` of channel ch through the chain.  hiss: the numerator of this channel-sample's draw (read
+// only when hiss_level != 0); pulses: audio_pulse_count() of this frame (read only when the buzz is on).
+AUDIO_HD int16_t audio_sample(const AudioCfg &c, AudioState &st, int ch, int16_t in, int hiss, int pulses)
+{
+    double s = (double)in / 32768;
+    double *bp = st.v + ch * 12;
+    for (int i = 0; i < AUDIO_PASSES; i++) s = audio_pole(bp[i], s, c.a_lo);
+    for (int i = 0; i < AUDIO_PASSES; i++) s = s - audio_pole(bp[6 + i], s, c.a_hi);
+    if (c.pre)
+        for (int i = 0; i < c.channels; i++) s = s + (s - audio_pole(st.v[24 + i], s, c.a_pre));
+    if (audio_buzz_on(c)) {
+        const double q = c.buzz / AUDIO_OVERSAMPLE / 2;
+        for (int k = 0; k < pulses; k++) s -= q;
+    }
+    if (s > 1.0) s = 1.0;
+    else if (s < -1.0) s = -1.0;
+    if (c.hiss_level != 0) s += ((double)hiss) / 20000;
+    if (audio_boost_on(c)) s += (s - audio_pole(st.v[28 + ch], s, c.a_boost)) * c.boost_gain;
+    if (c.post)
+        for (int i = 0; i < c.channels; i++) s = audio_pole(st.v[26 + i], s, c.a_post);
+    return audio_pack(s);
+}
+
+// composite_audio_process(audio, frames) from src to dst (dst may be src).  draw(): the next rand(), called once per
+// channel-sample when hiss_level != 0 and never otherwise.
+template <class Draw>
+inline void audio_run_serial(const AudioCfg &c, AudioState &st, const int16_t *src, int16_t *dst, uint64_t frames, Draw &&draw)
+{
+    if (!c.enabled) {
+        if (dst != src) std::memmove(dst, src, (size_t)frames * (size_t)c.channels * sizeof(int16_t));
+        return;
+    }
+    const bool buzz = audio_buzz_on(c);
+    for (uint64_t f = 0; f < frames; f++) {
+        const int pulses = buzz ? audio_pulse_count(c, st.count) : 0;
+        for (int ch = 0; ch < c.channels; ch++) {
+            const int h = c.hiss_level != 0 ? audio_hiss_num(draw(), c.hiss_level) : 0;
+            dst[f * c.channels + ch] = audio_sample(c, st, ch, src[f * c.channels + ch], h, pulses);
+        }
+        st.count++;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the plan
+// Segment j owns frames [j * L, min((j + 1) * L, total)) of the call and starts running W frames earlier, at
+// max(0, start - W).  One whose run starts at frame 0 starts from the carried, true state and is exact by construction;
+// every other starts from zeros in the values the chain updates (audio_spec_state()) and is checked afterwards.
+
+// 72 tau of the slowest pole, up to a multiple of 64: 25,280 frames at 20 Hz, 5,056 at 100 Hz
+inline uint32_t audio_default_warmup(const AudioCfg &c)
+{
+    const double tau = c.rate / (2 * 3.14159265358979323846 * c.highpass_hz);
+    const uint64_t w = (uint64_t)(72.0 * tau) + 1;
+    return (uint32_t)((w + 63) / 64 * 64);
+}
+constexpr uint32_t AUDIO_DEFAULT_SEG = 4096;
+
+struct AudioSeg {
+    uint64_t start, len, run_start;      // frames of the call
+};
+AUDIO_HD uint64_t audio_seg_count(uint64_t total, uint32_t L) { return (total + L - 1) / L; }
+AUDIO_HD AudioSeg audio_seg(uint64_t total, uint32_t L, uint32_t W, uint64_t j)
+{
+    AudioSeg s;
+    s.start = j * (uint64_t)L;
+    s.len = total - s.start < L ? total - s.start : L;
+    s.run_start = s.start > W ? s.start - W : 0;
+    return s;
+}
+
+// does the chain update value i of the state?
+AUDIO_HD bool audio_value_live(const AudioCfg &c, int i)
+{
+    if (i < 24) return i / 12 < c.channels;
+    if (i < 26) return c.pre && i - 24 < c.channels;
+    if (i < 28) return c.post && i - 26 < c.channels;
+    return audio_boost_on(c) && i - 28 < c.channels;
+}
+
+// the state a speculative segment starts from: zeros where the chain writes, the carried values where it does not
+AUDIO_HD AudioState audio_spec_state(const AudioCfg &c, const AudioState &carried, uint64_t run_start)
+{
+    AudioState s = carried;
+    for (int i = 0; i < AUDIO_STATE_VALUES; i++)
+        if (audio_value_live(c, i)) s.v[i] = 0;
+    s.count = carried.count + run_start;
+    return s;
+}
+
+AUDIO_HD bool audio_state_same(const AudioState &a, const AudioState &b)
+{
+    if (a.count != b.count) return false;
+    for (int i = 0; i < AUDIO_STATE_VALUES; i++) {
+        uint64_t x, y;
+        memcpy(&x, &a.v[i], 8);
+        memcpy(&y, &b.v[i], 8);
+        if (x != y) return false;
+    }
+    return true;
+}
+
+struct AudioPlanStats {
+    uint64_t segments, repaired;
+    uint64_t worst_convergence;          // host only: most frames a speculative run needed to meet the true states
+};
+
+// frames [first, first + n) of the call from state st; hiss: numerators of the whole call (NULL: no hiss)
+inline void audio_run_span(const AudioCfg &c, AudioState &st, const int16_t *src, int16_t *dst, const int32_t *hiss, uint64_t first, uint64_t n)
+{
+    const bool buzz = audio_buzz_on(c);
+    for (uint64_t f = first; f < first + n; f++) {
+        const int pulses = buzz ? audio_pulse_count(c, st.count) : 0;
+        for (int ch = 0; ch < c.channels; ch++) {
+            const int16_t o = audio_sample(c, st, ch, src[f * c.channels + ch], hiss ? hiss[f * c.channels + ch] : 0, pulses);
+            if (dst) dst[f * c.channels + ch] = o;
+        }
+        st.count++;
+    }
+}
+
+// Run, verify, repair: what k_audio_segments and k_audio_verify_repair do, in their order.  dst must not overlap src.
+inline void audio_run_planned(const AudioCfg &c, AudioState &st, const int16_t *src, int16_t *dst, const int32_t *hiss, uint64_t total, uint32_t L,
+                              uint32_t W, AudioPlanStats *stats)
+{
+    if (stats) stats->segments = stats->repaired = stats->worst_convergence = 0;
+    if (!c.enabled) {
+        std::memcpy(dst, src, (size_t)total * (size_t)c.channels * sizeof(int16_t));
+        return;
+    }
+    if (L == 0) L = 1;
+    const uint64_t nseg = audio_seg_count(total, L);
+    std::vector<AudioState> at_start((size_t)nseg), at_end((size_t)nseg);
+    for (uint64_t j = 0; j < nseg; j++) {                                       // the speculative pass
+        const AudioSeg g = audio_seg(total, L, W, j);
+        AudioState s = g.run_start == 0 ? st : audio_spec_state(c, st, g.run_start);
+        audio_run_span(c, s, src, nullptr, hiss, g.run_start, g.start - g.run_start);
+        at_start[(size_t)j] = s;
+        audio_run_span(c, s, src, dst, hiss, g.start, g.len);
+        at_end[(size_t)j] = s;
+    }
+    AudioState truth = st;
+    for (uint64_t j = 0; j < nseg; j++) {                                       // verify, repair
+        const AudioSeg g = audio_seg(total, L, W, j);
+        if (!audio_state_same(at_start[(size_t)j], truth)) {
+            audio_run_span(c, truth, src, dst, hiss, g.start, g.len);
+            if (stats) stats->repaired++;
+        } else {
+            truth = at_end[(size_t)j];
+        }
+    }
+    st = truth;
+    if (stats) stats->segments = nseg;
+}
+
+} // namespace ntscsim

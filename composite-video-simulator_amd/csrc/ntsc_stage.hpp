@@ -1,5 +1,5 @@
 // ntsc_stage.hpp -- the host scaffold of the device stages that are translation units of their own (frameblend:
-// csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip, filmac: csrc/ntsc_filmac.hip, posterize and colormap: csrc/ntsc_pixmap.hip): what they see of an ntscsim_ctx,
+// csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip, filmac: csrc/ntsc_filmac.hip, posterize and colormap: csrc/ntsc_pixmap.hip, the audio chain: csrc/ntsc_audio.hip): what they see of an ntscsim_ctx,
 // whose definition stays private to ntscsim_hip.hip, the pinned record slots their launches go up through, and the
 // arena their *_frames_host() calls copy host frames through.  The host logic without HIP in it: ntsc_frames.hpp (every
 // stage's); what only the two layer stages share: ntsc_layer.hpp (no HIP in it either) and ntsc_layer_frames.hpp.
@@ -22,6 +22,7 @@ struct LedState;                         // ntsc_led.hip: bound params, record s
 struct FilmacState;                      // ntsc_filmac.hip: bound params, gamma tables, level state, record slots, scratch, host-frame arena
 struct PostState;                        // ntsc_pixmap.hip: bound size, the inputs' masks, record slots, host-frame arena
 struct CmapState;                        // ntsc_pixmap.hip: bound size, the colour table, record slots, host-frame arena
+struct AudioStageState;                  // ntsc_audio.hip: bound params, carried chain state, draw polynomials, scratch, record slots, staging
 
 struct CtxStageView {
     int device;
@@ -36,6 +37,7 @@ struct CtxStageView {
     FilmacState **filmac;
     PostState **post;
     CmapState **cmap;
+    AudioStageState **audio;
 };
 CtxStageView ctx_stage_view(ntscsim_ctx *c);     // ntscsim_hip.hip
 void blend_state_destroy(BlendState *b);         // ntsc_blend.hip
@@ -46,6 +48,7 @@ void led_state_destroy(LedState *k);             // ntsc_led.hip
 void filmac_state_destroy(FilmacState *k);       // ntsc_filmac.hip
 void post_state_destroy(PostState *k);           // ntsc_pixmap.hip
 void cmap_state_destroy(CmapState *k);           // ntsc_pixmap.hip
+void audio_state_destroy(AudioStageState *k);    // ntsc_audio.hip
 // ntscsim_debug_last_kernels(): "k_scan_splat" becomes "k_scan_splat+spill" if a workgroup of the last call spilled
 void scan_kernels_tap(ScanState *k, int device, std::string &kernels);   // ntsc_scan.hip
 

@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "AutoContrast", "Posterizer", "ColorMapper", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "AutoContrast", "AudioChain", "Posterizer", "ColorMapper", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -941,6 +941,130 @@ class AutoContrast:
 
     def last_kernels(self):
         return self.sim.last_kernels()
+
+    def sync(self):
+        self.sim.sync()
+
+
+class AudioChain:
+    """The VHS audio chain of ffmpeg_ntsc / ffmpeg_to_composite (ntscsim_audio_*): composite_audio_process() on
+    interleaved int16, bit-identical to the tool, the hiss draws included.  params: ntscsim_audio_params
+    (_capi.make_audio_params(flags)[0]) or None with `flags` / `tool`.  sim: share the context -- and with it the
+    rand() position -- of a FieldSimulator; otherwise a context of its own is created.  The filter states and the
+    sample count live on the device and carry from block to block and from call to call; calls must be ordered by the
+    caller (one stream)."""
+
+    def __init__(self, params=None, cli=None, device=0, flags=(), tool="ntsc", sim=None):
+        if params is None:
+            params = _capi.make_audio_params(flags, tool)[0]
+        elif not isinstance(params, _capi.AudioParams):                         # (ntscsim_params, ntscsim_cli)
+            ap = _capi.AudioParams()
+            rc = _capi.lib().ntscsim_audio_params_from_cli(C.byref(ap), C.byref(params), C.byref(cli))
+            if rc != _capi.OK:
+                raise NtscsimError(rc, "ntscsim_audio_params_from_cli")
+            params = ap
+        self.params = params
+        self.channels = int(params.channels)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        try:
+            self._call("bind", C.byref(self.params))
+        except Exception:
+            self.close()
+            raise
+
+    def _call(self, what, *args):
+        name = "ntscsim_audio_%s" % what
+        self.sim._chk(getattr(self._lib, name)(self.sim._h, *args), name)
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    def process(self, src, dst, blocks=None, stream=None):
+        """ntscsim_audio_device: src, dst are torch int16 CUDA tensors [frames, channels] (or flat), contiguous.
+        blocks: [(frames, rng_pos or None), ...] cutting them into the call's descriptors in order (None: one block at
+        the ctx's rand() position).  Enqueues; does not synchronise."""
+        ch = self.channels
+        total = src.numel() // ch
+        assert src.is_contiguous() and dst.is_contiguous() and dst.numel() == src.numel()
+        if blocks is None:
+            blocks = [(total, None)]
+        assert sum(b[0] for b in blocks) == total
+        arr = (_capi.AudioDesc * max(1, len(blocks)))()
+        at = 0
+        for d, (frames, pos) in zip(arr, blocks):
+            d.src = src.data_ptr() + at * ch * 2
+            d.dst = dst.data_ptr() + at * ch * 2
+            d.samples = int(frames)
+            d.rng_pos = RNG_AUTO if pos is None else int(pos)
+            at += int(frames)
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("device", arr, len(blocks), C.c_void_p(stream))
+
+    def host(self, array):
+        """ntscsim_audio_host: composite_audio_process(array, frames) in place on a numpy int16 array whose samples
+        are contiguous (any alignment).  Synchronous."""
+        assert array.dtype.str in ("<i2", "=i2") and array.flags["C_CONTIGUOUS"] and array.flags["WRITEABLE"]
+        self._call("host", C.c_void_p(array.ctypes.data), array.size // self.channels)
+
+    def reset(self):
+        self._call("reset")
+
+    @property
+    def state(self):
+        """(30 filter values as a tuple, sample count).  Reading and writing synchronise."""
+        s = _capi.AudioState()
+        self._call("get_state", C.byref(s))
+        v = [x for c in s.bandpass for x in c] + list(s.pre) + list(s.post) + list(s.boost)
+        return tuple(v), int(s.count)
+
+    @state.setter
+    def state(self, value):
+        v, count = value
+        s = _capi.AudioState()
+        for c in range(2):
+            for i in range(12):
+                s.bandpass[c][i] = v[c * 12 + i]
+        for i in range(2):
+            s.pre[i], s.post[i], s.boost[i] = v[24 + i], v[26 + i], v[28 + i]
+        s.count = int(count)
+        self._call("set_state", C.byref(s))
+
+    def set_plan(self, seg_len=0, warmup=0):
+        """ntscsim_audio_debug_set_plan: (0, 0) restores the defaults; otherwise warmup is taken as given."""
+        self._call("debug_set_plan", int(seg_len), int(warmup))
+
+    def default_warmup(self):
+        """72 tau of the high-pass, up to a multiple of 64 (csrc/audio_chain.hpp: audio_default_warmup)."""
+        import math
+        tau = self.params.rate / (2 * math.pi * self.params.highpass_hz)
+        return (int(72.0 * tau) + 1 + 63) // 64 * 64
+
+    def stats(self):
+        """(segments, repaired segments) of the last call.  Synchronises."""
+        s = _capi.AudioStats()
+        self._call("debug_stats", C.byref(s))
+        return int(s.segments), int(s.repaired)
+
+    def pulses(self, count0, n):
+        """The device's sync pulse counts of frames count0 .. count0 + n - 1, as a numpy uint8 array."""
+        import numpy as np
+        out = np.zeros(int(n), np.uint8)
+        self._call("debug_pulses", int(count0), int(n), C.c_void_p(out.ctypes.data))
+        return out
+
+    def debug_time_kernels(self, on=True):
+        self._call("debug_time_kernels", 1 if on else 0)
+
+    def kernel_ms(self):
+        """(draws and pulse counts, k_audio_segments, k_audio_verify_repair) milliseconds of the last call."""
+        out = (C.c_float * 3)()
+        self._call("debug_kernel_ms", out)
+        return tuple(float(v) for v in out)
 
     def sync(self):
         self.sim.sync()

@@ -69,6 +69,9 @@ EXPORTS = (
     "ntscsim_cmap_params_init", "ntscsim_cmap_params_free", "ntscsim_cmap_parse_argv", "ntscsim_cmap_bind",
     "ntscsim_cmap_frames_device", "ntscsim_cmap_frames_host", "ntscsim_cmap_reset", "ntscsim_cmap_get_table",
     "ntscsim_cmap_set_table",
+    "ntscsim_audio_params_from_cli", "ntscsim_audio_bind", "ntscsim_audio_device", "ntscsim_audio_host", "ntscsim_audio_reset",
+    "ntscsim_audio_get_state", "ntscsim_audio_set_state", "ntscsim_audio_debug_set_plan", "ntscsim_audio_debug_stats",
+    "ntscsim_audio_debug_pulses", "ntscsim_audio_debug_time_kernels", "ntscsim_audio_debug_kernel_ms",
 )
 
 
@@ -406,6 +409,43 @@ class CmapDesc(C.Structure):
                 ("map", C.c_void_p), ("map_linesize", C.c_int32), ("_pad2", C.c_int32)]
 
 
+class Cli(C.Structure):
+    """struct ntscsim_cli -- keep in lock-step with include/ntscsim.h."""
+    _fields_ = [("input_paths", C.c_char_p * 16), ("n_inputs", C.c_int32), ("frame_delay", C.c_int32),
+                ("output_path", C.c_char_p), ("use_422_colorspace", C.c_int32),
+                ("emulating_preemphasis", C.c_int32), ("emulating_deemphasis", C.c_int32), ("output_vhs_hifi", C.c_int32),
+                ("output_audio_hiss_db", C.c_double), ("output_audio_linear_buzz", C.c_double),
+                ("vhs_linear_high_boost", C.c_double), ("output_video_as_interlaced", C.c_int32), ("_pad", C.c_int32)]
+
+
+class AudioParams(C.Structure):
+    """struct ntscsim_audio_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_int32), ("channels", C.c_int32), ("rate", C.c_int32),
+                ("passes", C.c_int32), ("hifi", C.c_int32), ("preemphasis", C.c_int32), ("deemphasis", C.c_int32),
+                ("hiss_level", C.c_int32), ("tv_standard", C.c_int32), ("vsync_lines", C.c_int32), ("vpulse_end", C.c_int32),
+                ("lowpass_hz", C.c_double), ("highpass_hz", C.c_double), ("emphasis_hz", C.c_double), ("boost_hz", C.c_double),
+                ("hsync_hz", C.c_double), ("hpulse_end", C.c_double), ("buzz", C.c_double), ("boost_gain", C.c_double),
+                ("alpha_lowpass", C.c_double), ("alpha_highpass", C.c_double), ("alpha_pre", C.c_double),
+                ("alpha_post", C.c_double), ("alpha_boost", C.c_double)]
+
+
+class AudioState(C.Structure):
+    """struct ntscsim_audio_state"""
+    _fields_ = [("bandpass", (C.c_double * 12) * 2), ("pre", C.c_double * 2), ("post", C.c_double * 2),
+                ("boost", C.c_double * 2), ("count", C.c_uint64)]
+
+
+class AudioDesc(C.Structure):
+    """struct ntscsim_audio_desc"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("samples", C.c_uint32), ("_pad", C.c_uint32),
+                ("rng_pos", C.c_uint64)]
+
+
+class AudioStats(C.Structure):
+    """struct ntscsim_audio_stats"""
+    _fields_ = [("segments", C.c_uint64), ("repaired", C.c_uint64)]
+
+
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
 
@@ -738,6 +778,30 @@ def lib():
     L.ntscsim_filmac_debug_time_kernels.restype = C.c_int
     L.ntscsim_filmac_debug_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.ntscsim_filmac_debug_kernel_ms.restype = C.c_int
+    L.ntscsim_audio_params_from_cli.argtypes = [C.POINTER(AudioParams), C.POINTER(Params), C.POINTER(Cli)]
+    L.ntscsim_audio_params_from_cli.restype = C.c_int
+    L.ntscsim_audio_bind.argtypes = [C.c_void_p, C.POINTER(AudioParams)]
+    L.ntscsim_audio_bind.restype = C.c_int
+    L.ntscsim_audio_device.argtypes = [C.c_void_p, C.POINTER(AudioDesc), C.c_int, C.c_void_p]
+    L.ntscsim_audio_device.restype = C.c_int
+    L.ntscsim_audio_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ntscsim_audio_host.restype = C.c_int
+    L.ntscsim_audio_reset.argtypes = [C.c_void_p]
+    L.ntscsim_audio_reset.restype = C.c_int
+    L.ntscsim_audio_get_state.argtypes = [C.c_void_p, C.POINTER(AudioState)]
+    L.ntscsim_audio_get_state.restype = C.c_int
+    L.ntscsim_audio_set_state.argtypes = [C.c_void_p, C.POINTER(AudioState)]
+    L.ntscsim_audio_set_state.restype = C.c_int
+    L.ntscsim_audio_debug_set_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    L.ntscsim_audio_debug_set_plan.restype = C.c_int
+    L.ntscsim_audio_debug_stats.argtypes = [C.c_void_p, C.POINTER(AudioStats)]
+    L.ntscsim_audio_debug_stats.restype = C.c_int
+    L.ntscsim_audio_debug_pulses.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+    L.ntscsim_audio_debug_pulses.restype = C.c_int
+    L.ntscsim_audio_debug_time_kernels.argtypes = [C.c_void_p, C.c_int]
+    L.ntscsim_audio_debug_time_kernels.restype = C.c_int
+    L.ntscsim_audio_debug_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.ntscsim_audio_debug_kernel_ms.restype = C.c_int
     L.ntscsim_pixmap_params_init.argtypes = [C.POINTER(PixmapParams)]
     L.ntscsim_pixmap_params_init.restype = None
     L.ntscsim_pixmap_params_free.argtypes = [C.POINTER(PixmapParams)]
@@ -807,6 +871,26 @@ def make_params(flags=(), **overrides):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def make_audio_params(flags=(), tool="ntsc"):
+    """(ntscsim_audio_params, ntscsim_params) from the switches of ffmpeg_ntsc (tool="ntsc") or ffmpeg_to_composite
+    (tool="to_composite"): the parser's record, then ntscsim_audio_params_from_cli()."""
+    L = lib()
+    p, cli, ap = Params(), Cli(), AudioParams()
+    L.ntscsim_cli_init(C.byref(cli))
+    sibling = tool == "to_composite"
+    (L.ntscsim_params_init_to_composite if sibling else L.ntscsim_params_init)(C.byref(p))
+    argv = [b"ffmpeg_to_composite" if sibling else b"ffmpeg_ntsc"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    parse = L.ntscsim_params_parse_argv_to_composite if sibling else L.ntscsim_params_parse_argv
+    rc = parse(C.byref(p), C.cast(C.byref(cli), C.c_void_p), len(argv), arr, 0)
+    if rc != OK:
+        raise NtscsimError(rc, "parse_argv(%r)" % (list(flags),))
+    rc = L.ntscsim_audio_params_from_cli(C.byref(ap), C.byref(p), C.byref(cli))
+    if rc != OK:
+        raise NtscsimError(rc, "ntscsim_audio_params_from_cli")
+    return ap, p
 
 
 def make_raw28_opts(flags=()):

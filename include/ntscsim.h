@@ -1612,6 +1612,97 @@ int  ntscsim_cmap_reset(ntscsim_ctx *ctx);
 int  ntscsim_cmap_get_table(ntscsim_ctx *ctx, uint32_t out[256]);
 int  ntscsim_cmap_set_table(ntscsim_ctx *ctx, const uint32_t in[256]);
 
+/* ------------------------------------------------------------------------------------------
+ * The VHS audio chain of ffmpeg_ntsc and ffmpeg_to_composite as a device stage: composite_audio_process()
+ * (ffmpeg_ntsc.cpp:889-970, filters :74-203, set-up :2031-2067; the sibling's :558-627 and :2126-2162 are the same
+ * text).  Interleaved int16 in and out, bit-identical to the tool, the rand() draws of the hiss included: they come
+ * from the ctx's stream position, which the call advances as the field calls do, so that fields and audio blocks
+ * called in the tool's order reproduce the tool's stream.  DESIGN.md 7l.
+ */
+typedef struct ntscsim_audio_params {
+    uint32_t struct_size;          /* sizeof(ntscsim_audio_params)                                              */
+    int32_t  enabled;              /* enable_audio_emulation :799; 0 (-nocomp): a copy that draws nothing        */
+    int32_t  channels;             /* output_audio_channels :1229-1262                                          */
+    int32_t  rate;                 /* output_audio_rate :212  44100                                             */
+    int32_t  passes;               /* :2035  6 (the only value the stage runs)                                   */
+    int32_t  hifi;                 /* output_vhs_hifi                                                           */
+    int32_t  preemphasis;          /* emulating_preemphasis                                                     */
+    int32_t  deemphasis;           /* emulating_deemphasis                                                      */
+    int32_t  hiss_level;           /* (int)(dBFS(output_audio_hiss_db) * 5000) :1267                            */
+    int32_t  tv_standard;          /* NTSCSIM_TV_NTSC / NTSCSIM_TV_PAL                                          */
+    int32_t  vsync_lines;          /* :905  525 / 625                                                           */
+    int32_t  vpulse_end;           /* :906  10 / 12                                                             */
+    double   lowpass_hz;           /* output_audio_lowpass                                                      */
+    double   highpass_hz;          /* output_audio_highpass                                                     */
+    double   emphasis_hz;          /* :2047 / :2052  16000 (Hi-Fi) or 8000 (linear)                             */
+    double   boost_hz;             /* :2040  10000                                                              */
+    double   hsync_hz;             /* :904  15734 / 15625                                                       */
+    double   hpulse_end;           /* :907  hsync_hz * (4.7 or 4.0 us)                                          */
+    double   buzz;                 /* dBFS(output_audio_linear_buzz) :903, libm pow on the host                  */
+    double   boost_gain;           /* vhs_linear_high_boost                                                     */
+    double   alpha_lowpass, alpha_highpass, alpha_pre, alpha_post, alpha_boost; /* LowpassFilter::setFilter :78  */
+} ntscsim_audio_params;
+/* From what the two parsers record: the post-parse derivation :1229-1267 and the set-up :2031-2067.  `cli` is the one
+ * the parser filled next to `p` (either tool's).  NTSCSIM_E_ARG for a NULL pointer or a wrong struct_size of p. */
+int  ntscsim_audio_params_from_cli(ntscsim_audio_params *ap, const ntscsim_params *p, const ntscsim_cli *cli);
+
+typedef struct ntscsim_audio_state {
+    double   bandpass[2][12];      /* per channel: the six low-pass states, then the six high-pass states        */
+    double   pre[2], post[2];      /* audio_linear_preemphasis_pre / _post: SHARED by the channels (:920, :960)  */
+    double   boost[2];             /* audio_post_vhs_boost, per channel                                         */
+    uint64_t count;                /* audio_proc_count :889                                                     */
+} ntscsim_audio_state;
+
+typedef struct ntscsim_audio_desc {
+    const int16_t *src;            /* device pointer, `samples` frames of `channels` interleaved int16           */
+    int16_t       *dst;
+    uint32_t       samples;        /* sample frames, as composite_audio_process()'s second argument; 0 allowed   */
+    uint32_t       _pad;
+    uint64_t       rng_pos;        /* rand() position of the block's first draw, or NTSCSIM_RNG_AUTO             */
+} ntscsim_audio_desc;
+
+typedef struct ntscsim_audio_stats {
+    uint64_t segments;             /* of the last call                                                          */
+    uint64_t repaired;             /* segments of it that k_audio_verify_repair ran again                        */
+} ntscsim_audio_stats;
+
+/* Snapshot the parameters and reset the state (zeros, count 0).  Waits for audio work in flight.
+ * NTSCSIM_E_PARAM: channels outside 1..2, passes != 6, a rate or cut-off <= 0. */
+int  ntscsim_audio_bind(ntscsim_ctx *ctx, const ntscsim_audio_params *ap);
+/*
+ * The n blocks are ONE continuous stream, in order: filter states and the sample count run through them (and on into
+ * the next call).  Each block has its own rand() position, because the tool's audio packets interleave with its
+ * fields; NTSCSIM_RNG_AUTO continues from the ctx's position.  The ctx's position moves at call time, by
+ * samples * channels per block when hiss_level != 0.  Pointers are DEVICE pointers; `descs` is host memory and is
+ * consumed by the call.  Enqueued on hip_stream (NULL: the ctx's own stream), returns without synchronising.
+ * Kernels: k_audio_hiss (the draws, by jump-ahead, when hiss_level != 0), k_audio_pulses (sync pulse counts, when the
+ * buzz is on), k_audio_segments (segments of the stream run speculatively from a zero state one warm-up early, each by
+ * a group of 21 adjacent lanes, one lane per stage of the chain), k_audio_verify_repair (one workgroup: compares each
+ * segment's recorded start state bitwise with its predecessor's true end state, runs it again where they differ,
+ * writes the ctx's state).  The result never depends on the plan.  Calls on one ctx must be ordered by the caller (one
+ * stream, or events between streams): they share the ctx's state and scratch.
+ * NTSCSIM_E_ARG: no ntscsim_audio_bind() before, a NULL or odd pointer in a block with samples, a dst that overlaps
+ * any src of the call (a warm-up reads input again).
+ */
+int  ntscsim_audio_device(ntscsim_ctx *ctx, const ntscsim_audio_desc *descs, int n, void *hip_stream);
+/* Drop-in for composite_audio_process(audio, samples): HOST memory, in place, through pinned staging of the ctx.
+ * Synchronous.  The rand() position is the ctx's. */
+int  ntscsim_audio_host(ntscsim_ctx *ctx, int16_t *audio, uint32_t samples);
+/* reset: the tool's start.  get / set: a track processed in pieces, or started at any sample count.  All wait for
+ * the device and require ntscsim_audio_bind(). */
+int  ntscsim_audio_reset(ntscsim_ctx *ctx);
+int  ntscsim_audio_get_state(ntscsim_ctx *ctx, ntscsim_audio_state *out);
+int  ntscsim_audio_set_state(ntscsim_ctx *ctx, const ntscsim_audio_state *in);
+/* Debug taps.  set_plan: segment length and warm-up in frames.  (0, 0) restores both defaults (4096 frames; 72 time
+ * constants of the high-pass, up to a multiple of 64); with any other pair the warm-up is taken as given (0: none) and a
+ * seg_len of 0 is the default length.  seg_len >= the call's frames is the serial form.  pulses: the device's pulse counts of frames count0 .. count0+n-1 (host `out`). */
+int  ntscsim_audio_debug_set_plan(ntscsim_ctx *ctx, uint32_t seg_len, uint32_t warmup);
+int  ntscsim_audio_debug_stats(ntscsim_ctx *ctx, ntscsim_audio_stats *out);
+int  ntscsim_audio_debug_pulses(ntscsim_ctx *ctx, uint64_t count0, uint32_t n, uint8_t *out);
+int  ntscsim_audio_debug_time_kernels(ntscsim_ctx *ctx, int on);
+/* (k_audio_hiss + k_audio_pulses, k_audio_segments, k_audio_verify_repair) milliseconds of the last call */
+int  ntscsim_audio_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif
