@@ -1,0 +1,322 @@
+// cass_chain.hpp -- ffmpeg_cassette's tape chain, composite_audio_process() (ffmpeg_cassette.cpp:334-416 with the
+// filters of :80-209, the ConvolutionMap of :278-324 and the set-up :864-880), stated once for the kernels
+// (csrc/ntsc_cass.hip), the host checker (tests/cass_chain_check.cpp) and the command line host's fallback
+// (host/cassette_cli.cpp).  No HIP in it.  Built with -ffp-contract=off: every product and sum is rounded on its own, in
+// the reference's order.  The poles, the hiss numerator, the pack and the segment plan are audio_chain.hpp's.
+//
+// The tool's loop body is FRONT (band-pass, pre-emphasis, clip, hiss) -> a per-sample FIR whose taps follow the head
+// tilt -> BACK (de-emphasis, pack, mono downmix).  The pre-emphasis states are touched by the front alone, the
+// de-emphasis states by the back alone and the FIR has a delay line per channel, so running the three as passes over a
+// call's frames computes what the interleaved loop computes, draw for draw.  DESIGN.md 7m.
+#pragma once
+#include <cmath>
+
+#include "audio_chain.hpp"
+
+namespace ntscsim {
+
+constexpr int CASS_MAX_TAPS = 512;       // enough for |headalign| <= 100: floor(200 + 300 + 7.5) = 507
+constexpr int CASS_HIST = CASS_MAX_TAPS - 1;
+constexpr int CASS_FRONT_VALUES = 26;    // 2 * 12 band-pass, 2 pre
+constexpr int CASS_CHANNELS = 2;         // output_audio_channels: the tool never changes it
+
+struct CassCfg {
+    int pre, post, mono;                 // emulating_preemphasis / emulating_deemphasis / mono_downmix
+    int hiss_level;                      // output_audio_hiss_level :582
+    int taps;                            // audio_conv[].length :338
+    double rate;                         // output_audio_rate
+    double highpass_hz;                  // the slowest pole: sets the front's default warm-up
+    double tilt, waver;                  // head_tilt, head_tilt_waver
+    double a_lo, a_hi, a_pre, a_post;
+};
+
+// v[c*12 + i]: low-pass i of channel c, v[c*12 + 6 + i]: its high-pass; v[24 + i]: pre-emphasis filter i (shared by the
+// channels).  count: audio_proc_count
+struct CassFront {
+    double v[CASS_FRONT_VALUES];
+    uint64_t count;
+};
+struct CassBack {
+    double post[2];                      // de-emphasis filter i (shared by the channels)
+};
+// hist[k][c]: x of frame (next frame - (taps - 1) + k), k < taps - 1: the delay line of ConvolutionMap::calc, oldest
+// first; the entries from taps - 1 on are not read and stay as they are
+struct CassState {
+    CassFront front;
+    CassBack back;
+    uint32_t taps, _pad;
+    double hist[CASS_HIST][CASS_CHANNELS];
+};
+
+// :338 -- (int)floor(fabs(tilt * 2) + fabs(tilt * 3) + 7.5)
+inline int cass_taps(double tilt) { return (int)std::floor(std::fabs(tilt * 2) + std::fabs(tilt * 3) + 7.5); }
+
+// :344-345 -- the argument of the frame's sin(), in the tool's order of operations, and head_tilt_final from its result.
+// sin() itself is libm's, called by the host: cass_fill_tilt().  Nothing else here evaluates it.
+inline double cass_sin_arg(const CassCfg &c, uint64_t count)
+{
+    const double t = (double)count / c.rate;
+    return t * 3.14159265358979323846 * 2 * 1.5;
+}
+inline double cass_tilt_of_sin(const CassCfg &c, double s) { return (c.waver * s) + c.tilt; }
+inline void cass_fill_tilt(const CassCfg &c, uint64_t count0, uint64_t n, double *tf)
+{
+    for (uint64_t i = 0; i < n; i++) tf[i] = cass_tilt_of_sin(c, std::sin(cass_sin_arg(c, count0 + i)));
+}
+
+// ------------------------------------------------------------------------------------------------ front
+// :376-396 of one channel-sample; hiss: the numerator of its draw (read only when hiss_level != 0)
+AUDIO_HD double cass_front_sample(const CassCfg &c, CassFront &st, int ch, int16_t in, int hiss)
+{
+    double s = (double)in / 32768;
+    double *bp = st.v + ch * 12;
+    for (int i = 0; i < AUDIO_PASSES; i++) s = audio_pole(bp[i], s, c.a_lo);
+    for (int i = 0; i < AUDIO_PASSES; i++) s = s - audio_pole(bp[6 + i], s, c.a_hi);
+    if (c.pre)
+        for (int i = 0; i < CASS_CHANNELS; i++) s = s + (s - audio_pole(st.v[24 + i], s, c.a_pre));
+    if (s > 1.0) s = 1.0;
+    else if (s < -1.0) s = -1.0;
+    if (c.hiss_level != 0) s += ((double)hiss) / 20000;
+    return s;
+}
+
+// ------------------------------------------------------------------------------------------------ taps, FIR
+// :349-357 / :361-369 -- tap i of channel ch at head_tilt_final tf.  Both divisions stay divisions.
+AUDIO_HD double cass_tap(int taps, double tf, int ch, int i)
+{
+    const double lr = tf * 1.5;
+    const double inv = fabs(tf) + 1.0;
+    const double mid = (ch ? -lr : lr) + ((double)taps / 2);
+    double d = ((double)i - mid) / inv;
+    d = 1.0 - fabs(d);
+    if (d < 0) d = 0;
+    d /= inv;
+    return d;
+}
+
+// The taps that can be other than zero lie in [lo, hi): |i - mid| >= inv + 1 gives |(i - mid) / inv| >= 1 + 1 / inv,
+// which no rounding of the subtraction and the division brings down to 1, so d < 0 there and the tap is +0.  The
+// bounds leave that whole frame of slack and are clamped in double before the conversion.
+AUDIO_HD void cass_tap_range(int taps, double tf, int ch, int &lo, int &hi)
+{
+    const double lr = tf * 1.5;
+    const double inv = fabs(tf) + 1.0;
+    const double mid = (ch ? -lr : lr) + ((double)taps / 2);
+    double a = mid - inv - 2.0, b = mid + inv + 3.0;
+    if (!(a > 0)) a = 0;
+    if (!(b < (double)taps)) b = (double)taps;
+    if (!(a < (double)taps)) a = (double)taps;
+    if (!(b > 0)) b = 0;
+    lo = (int)a;
+    hi = (int)b;
+    if (hi < lo) hi = lo;
+}
+
+// ConvolutionMap::calc :308-319 for the frame whose own x is w[(taps - 1) * stride]: w[i * stride] is map[i], oldest
+// first.  Skip: products with a tap of +0 are left out.  That changes no bit: r starts at +0, a tap is never negative, x
+// is finite (the clip, then a hiss term of at most 0.5), so a skipped product is +0 or -0; +0 + (+-0) = +0, and a sum
+// of finite doubles is -0 only if both terms are, which r never is -- so r is the same double with and without them.
+// The checker runs Skip = false, every tap; the kernels run Skip = true and are tested against it.
+template <bool Skip>
+AUDIO_HD double cass_conv(int taps, double tf, int ch, const double *w, int stride)
+{
+    double r = 0;
+    int lo = 0, hi = taps;
+    if (Skip) cass_tap_range(taps, tf, ch, lo, hi);
+    for (int i = lo; i < hi; i++) {
+        const double d = cass_tap(taps, tf, ch, i);
+        if (Skip && d == 0) continue;
+        r += w[i * stride] * d;
+    }
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------ back
+// :402-408 of one channel-sample
+AUDIO_HD int16_t cass_back_sample(const CassCfg &c, CassBack &st, double r)
+{
+    if (c.post)
+        for (int i = 0; i < CASS_CHANNELS; i++) r = audio_pole(st.post[i], r, c.a_post);
+    return audio_pack(r);
+}
+// :411-412 -- the int division truncates toward zero
+AUDIO_HD void cass_downmix(const CassCfg &c, int16_t &o0, int16_t &o1)
+{
+    if (c.mono) o0 = o1 = (int16_t)(((int)o0 + (int)o1) / 2);
+}
+
+// ------------------------------------------------------------------------------------------------ serial
+// Frames [first, first + n) of the call through the front, from state st.  xs (NULL: states only): the call's plane of
+// x behind its taps - 1 frames of history, xs[(taps - 1 + f) * 2 + c].  hiss: numerators of the whole call (NULL: none)
+inline void cass_front_span(const CassCfg &c, CassFront &st, const int16_t *src, double *xs, const int32_t *hiss, uint64_t first, uint64_t n)
+{
+    for (uint64_t f = first; f < first + n; f++) {
+        for (int ch = 0; ch < CASS_CHANNELS; ch++) {
+            const double x = cass_front_sample(c, st, ch, src[f * 2 + ch], hiss ? hiss[f * 2 + ch] : 0);
+            if (xs) xs[((uint64_t)(c.taps - 1) + f) * 2 + ch] = x;
+        }
+        st.count++;
+    }
+}
+
+// the FIR of frames [first, first + n): rs[f * 2 + c]
+template <bool Skip>
+inline void cass_conv_span(const CassCfg &c, const double *xs, const double *tf, double *rs, uint64_t first, uint64_t n)
+{
+    for (uint64_t f = first; f < first + n; f++)
+        for (int ch = 0; ch < CASS_CHANNELS; ch++) rs[f * 2 + ch] = cass_conv<Skip>(c.taps, tf[f], ch, xs + f * 2 + ch, 2);
+}
+
+// frames [first, first + n) through the back, from state st; dst NULL: states only
+inline void cass_back_span(const CassCfg &c, CassBack &st, const double *rs, int16_t *dst, uint64_t first, uint64_t n)
+{
+    for (uint64_t f = first; f < first + n; f++) {
+        int16_t o0 = cass_back_sample(c, st, rs[f * 2]);
+        int16_t o1 = cass_back_sample(c, st, rs[f * 2 + 1]);
+        cass_downmix(c, o0, o1);
+        if (dst) { dst[f * 2] = o0; dst[f * 2 + 1] = o1; }
+    }
+}
+
+// the plane of x of a call: the carried history in front, room for `total` frames behind it
+inline void cass_plane_begin(const CassCfg &c, const CassState &st, std::vector<double> &xs, uint64_t total)
+{
+    const size_t h = (size_t)(c.taps - 1);
+    xs.assign((h + (size_t)total) * 2, 0.0);
+    for (size_t k = 0; k < h; k++)
+        for (int ch = 0; ch < CASS_CHANNELS; ch++) xs[k * 2 + ch] = st.hist[k][ch];
+}
+// the call's last taps - 1 values of x become the history (a call shorter than that keeps part of the old one)
+inline void cass_plane_end(const CassCfg &c, CassState &st, const std::vector<double> &xs, uint64_t total)
+{
+    const size_t h = (size_t)(c.taps - 1);
+    for (size_t k = 0; k < h; k++)
+        for (int ch = 0; ch < CASS_CHANNELS; ch++) st.hist[k][ch] = xs[((size_t)total + k) * 2 + ch];
+}
+
+// composite_audio_process(audio, frames) from src to dst (dst may be src).  tf: head_tilt_final of each frame
+// (cass_fill_tilt(c, st.front.count, frames, tf), or built from recorded sines).  draw(): the next rand(), called once
+// per channel-sample when hiss_level != 0, in the tool's order.  Every tap is run.
+template <class Draw>
+inline void cass_run_serial(const CassCfg &c, CassState &st, const int16_t *src, int16_t *dst, uint64_t frames, const double *tf, Draw &&draw)
+{
+    std::vector<double> xs, rs((size_t)frames * 2);
+    std::vector<int32_t> hiss;
+    if (c.hiss_level != 0) {
+        hiss.resize((size_t)frames * 2);
+        for (int32_t &h : hiss) h = audio_hiss_num(draw(), c.hiss_level);
+    }
+    cass_plane_begin(c, st, xs, frames);
+    cass_front_span(c, st.front, src, xs.data(), hiss.empty() ? nullptr : hiss.data(), 0, frames);
+    cass_conv_span<false>(c, xs.data(), tf, rs.data(), 0, frames);
+    cass_back_span(c, st.back, rs.data(), dst, 0, frames);
+    cass_plane_end(c, st, xs, frames);
+}
+
+// ------------------------------------------------------------------------------------------------ the plan
+// The front and the back are cut into the segments of audio_chain.hpp (audio_seg()), each pass with a warm-up of its
+// own; a segment writes x (the back: the samples) of its own frames only, so the FIR between them reads nothing
+// speculative once the front is verified and its history is no part of the speculation.
+
+// the front's default warm-up is the audio chain's: 72 tau of the high-pass
+inline uint32_t cass_default_front_warmup(const CassCfg &c)
+{
+    AudioCfg a;
+    std::memset(&a, 0, sizeof(a));
+    a.rate = c.rate;
+    a.highpass_hz = c.highpass_hz;
+    return audio_default_warmup(a);
+}
+// The back's: two poles at 4000 Hz.  Measured on the fixture's inputs (tests/test_cass_chain_host.py): a
+// zero-state run meets the true states bit for bit after 52 frames at the most; a fifth on top, up to a multiple of 64
+constexpr uint32_t CASS_BACK_MEASURED = 52;
+constexpr uint32_t CASS_DEFAULT_BACK_WARMUP = ((CASS_BACK_MEASURED + CASS_BACK_MEASURED / 5 + 1) + 63) / 64 * 64;
+
+AUDIO_HD CassFront cass_front_spec(const CassCfg &c, const CassFront &carried, uint64_t run_start)
+{
+    CassFront s = carried;
+    for (int i = 0; i < CASS_FRONT_VALUES; i++)
+        if (i < 24 || c.pre) s.v[i] = 0;
+    s.count = carried.count + run_start;
+    return s;
+}
+AUDIO_HD bool cass_bits_same(const double *a, const double *b, int n)
+{
+    for (int i = 0; i < n; i++) {
+        uint64_t x, y;
+        memcpy(&x, &a[i], 8);
+        memcpy(&y, &b[i], 8);
+        if (x != y) return false;
+    }
+    return true;
+}
+AUDIO_HD bool cass_front_same(const CassFront &a, const CassFront &b) { return a.count == b.count && cass_bits_same(a.v, b.v, CASS_FRONT_VALUES); }
+AUDIO_HD bool cass_back_same(const CassBack &a, const CassBack &b) { return cass_bits_same(a.post, b.post, 2); }
+
+struct CassPlanStats {
+    uint64_t segments, repaired_front, repaired_back;
+};
+
+// Run, verify, repair: what k_cass_front, k_cass_front_verify, k_cass_conv, k_cass_back and k_cass_back_verify do, in
+// their order and with the kernels' skipping FIR.  dst must not overlap src.
+inline void cass_run_planned(const CassCfg &c, CassState &st, const int16_t *src, int16_t *dst, const int32_t *hiss, const double *tf, uint64_t total,
+                             uint32_t L, uint32_t Wf, uint32_t Wb, CassPlanStats *stats)
+{
+    if (stats) stats->segments = stats->repaired_front = stats->repaired_back = 0;
+    if (L == 0) L = 1;
+    const uint64_t nseg = audio_seg_count(total, L);
+    std::vector<double> xs, rs((size_t)total * 2);
+    cass_plane_begin(c, st, xs, total);
+    {
+        std::vector<CassFront> at_start((size_t)nseg), at_end((size_t)nseg);
+        for (uint64_t j = 0; j < nseg; j++) {                                   // the speculative pass
+            const AudioSeg g = audio_seg(total, L, Wf, j);
+            CassFront s = g.run_start == 0 ? st.front : cass_front_spec(c, st.front, g.run_start);
+            cass_front_span(c, s, src, nullptr, hiss, g.run_start, g.start - g.run_start);
+            at_start[(size_t)j] = s;
+            cass_front_span(c, s, src, xs.data(), hiss, g.start, g.len);
+            at_end[(size_t)j] = s;
+        }
+        CassFront truth = st.front;
+        for (uint64_t j = 0; j < nseg; j++) {                                   // verify, repair
+            const AudioSeg g = audio_seg(total, L, Wf, j);
+            if (!cass_front_same(at_start[(size_t)j], truth)) {
+                cass_front_span(c, truth, src, xs.data(), hiss, g.start, g.len);
+                if (stats) stats->repaired_front++;
+            } else {
+                truth = at_end[(size_t)j];
+            }
+        }
+        st.front = truth;
+    }
+    cass_conv_span<true>(c, xs.data(), tf, rs.data(), 0, total);
+    if (!c.post) {
+        cass_back_span(c, st.back, rs.data(), dst, 0, total);                   // no state: nothing to speculate on
+    } else {
+        std::vector<CassBack> at_start((size_t)nseg), at_end((size_t)nseg);
+        for (uint64_t j = 0; j < nseg; j++) {
+            const AudioSeg g = audio_seg(total, L, Wb, j);
+            CassBack s = st.back;
+            if (g.run_start != 0) s.post[0] = s.post[1] = 0;
+            cass_back_span(c, s, rs.data(), nullptr, g.run_start, g.start - g.run_start);
+            at_start[(size_t)j] = s;
+            cass_back_span(c, s, rs.data(), dst, g.start, g.len);
+            at_end[(size_t)j] = s;
+        }
+        CassBack truth = st.back;
+        for (uint64_t j = 0; j < nseg; j++) {
+            const AudioSeg g = audio_seg(total, L, Wb, j);
+            if (!cass_back_same(at_start[(size_t)j], truth)) {
+                cass_back_span(c, truth, rs.data(), dst, g.start, g.len);
+                if (stats) stats->repaired_back++;
+            } else {
+                truth = at_end[(size_t)j];
+            }
+        }
+        st.back = truth;
+    }
+    cass_plane_end(c, st, xs, total);
+    if (stats) stats->segments = nseg;
+}
+
+} // namespace ntscsim

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "audio_chain.hpp"
+#include "audio_hiss.hpp"
 #include "glibc_rand.hpp"
 #include "ntsc_frames.hpp"
 #include "ntsc_stage.hpp"
@@ -28,19 +29,11 @@ namespace ntscsim {
 constexpr int AUDIO_LANES = 21;          // stages of the chain = lanes of a group
 constexpr int AUDIO_GROUPS = 3;          // groups of a wavefront
 constexpr int AUDIO_RING = 3 * AUDIO_LANES;
-constexpr int HISS_ROUNDS = 16;
-constexpr int HISS_CHUNK = 31 * HISS_ROUNDS;   // draws of one lane of k_audio_hiss
-constexpr int HISS_POLYS = 26;           // x^(HISS_CHUNK * 2^j): 2^33 draws of a block are 2^25 chunks at the most
 
 struct AudioBlock {                      // one descriptor; first: its first frame in the call
     const int16_t *src;
     int16_t *dst;
     uint64_t first, frames;
-};
-struct AudioHissBlock {                  // rand() window at the block's position; first: its first channel-sample in the call
-    uint32_t w[31];
-    uint32_t _pad;
-    uint64_t first, items;
 };
 struct AudioSegRec {
     AudioState at_start, at_end;         // at the segment's first own frame, behind its last
@@ -82,6 +75,25 @@ __global__ __launch_bounds__(64) void k_audio_hiss(const AudioHissBlock *__restr
             }
         }
     }
+}
+
+void audio_hiss_launch(const AudioHissBlock *blocks, int m, uint64_t max_items, const uint32_t *polys, int level, int32_t *out, hipStream_t st)
+{
+    const uint64_t chunks = (max_items + HISS_CHUNK - 1) / HISS_CHUNK;
+    const unsigned gx = (unsigned)std::min<uint64_t>((chunks + 63) / 64, 65535), gy = (unsigned)std::min(m, 1024);
+    hipLaunchKernelGGL(k_audio_hiss, dim3(gx, gy), dim3(64), 0, st, blocks, m, polys, level, out);
+}
+
+int audio_hiss_polys(const CtxStageView &v, uint32_t **polys)
+{
+    std::vector<uint32_t> host((size_t)HISS_POLYS * 31);
+    for (int j = 0; j < HISS_POLYS; j++) {
+        const RandPoly q = rand_poly_pow((uint64_t)HISS_CHUNK << j);
+        std::memcpy(&host[(size_t)j * 31], q.c, sizeof(q.c));
+    }
+    STAGECHK(v, hipMalloc((void **)polys, host.size() * sizeof(uint32_t)));
+    STAGECHK(v, hipMemcpy(*polys, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return NTSCSIM_OK;
 }
 
 // st != NULL: counts run from the ctx's sample count
@@ -509,19 +521,8 @@ int audio_blocks(ntscsim_ctx *c, const ntscsim_audio_desc *descs, int n, hipStre
         if (d.samples == 0) continue;
         blocks[o] = AudioBlock{d.src, d.dst, first, d.samples};
         if (hiss) {
-            AudioHissBlock &h = hb[o];
-            const uint64_t p = block_pos[(size_t)i];
-            // small blocks that follow each other (the tool's packets): step the generator instead of jumping
-            if (seq_pos == UINT64_MAX || p < seq_pos || p - seq_pos > 65536) {
-                seq = RandSeq(rand_state_at(p));
-                seq_pos = p;
-            }
-            for (; seq_pos < p; seq_pos++) (void)seq.next();
-            for (int j = 0; j < 31; j++) h.w[j] = seq.r[(seq.i + j) % 31];
-            h._pad = 0;
-            h.first = first * cfg.channels;
-            h.items = (uint64_t)d.samples * cfg.channels;
-            max_items = std::max(max_items, h.items);
+            audio_hiss_window(hb[o], seq, seq_pos, block_pos[(size_t)i], first * cfg.channels, (uint64_t)d.samples * cfg.channels);
+            max_items = std::max(max_items, hb[o].items);
         }
         first += d.samples;
         o++;
@@ -537,10 +538,7 @@ int audio_blocks(ntscsim_ctx *c, const ntscsim_audio_desc *descs, int n, hipStre
     int lrc = audio_mark(v, k, st);
     if (lrc != NTSCSIM_OK) return lrc;
     if (hiss) {
-        const uint64_t chunks = (max_items + HISS_CHUNK - 1) / HISS_CHUNK;
-        const unsigned gx = (unsigned)std::min<uint64_t>((chunks + 63) / 64, 65535), gy = (unsigned)std::min(m, 1024);
-        hipLaunchKernelGGL(k_audio_hiss, dim3(gx, gy), dim3(64), 0, st, reinterpret_cast<const AudioHissBlock *>(slot->dev + blocks_bytes), m, k->polys,
-                           cfg.hiss_level, k->hiss);
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + blocks_bytes), m, max_items, k->polys, cfg.hiss_level, k->hiss, st);
         lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
         if (lrc != NTSCSIM_OK) return lrc;
     }
@@ -584,13 +582,8 @@ extern "C" int ntscsim_audio_bind(ntscsim_ctx *c, const ntscsim_audio_params *p)
     if (!k->state) STAGECHK(v, hipMalloc((void **)&k->state, sizeof(AudioState)));
     if (!k->stats) STAGECHK(v, hipMalloc((void **)&k->stats, 2 * sizeof(uint64_t)));
     if (!k->polys) {
-        std::vector<uint32_t> host((size_t)HISS_POLYS * 31);
-        for (int j = 0; j < HISS_POLYS; j++) {
-            const RandPoly q = rand_poly_pow((uint64_t)HISS_CHUNK << j);
-            std::memcpy(&host[(size_t)j * 31], q.c, sizeof(q.c));
-        }
-        STAGECHK(v, hipMalloc((void **)&k->polys, host.size() * sizeof(uint32_t)));
-        STAGECHK(v, hipMemcpy(k->polys, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        const int prc = audio_hiss_polys(v, &k->polys);
+        if (prc != NTSCSIM_OK) return prc;
     }
     STAGECHK(v, hipMemset(k->state, 0, sizeof(AudioState)));
     STAGECHK(v, hipMemset(k->stats, 0, 2 * sizeof(uint64_t)));

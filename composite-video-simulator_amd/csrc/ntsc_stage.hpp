@@ -1,5 +1,5 @@
 // ntsc_stage.hpp -- the host scaffold of the device stages that are translation units of their own (frameblend:
-// csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip, filmac: csrc/ntsc_filmac.hip, posterize and colormap: csrc/ntsc_pixmap.hip, the audio chain: csrc/ntsc_audio.hip): what they see of an ntscsim_ctx,
+// csrc/ntsc_blend.hip, colorkey: csrc/ntsc_key.hip, average_delay: csrc/ntsc_avg.hip, scanimate: csrc/ntsc_scan.hip, vhsled: csrc/ntsc_led.hip, filmac: csrc/ntsc_filmac.hip, posterize and colormap: csrc/ntsc_pixmap.hip, the audio chain: csrc/ntsc_audio.hip, the cassette chain: csrc/ntsc_cass.hip): what they see of an ntscsim_ctx,
 // whose definition stays private to ntscsim_hip.hip, the pinned record slots their launches go up through, and the
 // arena their *_frames_host() calls copy host frames through.  The host logic without HIP in it: ntsc_frames.hpp (every
 // stage's); what only the two layer stages share: ntsc_layer.hpp (no HIP in it either) and ntsc_layer_frames.hpp.
@@ -23,6 +23,7 @@ struct FilmacState;                      // ntsc_filmac.hip: bound params, gamma
 struct PostState;                        // ntsc_pixmap.hip: bound size, the inputs' masks, record slots, host-frame arena
 struct CmapState;                        // ntsc_pixmap.hip: bound size, the colour table, record slots, host-frame arena
 struct AudioStageState;                  // ntsc_audio.hip: bound params, carried chain state, draw polynomials, scratch, record slots, staging
+struct CassStageState;                   // ntsc_cass.hip: bound params, carried chain state and history, scratch planes, tilt staging, record slots
 
 struct CtxStageView {
     int device;
@@ -38,6 +39,7 @@ struct CtxStageView {
     PostState **post;
     CmapState **cmap;
     AudioStageState **audio;
+    CassStageState **cass;
 };
 CtxStageView ctx_stage_view(ntscsim_ctx *c);     // ntscsim_hip.hip
 void blend_state_destroy(BlendState *b);         // ntsc_blend.hip
@@ -49,6 +51,7 @@ void filmac_state_destroy(FilmacState *k);       // ntsc_filmac.hip
 void post_state_destroy(PostState *k);           // ntsc_pixmap.hip
 void cmap_state_destroy(CmapState *k);           // ntsc_pixmap.hip
 void audio_state_destroy(AudioStageState *k);    // ntsc_audio.hip
+void cass_state_destroy(CassStageState *k);      // ntsc_cass.hip
 // ntscsim_debug_last_kernels(): "k_scan_splat" becomes "k_scan_splat+spill" if a workgroup of the last call spilled
 void scan_kernels_tap(ScanState *k, int device, std::string &kernels);   // ntsc_scan.hip
 

@@ -227,10 +227,11 @@ struct ntscsim_ctx {
     ntscsim::PostState *post = nullptr;     // ntscsim_post_bind(): state of the posterize stage (csrc/ntsc_pixmap.hip)
     ntscsim::CmapState *cmap = nullptr;     // ntscsim_cmap_bind(): state of the colormap stage (csrc/ntsc_pixmap.hip)
     ntscsim::AudioStageState *audio = nullptr; // ntscsim_audio_bind(): state of the audio stage (csrc/ntsc_audio.hip)
+    ntscsim::CassStageState *cass = nullptr;   // ntscsim_cass_bind(): state of the cassette stage (csrc/ntsc_cass.hip)
 };
 ntscsim::CtxStageView ntscsim::ctx_stage_view(ntscsim_ctx *c)
 {
-    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan, &c->led, &c->filmac, &c->post, &c->cmap, &c->audio};
+    return CtxStageView{c->device, c->stream, &c->err, &c->kernels, &c->blend, &c->key, &c->avg, &c->scan, &c->led, &c->filmac, &c->post, &c->cmap, &c->audio, &c->cass};
 }
 static void submit_engine_destroy(ntscsim_ctx *c);
 static int sub_wait_ticket(ntscsim_ctx *c, uint64_t ticket);
@@ -479,6 +480,7 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
     if (c->post) { ntscsim::post_state_destroy(c->post); c->post = nullptr; }
     if (c->cmap) { ntscsim::cmap_state_destroy(c->cmap); c->cmap = nullptr; }
     if (c->audio) { ntscsim::audio_state_destroy(c->audio); c->audio = nullptr; }
+    if (c->cass) { ntscsim::cass_state_destroy(c->cass); c->cass = nullptr; }
     for (Geometry *e : c->geoms) {
         e->lskip.release(); e->pskip.release(); e->jrow.release();
         delete e;

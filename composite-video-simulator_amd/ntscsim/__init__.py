@@ -16,7 +16,7 @@ from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
-__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "AutoContrast", "AudioChain", "Posterizer", "ColorMapper", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
+__all__ = ["FieldSimulator", "FrameBlender", "ColorKeyer", "FrameAverager", "Scanimator", "EdgeAligner", "AutoContrast", "AudioChain", "Cassette", "Posterizer", "ColorMapper", "blend_plan", "blend_frame_times", "Pool", "Params", "FieldDesc", "make_params", "NtscsimError", "lib",
            "field_rows", "calls_per_field", "field_schedule"]
 
 
@@ -1063,6 +1063,123 @@ class AudioChain:
     def kernel_ms(self):
         """(draws and pulse counts, k_audio_segments, k_audio_verify_repair) milliseconds of the last call."""
         out = (C.c_float * 3)()
+        self._call("debug_kernel_ms", out)
+        return tuple(float(v) for v in out)
+
+    def sync(self):
+        self.sim.sync()
+
+
+class Cassette:
+    """ffmpeg_cassette's tape chain (ntscsim_cass_*): its composite_audio_process() on interleaved int16 stereo,
+    bit-identical to the tool on the host that makes the call (the per-frame sin() is the host's libm), the hiss draws
+    included.  params: ntscsim_cass_params (_capi.make_cass_params(flags)) or None with `flags`.  sim: share the context
+    -- and with it the rand() position -- of a FieldSimulator; otherwise a context of its own is created.  Filter
+    states, sample count and the FIR's history live on the device and carry from block to block and from call to call;
+    calls must be ordered by the caller (one stream)."""
+
+    channels = 2
+
+    def __init__(self, params=None, device=0, flags=(), sim=None):
+        if params is None:
+            params = _capi.make_cass_params(flags)
+        self.params = params
+        self.taps = int(params.taps)
+        self._own = sim is None
+        self.sim = sim if sim is not None else FieldSimulator(device=device)
+        self._lib = self.sim._lib
+        try:
+            self._call("bind", C.byref(self.params))
+        except Exception:
+            self.close()
+            raise
+
+    def _call(self, what, *args):
+        name = "ntscsim_cass_%s" % what
+        self.sim._chk(getattr(self._lib, name)(self.sim._h, *args), name)
+
+    def close(self):
+        if self._own and self.sim is not None:
+            self.sim.close()
+        self.sim = None
+
+    def process(self, src, dst, blocks=None, stream=None):
+        """ntscsim_cass_device: src, dst are torch int16 CUDA tensors [frames, 2] (or flat), contiguous.  blocks:
+        [(frames, rng_pos or None), ...] cutting them into the call's descriptors in order (None: one block at the
+        ctx's rand() position).  Enqueues; does not synchronise."""
+        total = src.numel() // 2
+        assert src.is_contiguous() and dst.is_contiguous() and dst.numel() == src.numel()
+        if blocks is None:
+            blocks = [(total, None)]
+        assert sum(b[0] for b in blocks) == total
+        arr = (_capi.CassDesc * max(1, len(blocks)))()
+        at = 0
+        for d, (frames, pos) in zip(arr, blocks):
+            d.src = src.data_ptr() + at * 4
+            d.dst = dst.data_ptr() + at * 4
+            d.samples = int(frames)
+            d.rng_pos = RNG_AUTO if pos is None else int(pos)
+            at += int(frames)
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("device", arr, len(blocks), C.c_void_p(stream))
+
+    def host(self, array):
+        """ntscsim_cass_host: composite_audio_process(array, frames) in place on a numpy int16 array whose samples are
+        contiguous (any alignment).  Synchronous."""
+        assert array.dtype.str in ("<i2", "=i2") and array.flags["C_CONTIGUOUS"] and array.flags["WRITEABLE"]
+        self._call("host", C.c_void_p(array.ctypes.data), array.size // 2)
+
+    def reset(self):
+        self._call("reset")
+
+    @property
+    def state(self):
+        """(28 filter values as a tuple: 24 band-pass, pre[2], post[2]; sample count; the FIR's history as a tuple of
+        taps - 1 (left, right) pairs).  Reading and writing synchronise."""
+        s = _capi.CassState()
+        self._call("get_state", C.byref(s))
+        v = [x for c in s.bandpass for x in c] + list(s.pre) + list(s.post)
+        return tuple(v), int(s.count), tuple((s.history[k][0], s.history[k][1]) for k in range(self.taps - 1))
+
+    @state.setter
+    def state(self, value):
+        v, count, hist = value
+        s = _capi.CassState()
+        for c in range(2):
+            for i in range(12):
+                s.bandpass[c][i] = v[c * 12 + i]
+        for i in range(2):
+            s.pre[i], s.post[i] = v[24 + i], v[26 + i]
+        s.count = int(count)
+        s.taps = self.taps
+        for k, (a, b) in enumerate(hist):
+            s.history[k][0], s.history[k][1] = a, b
+        self._call("set_state", C.byref(s))
+
+    def set_plan(self, seg_len=0, warmup_front=0, warmup_back=0):
+        """ntscsim_cass_debug_set_plan: (0, 0, 0) restores the defaults; otherwise the warm-ups are taken as given."""
+        self._call("debug_set_plan", int(seg_len), int(warmup_front), int(warmup_back))
+
+    def default_warmups(self):
+        """(front: 72 tau of the high-pass, up to a multiple of 64; back: csrc/cass_chain.hpp CASS_DEFAULT_BACK_WARMUP)"""
+        import math
+        tau = self.params.rate / (2 * math.pi * self.params.highpass_hz)
+        return (int(72.0 * tau) + 1 + 63) // 64 * 64, 64
+
+    def stats(self):
+        """(segments, segments the front repaired, segments the back repaired) of the last call.  Synchronises."""
+        s = _capi.CassStats()
+        self._call("debug_stats", C.byref(s))
+        return int(s.segments), int(s.repaired_front), int(s.repaired_back)
+
+    def debug_time_kernels(self, on=True):
+        self._call("debug_time_kernels", 1 if on else 0)
+
+    def kernel_ms(self):
+        """(host sin fill, its upload, k_audio_hiss, k_cass_front, k_cass_front_verify, k_cass_conv, k_cass_back,
+        k_cass_back_verify) milliseconds of the last call."""
+        out = (C.c_float * 8)()
         self._call("debug_kernel_ms", out)
         return tuple(float(v) for v in out)
 

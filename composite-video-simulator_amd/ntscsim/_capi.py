@@ -72,6 +72,9 @@ EXPORTS = (
     "ntscsim_audio_params_from_cli", "ntscsim_audio_bind", "ntscsim_audio_device", "ntscsim_audio_host", "ntscsim_audio_reset",
     "ntscsim_audio_get_state", "ntscsim_audio_set_state", "ntscsim_audio_debug_set_plan", "ntscsim_audio_debug_stats",
     "ntscsim_audio_debug_pulses", "ntscsim_audio_debug_time_kernels", "ntscsim_audio_debug_kernel_ms",
+    "ntscsim_cass_params_init", "ntscsim_cass_parse_argv", "ntscsim_cass_params_derive", "ntscsim_cass_bind", "ntscsim_cass_device",
+    "ntscsim_cass_host", "ntscsim_cass_reset", "ntscsim_cass_get_state", "ntscsim_cass_set_state", "ntscsim_cass_debug_set_plan",
+    "ntscsim_cass_debug_stats", "ntscsim_cass_debug_time_kernels", "ntscsim_cass_debug_kernel_ms",
 )
 
 
@@ -446,6 +449,38 @@ class AudioStats(C.Structure):
     _fields_ = [("segments", C.c_uint64), ("repaired", C.c_uint64)]
 
 
+CASS_MAX_TAPS = 512
+
+
+class CassParams(C.Structure):
+    """struct ntscsim_cass_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_int32), ("rate", C.c_int32), ("passes", C.c_int32),
+                ("preemphasis", C.c_int32), ("deemphasis", C.c_int32), ("mono", C.c_int32), ("hiss_level", C.c_int32),
+                ("taps", C.c_int32), ("audio_stream_index", C.c_int32),
+                ("hiss_db", C.c_double), ("lowpass_hz", C.c_double), ("highpass_hz", C.c_double), ("emphasis_hz", C.c_double),
+                ("head_tilt", C.c_double), ("head_tilt_waver", C.c_double),
+                ("transcode_start", C.c_double), ("transcode_end", C.c_double), ("transcode_dur", C.c_double),
+                ("alpha_lowpass", C.c_double), ("alpha_highpass", C.c_double), ("alpha_pre", C.c_double), ("alpha_post", C.c_double),
+                ("input_path", C.c_char_p), ("output_path", C.c_char_p)]
+
+
+class CassState(C.Structure):
+    """struct ntscsim_cass_state"""
+    _fields_ = [("bandpass", (C.c_double * 12) * 2), ("pre", C.c_double * 2), ("count", C.c_uint64), ("post", C.c_double * 2),
+                ("taps", C.c_uint32), ("_pad", C.c_uint32), ("history", (C.c_double * 2) * (CASS_MAX_TAPS - 1))]
+
+
+class CassDesc(C.Structure):
+    """struct ntscsim_cass_desc"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("samples", C.c_uint32), ("_pad", C.c_uint32),
+                ("rng_pos", C.c_uint64)]
+
+
+class CassStats(C.Structure):
+    """struct ntscsim_cass_stats"""
+    _fields_ = [("segments", C.c_uint64), ("repaired_front", C.c_uint64), ("repaired_back", C.c_uint64)]
+
+
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
 
@@ -802,6 +837,32 @@ def lib():
     L.ntscsim_audio_debug_time_kernels.restype = C.c_int
     L.ntscsim_audio_debug_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.ntscsim_audio_debug_kernel_ms.restype = C.c_int
+    L.ntscsim_cass_params_init.argtypes = [C.POINTER(CassParams)]
+    L.ntscsim_cass_params_init.restype = None
+    L.ntscsim_cass_parse_argv.argtypes = [C.POINTER(CassParams), C.c_int, C.POINTER(C.c_char_p), C.c_int]
+    L.ntscsim_cass_parse_argv.restype = C.c_int
+    L.ntscsim_cass_params_derive.argtypes = [C.POINTER(CassParams)]
+    L.ntscsim_cass_params_derive.restype = C.c_int
+    L.ntscsim_cass_bind.argtypes = [C.c_void_p, C.POINTER(CassParams)]
+    L.ntscsim_cass_bind.restype = C.c_int
+    L.ntscsim_cass_device.argtypes = [C.c_void_p, C.POINTER(CassDesc), C.c_int, C.c_void_p]
+    L.ntscsim_cass_device.restype = C.c_int
+    L.ntscsim_cass_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ntscsim_cass_host.restype = C.c_int
+    L.ntscsim_cass_reset.argtypes = [C.c_void_p]
+    L.ntscsim_cass_reset.restype = C.c_int
+    L.ntscsim_cass_get_state.argtypes = [C.c_void_p, C.POINTER(CassState)]
+    L.ntscsim_cass_get_state.restype = C.c_int
+    L.ntscsim_cass_set_state.argtypes = [C.c_void_p, C.POINTER(CassState)]
+    L.ntscsim_cass_set_state.restype = C.c_int
+    L.ntscsim_cass_debug_set_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.ntscsim_cass_debug_set_plan.restype = C.c_int
+    L.ntscsim_cass_debug_stats.argtypes = [C.c_void_p, C.POINTER(CassStats)]
+    L.ntscsim_cass_debug_stats.restype = C.c_int
+    L.ntscsim_cass_debug_time_kernels.argtypes = [C.c_void_p, C.c_int]
+    L.ntscsim_cass_debug_time_kernels.restype = C.c_int
+    L.ntscsim_cass_debug_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.ntscsim_cass_debug_kernel_ms.restype = C.c_int
     L.ntscsim_pixmap_params_init.argtypes = [C.POINTER(PixmapParams)]
     L.ntscsim_pixmap_params_init.restype = None
     L.ntscsim_pixmap_params_free.argtypes = [C.POINTER(PixmapParams)]
@@ -891,6 +952,20 @@ def make_audio_params(flags=(), tool="ntsc"):
     if rc != OK:
         raise NtscsimError(rc, "ntscsim_audio_params_from_cli")
     return ap, p
+
+
+def make_cass_params(flags=(), require_io=False):
+    """ntscsim_cass_params from ffmpeg_cassette's switches (ffmpeg_cassette.cpp parse_argv :441-590), derived settings
+    included.  The switch strings are kept alive on the result (input_path / output_path point into them)."""
+    L = lib()
+    cp = CassParams()
+    argv = [b"ffmpeg_cassette"] + [str(f).encode() for f in flags]
+    arr = (C.c_char_p * len(argv))(*argv)
+    rc = L.ntscsim_cass_parse_argv(C.byref(cp), len(argv), arr, 1 if require_io else 0)
+    if rc != OK:
+        raise NtscsimError(rc, "ntscsim_cass_parse_argv(%r)" % (list(flags),))
+    cp._argv = arr
+    return cp
 
 
 def make_raw28_opts(flags=()):

@@ -1703,6 +1703,105 @@ int  ntscsim_audio_debug_time_kernels(ntscsim_ctx *ctx, int on);
 /* (k_audio_hiss + k_audio_pulses, k_audio_segments, k_audio_verify_repair) milliseconds of the last call */
 int  ntscsim_audio_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[3]);
 
+/* ------------------------------------------------------------------------------------------
+ * ffmpeg_cassette's tape chain as a device stage: composite_audio_process() of ffmpeg_cassette.cpp:334-416 (filters
+ * :80-209, ConvolutionMap :278-324, set-up :864-880).  It is the VHS chain without buzz and boost, plus a per-sample
+ * FIR between hiss and de-emphasis whose taps follow a head tilt that wavers with sin(), mirrored between left and
+ * right, and an integer mono downmix behind the pack.  Interleaved int16 stereo in and out, bit-identical to the tool
+ * on the host that makes the call: the per-frame sin() is libm's, evaluated by the host and uploaded, never by the
+ * device.  The hiss draws come from the ctx's rand() position, as the audio stage's do.  DESIGN.md 7m.
+ */
+#define NTSCSIM_CASS_MAX_TAPS 512  /* enough for |headalign| <= 100 */
+typedef struct ntscsim_cass_params {
+    uint32_t struct_size;          /* sizeof(ntscsim_cass_params)                                               */
+    int32_t  channels;             /* output_audio_channels :448  2, the tool never changes it                   */
+    int32_t  rate;                 /* output_audio_rate :236  44100                                             */
+    int32_t  passes;               /* :868  6                                                                   */
+    int32_t  preemphasis;          /* -preemphasis <n>: n > 0                                                    */
+    int32_t  deemphasis;           /* -deemphasis <n>: n > 0                                                     */
+    int32_t  mono;                 /* -mono                                                                     */
+    int32_t  hiss_level;           /* derived: (int)(dBFS(hiss_db) * 5000) :582, libm pow on the host            */
+    int32_t  taps;                 /* derived: (int)floor(fabs(tilt*2) + fabs(tilt*3) + 7.5) :338                */
+    int32_t  audio_stream_index;   /* -a <n> / -an (-1): recorded, never used                                    */
+    double   hiss_db;              /* -audio-hiss, -45                                                          */
+    double   lowpass_hz;           /* -low (int)strtoul, presets; 20000                                         */
+    double   highpass_hz;          /* -high (int)strtoul, presets; 20                                           */
+    double   emphasis_hz;          /* :873 / :878  4000 for both filters                                        */
+    double   head_tilt;            /* -headalign atoi, presets; 0.2                                             */
+    double   head_tilt_waver;      /* -headalignwaver atoi, presets; 0.5                                        */
+    double   transcode_start, transcode_end, transcode_dur; /* -ss -se -t: recorded, never used                   */
+    double   alpha_lowpass, alpha_highpass, alpha_pre, alpha_post; /* derived: LowpassFilter::setFilter :84      */
+    const char *input_path, *output_path; /* -i / -o: point into argv; recorded, never used by the stage         */
+} ntscsim_cass_params;
+/* the tool's initial values (:235-248, :327-332, :446-448), derived fields included */
+void ntscsim_cass_params_init(ntscsim_cass_params *p);
+/* Mirror of parse_argv() :441-590; later switches override earlier ones.  argv[0] is the program name.  require_io != 0
+ * applies the tool's "You must specify an input and output file".  Ends with ntscsim_cass_params_derive().
+ * NTSCSIM_OK, NTSCSIM_E_HELP (-h / -help), NTSCSIM_E_FLAG (the tool's "return 1", or a switch without its value), or
+ * what the derivation answers. */
+int  ntscsim_cass_parse_argv(ntscsim_cass_params *p, int argc, const char *const *argv, int require_io);
+/* hiss_level, taps and the four alphas from the fields above them.  NTSCSIM_E_ARG: a cut-off of 0 (the tool's
+ * HiLoComboPass::init() returns without filters and its assert :335 ends it).  NTSCSIM_E_PARAM: a cut-off below 0, more
+ * than NTSCSIM_CASS_MAX_TAPS taps, a hiss level outside int. */
+int  ntscsim_cass_params_derive(ntscsim_cass_params *p);
+
+typedef struct ntscsim_cass_state {
+    double   bandpass[2][12];      /* per channel: the six low-pass states, then the six high-pass states        */
+    double   pre[2];               /* audio_linear_preemphasis_pre: SHARED by the channels (:383)                */
+    uint64_t count;                /* audio_proc_count :276                                                     */
+    double   post[2];              /* audio_linear_preemphasis_post: shared as well (:403)                       */
+    uint32_t taps;                 /* of the params the state belongs to                                        */
+    uint32_t _pad;
+    double   history[NTSCSIM_CASS_MAX_TAPS - 1][2]; /* the FIR's delay line: [k][c] is the value in front of the
+                                    * FIR of channel c, taps-1-k frames before the next frame; k < taps-1 are used */
+} ntscsim_cass_state;
+
+typedef struct ntscsim_cass_desc {
+    const int16_t *src;            /* device pointer, `samples` frames of 2 interleaved int16                     */
+    int16_t       *dst;
+    uint32_t       samples;        /* sample frames, as composite_audio_process()'s second argument; 0 allowed   */
+    uint32_t       _pad;
+    uint64_t       rng_pos;        /* rand() position of the block's first draw, or NTSCSIM_RNG_AUTO             */
+} ntscsim_cass_desc;
+
+typedef struct ntscsim_cass_stats {
+    uint64_t segments;             /* of the last call                                                          */
+    uint64_t repaired_front;       /* segments of it that k_cass_front_verify ran again                          */
+    uint64_t repaired_back;        /* segments of it that k_cass_back_verify ran again (0 without de-emphasis)    */
+} ntscsim_cass_stats;
+
+/* Snapshot the parameters and reset the state (zeros, count 0).  Waits for cassette work in flight.  Does not touch a
+ * bound audio stage.  NTSCSIM_E_PARAM: channels != 2, passes != 6, rate <= 0, a cut-off <= 0, taps that are not
+ * cass_taps(head_tilt) or outside 1..NTSCSIM_CASS_MAX_TAPS, a hiss level below 0. */
+int  ntscsim_cass_bind(ntscsim_ctx *ctx, const ntscsim_cass_params *cp);
+/*
+ * The n blocks are ONE continuous stream, as ntscsim_audio_device()'s are; the same rules for rand() positions, device
+ * pointers, stream order and overlap hold.  The host evaluates head_tilt_final of every frame (libm sin) into pinned
+ * staging of the ctx -- after it has enqueued the front's kernels, so the two overlap; a call of 2^18 frames or more
+ * splits the fill over four threads, a fixed number -- and uploads it on the call's stream.  Kernels: k_audio_hiss (the draws), k_cass_front (band-pass,
+ * pre-emphasis, clip, hiss: the speculative lane pipeline, doubles into a scratch plane), k_cass_front_verify (ordered
+ * walk, repairs), k_cass_conv (the FIR, parallel over frames from an LDS tile; packs and stores without de-emphasis),
+ * and with de-emphasis k_cass_back + k_cass_back_verify (the two shared poles, pack, downmix; speculative again).
+ * NTSCSIM_E_ARG: no ntscsim_cass_bind() before, a NULL or odd pointer in a block with samples, a dst that overlaps any
+ * src of the call.
+ */
+int  ntscsim_cass_device(ntscsim_ctx *ctx, const ntscsim_cass_desc *descs, int n, void *hip_stream);
+/* Drop-in for composite_audio_process(audio, samples): HOST memory, in place, any alignment.  Synchronous. */
+int  ntscsim_cass_host(ntscsim_ctx *ctx, int16_t *audio, uint32_t samples);
+/* reset: the tool's start.  get / set: a track processed in pieces, or started at any sample count.  set refuses a
+ * state whose taps are not the bound params' (NTSCSIM_E_ARG).  All wait for the device. */
+int  ntscsim_cass_reset(ntscsim_ctx *ctx);
+int  ntscsim_cass_get_state(ntscsim_ctx *ctx, ntscsim_cass_state *out);
+int  ntscsim_cass_set_state(ntscsim_ctx *ctx, const ntscsim_cass_state *in);
+/* Debug taps.  set_plan: segment length and the two warm-ups in frames.  (0, 0, 0) restores the defaults (4096 frames;
+ * 72 time constants of the high-pass for the front, 64 frames for the back); any other triple is taken as given. */
+int  ntscsim_cass_debug_set_plan(ntscsim_ctx *ctx, uint32_t seg_len, uint32_t warmup_front, uint32_t warmup_back);
+int  ntscsim_cass_debug_stats(ntscsim_ctx *ctx, ntscsim_cass_stats *out);
+int  ntscsim_cass_debug_time_kernels(ntscsim_ctx *ctx, int on);
+/* milliseconds of the last call: [0] the host's sin fill (CPU clock), [1] its upload, [2] k_audio_hiss, [3] k_cass_front,
+ * [4] k_cass_front_verify, [5] k_cass_conv, [6] k_cass_back, [7] k_cass_back_verify */
+int  ntscsim_cass_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[8]);
+
 #ifdef __cplusplus
 }
 #endif
