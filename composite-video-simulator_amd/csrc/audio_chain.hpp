@@ -5,7 +5,8 @@
 // every sum below is rounded on its own, in the reference's order.
 //
 // Also here: the PLAN that cuts a call's frames into segments which start early from a zero state, and
-// run / verify / repair over that plan, so that a host program executes what the device executes.
+// run / verify / repair over that plan, so that a host program executes what the device executes -- for one stream and
+// for many independent tracks in one call (the track table and the segment-to-track lookup).
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -250,6 +251,113 @@ inline void audio_run_planned(const AudioCfg &c, AudioState &st, const int16_t *
     }
     st = truth;
     if (stats) stats->segments = nseg;
+}
+
+// ------------------------------------------------------------------------------------------------ many tracks
+// A tracks call (ntscsim_audio_tracks_device) puts independent streams side by side: each track is planned on its own,
+// exactly as a call of its frames alone would be, and the segments of all tracks are numbered through -- track 0's, then
+// track 1's ... -- so that one launch runs them.  A warm-up clamps at frame 0 of ITS track and starts there from that
+// track's carried state.
+
+struct AudioTrackEnt {
+    uint64_t frames;                     // of the track
+    uint64_t plane;                      // its first frame in the PLANE: the frames of all tracks numbered through, which the
+                                         // call's hiss (times channels) and pulse scratch and the blocks' `first` are indexed by
+    uint64_t seg0;                       // its first segment in the call-wide numbering (= the segments of the tracks before it)
+    AudioState *state;                   // carried state: read at the start, written at the end; NULL: zeros, count 0, end discarded
+    int32_t block0, nblocks;             // its blocks in the call's block array (a block's `first` counts in the plane)
+};
+
+// fills plane and seg0 of tab[0..n) from the frames; returns the segments of the call
+inline uint64_t audio_tracks_layout(AudioTrackEnt *tab, int n, uint32_t L)
+{
+    uint64_t plane = 0, seg = 0;
+    for (int t = 0; t < n; t++) {
+        tab[t].plane = plane;
+        tab[t].seg0 = seg;
+        plane += tab[t].frames;
+        seg += audio_seg_count(tab[t].frames, L);
+    }
+    return seg;
+}
+
+// The track of call-wide segment j (j < the call's segments): the LAST t with tab[t].seg0 <= j.  Tracks without frames
+// share their seg0 with the track behind them, so the last one is the one that owns j.  j - tab[t].seg0 is the segment
+// within the track.
+AUDIO_HD int audio_track_of(const AudioTrackEnt *tab, int n, uint64_t j)
+{
+    int lo = 0, hi = n;                                                         // tab[lo].seg0 <= j < tab[hi].seg0 (tab[n]: the call's segments)
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (tab[mid].seg0 <= j) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+inline AudioState audio_track_carried(const AudioTrackEnt &e)
+{
+    if (e.state) return *e.state;
+    AudioState z;
+    for (int i = 0; i < AUDIO_STATE_VALUES; i++) z.v[i] = 0;
+    z.count = 0;
+    return z;
+}
+
+struct AudioTrackIO {                    // host: one track of audio_run_tracks_planned()
+    const int16_t *src;
+    int16_t *dst;                        // must not overlap any src
+    const int32_t *hiss;                 // numerators of the track (NULL: no hiss)
+    uint64_t frames;
+    AudioState *state;                   // as AudioTrackEnt's
+};
+
+// Run, verify, repair over a set of tracks: what k_audio_track_segments (every call-wide segment, found through
+// audio_track_of) and k_audio_track_verify (each track's records walked from its own true state) do.  stats[t]: of track t.
+inline void audio_run_tracks_planned(const AudioCfg &c, const AudioTrackIO *tracks, int n, uint32_t L, uint32_t W, AudioPlanStats *stats)
+{
+    for (int t = 0; t < n; t++) stats[t].segments = stats[t].repaired = stats[t].worst_convergence = 0;
+    if (!c.enabled) {
+        for (int t = 0; t < n; t++) std::memcpy(tracks[t].dst, tracks[t].src, (size_t)tracks[t].frames * (size_t)c.channels * sizeof(int16_t));
+        return;
+    }
+    if (L == 0) L = 1;
+    std::vector<AudioTrackEnt> tab((size_t)n);
+    for (int t = 0; t < n; t++) {
+        tab[(size_t)t].frames = tracks[t].frames;
+        tab[(size_t)t].state = tracks[t].state;
+        tab[(size_t)t].block0 = t;                                              // the host has one block per track
+        tab[(size_t)t].nblocks = 1;
+    }
+    const uint64_t nseg = audio_tracks_layout(tab.data(), n, L);
+    std::vector<AudioState> at_start((size_t)nseg), at_end((size_t)nseg);
+    for (uint64_t j = 0; j < nseg; j++) {                                       // the speculative pass
+        const int t = audio_track_of(tab.data(), n, j);
+        const AudioTrackEnt &e = tab[(size_t)t];
+        const AudioSeg g = audio_seg(e.frames, L, W, j - e.seg0);
+        const AudioState carried = audio_track_carried(e);
+        AudioState s = g.run_start == 0 ? carried : audio_spec_state(c, carried, g.run_start);
+        audio_run_span(c, s, tracks[t].src, nullptr, tracks[t].hiss, g.run_start, g.start - g.run_start);
+        at_start[(size_t)j] = s;
+        audio_run_span(c, s, tracks[t].src, tracks[t].dst, tracks[t].hiss, g.start, g.len);
+        at_end[(size_t)j] = s;
+    }
+    for (int t = 0; t < n; t++) {                                               // verify, repair: per track
+        const AudioTrackEnt &e = tab[(size_t)t];
+        const uint64_t nt = audio_seg_count(e.frames, L);
+        AudioState truth = audio_track_carried(e);
+        for (uint64_t j = 0; j < nt; j++) {
+            const AudioSeg g = audio_seg(e.frames, L, W, j);
+            if (!audio_state_same(at_start[(size_t)(e.seg0 + j)], truth)) {
+                audio_run_span(c, truth, tracks[t].src, tracks[t].dst, tracks[t].hiss, g.start, g.len);
+                stats[t].repaired++;
+            } else {
+                truth = at_end[(size_t)(e.seg0 + j)];
+            }
+        }
+        if (e.state) *e.state = truth;
+        stats[t].segments = nt;
+    }
 }
 
 } // namespace ntscsim

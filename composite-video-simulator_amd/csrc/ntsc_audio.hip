@@ -7,6 +7,7 @@
 // hands its result to lane r + 1 (__shfl_up, two dwords).  Three groups share a wavefront.  Stages with per-channel
 // state keep two values and alternate; the pre-/de-emphasis stages keep one, which IS the reference's cross-channel
 // coupling (:920, :960).  k_audio_verify_repair then makes the result independent of the speculation.
+// ntscsim_audio_tracks_device() runs many such streams side by side through a track table (k_audio_track_*).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -155,14 +156,15 @@ __device__ __forceinline__ void audio_seek(const AudioCall &k, int &b, uint64_t 
 }
 
 // Frames [first, first + warm + own) of the call through the 21 lanes of one group; r: this lane's place in its group
-// (>= AUDIO_LANES or !live: the lane only takes part in the hand-offs).  init[]: the state the run starts from.  The
+// (>= AUDIO_LANES or !live: the lane only takes part in the hand-offs).  init[]: the state the run starts from; b0: a
+// block at or in front of frame `first`, where the lane's block cursors start (a tracks call: the track's first).  The
 // outputs of the last `own` frames are stored.  at_start (may be NULL) / at_end receive the values this lane owns, at
 // the first own frame and behind the last; their other values and their counts are the caller's.
 // ring: AUDIO_RING entries of the group for each of the three prefetched inputs -- every lane fetches, one period of 21
 // steps ahead, what channel-sample (period * 21 + r) needs (input, hiss numerator, pulse count), so that no stage waits
 // for memory inside a step.
 __device__ void audio_run_lanes(const AudioCall &k, int r, bool live, uint64_t first, uint64_t warm, uint64_t own, const double *init,
-                                AudioState *at_start, AudioState *at_end, int32_t *ring_in, int32_t *ring_hiss, int32_t *ring_pulses)
+                                AudioState *at_start, AudioState *at_end, int32_t *ring_in, int32_t *ring_hiss, int32_t *ring_pulses, int b0 = 0)
 {
     const AudioCfg &c = k.c;
     const int ch = c.channels;
@@ -175,7 +177,7 @@ __device__ void audio_run_lanes(const AudioCall &k, int r, bool live, uint64_t f
 
     // prefetch cursor: channel-sample pf of the run, period by period
     uint64_t pf = (uint64_t)r;
-    int pf_block = 0, st_block = 0;
+    int pf_block = b0, st_block = b0;                                          // b0: a block at or in front of frame `first`
     int32_t pf_in = 0, pf_hiss = 0, pf_pulses = 0;
     uint64_t st_first = 0, st_end = 0;                                         // the block the store lane writes
     int16_t *st_dst = nullptr;
@@ -345,6 +347,121 @@ __global__ __launch_bounds__(64) void k_audio_verify_repair(AudioCall k, AudioSt
     if (lane == 0) { stats[0] = nseg; stats[1] = repaired; }
 }
 
+// ---------------------------------------------------------------------------------------- many tracks
+// ntscsim_audio_tracks_device(): independent streams side by side (the track table of audio_chain.hpp).  The kernels
+// above stay the single stream's; these hand the same audio_run_lanes a track's VIEW.  The three groups of a wavefront
+// may serve three tracks, so what differs between tracks lives in VGPRs; to keep that small the tracks are laid into ONE
+// frame numbering, the PLANE (track t owns frames [plane_t, plane_t + frames_t) of it): the hiss and pulse planes and the
+// blocks' `first` are indexed by it, their base pointers stay wave-uniform, and a view differs from the call only in
+// where the run stands in the plane and in the track's range of blocks (b0 .. nblocks).
+struct AudioTracksCall {
+    AudioCfg c;
+    const AudioTrackEnt *tracks;
+    const AudioBlock *blocks;            // of all tracks, `first` in the plane
+    const int32_t *hiss;                 // per channel-sample / per frame of the plane
+    const uint8_t *pulses;
+    uint64_t nseg;                       // segments of the call
+    int ntracks;
+};
+
+__device__ __forceinline__ AudioCall audio_track_view(const AudioTracksCall &k, const AudioTrackEnt &e)
+{
+    AudioCall v;
+    v.c = k.c;
+    v.blocks = k.blocks;
+    v.hiss = k.hiss;
+    v.pulses = k.pulses;
+    v.total = e.plane + e.frames;                                               // where the track ends in the plane
+    v.nblocks = e.block0 + e.nblocks;                                           // audio_seek stops at the track's last block
+    return v;
+}
+
+// pulse counts per frame of every track, each from its own sample count
+__global__ __launch_bounds__(256) void k_audio_track_pulses(AudioCfg c, const AudioTrackEnt *__restrict__ tracks, int ntracks, uint8_t *__restrict__ out)
+{
+    for (int t = (int)blockIdx.y; t < ntracks; t += (int)gridDim.y) {
+        const AudioTrackEnt e = tracks[t];
+        const uint64_t base = e.state ? e.state->count : 0;
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e.frames; i += (uint64_t)gridDim.x * blockDim.x)
+            out[e.plane + i] = (uint8_t)audio_pulse_count(c, base + i);
+    }
+}
+
+// One wavefront per workgroup; group g of workgroup b takes call-wide segment 3 b + g, whatever track it belongs to.
+__global__ __launch_bounds__(64) void k_audio_track_segments(AudioTracksCall k, AudioSegRec *__restrict__ recs, uint32_t seg_len, uint32_t warmup)
+{
+    __shared__ int32_t ring[AUDIO_GROUPS + 1][3][AUDIO_RING];
+    __shared__ double init[AUDIO_GROUPS + 1][AUDIO_STATE_VALUES];
+    const int lane = (int)threadIdx.x, g = lane / AUDIO_LANES, r = lane - g * AUDIO_LANES;
+    const uint64_t j = (uint64_t)blockIdx.x * AUDIO_GROUPS + (uint64_t)g;
+    const bool live = g < AUDIO_GROUPS && j < k.nseg;
+    AudioTrackEnt e{0, 0, 0, nullptr, 0, 0};
+    AudioSeg s{0, 0, 0};
+    if (live) {
+        e = k.tracks[audio_track_of(k.tracks, k.ntracks, j)];
+        s = audio_seg(e.frames, seg_len, warmup, j - e.seg0);                    // clamps at frame 0 of this track
+        const bool spec = s.run_start != 0;
+        for (int i = r; i < AUDIO_STATE_VALUES; i += AUDIO_LANES) {
+            const double v = (spec && audio_value_live(k.c, i)) || !e.state ? 0.0 : e.state->v[i];
+            init[g][i] = v;
+            recs[j].at_start.v[i] = v;
+            recs[j].at_end.v[i] = v;
+        }
+        if (r == 0) {
+            const uint64_t count = e.state ? e.state->count : 0;
+            recs[j].at_start.count = count + s.start;
+            recs[j].at_end.count = count + s.start + s.len;
+        }
+    }
+    __syncthreads();
+    const AudioCall view = audio_track_view(k, e);
+    audio_run_lanes(view, r, live, e.plane + s.run_start, s.start - s.run_start, s.len, init[g], live ? &recs[j].at_start : nullptr,
+                    live ? &recs[j].at_end : nullptr, ring[g][0], ring[g][1], ring[g][2], e.block0);
+}
+
+// One workgroup (one wavefront) per track: the walk of k_audio_verify_repair over that track's records, from that
+// track's true state.
+__global__ __launch_bounds__(64) void k_audio_track_verify(AudioTracksCall k, const AudioSegRec *__restrict__ recs, uint32_t seg_len, uint32_t warmup,
+                                                           uint64_t *__restrict__ stats)
+{
+    __shared__ int32_t ring[3][AUDIO_RING];
+    __shared__ AudioState truth;
+    __shared__ double init[AUDIO_STATE_VALUES];
+    const int lane = (int)threadIdx.x;
+    const AudioTrackEnt e = k.tracks[blockIdx.x];
+    const AudioCall view = audio_track_view(k, e);
+    const uint64_t nseg = audio_seg_count(e.frames, seg_len);
+    recs += e.seg0;
+    if (lane < AUDIO_STATE_VALUES) truth.v[lane] = e.state ? e.state->v[lane] : 0.0;
+    if (lane == AUDIO_STATE_VALUES) truth.count = e.state ? e.state->count : 0;
+    __syncthreads();
+    uint64_t repaired = 0;
+    for (uint64_t j = 0; j < nseg; j++) {
+        bool same = true;
+        if (lane < AUDIO_STATE_VALUES) same = __double_as_longlong(recs[j].at_start.v[lane]) == __double_as_longlong(truth.v[lane]);
+        if (lane == AUDIO_STATE_VALUES) same = recs[j].at_start.count == truth.count;
+        const bool ok = __all(same);
+        __syncthreads();
+        if (ok) {
+            if (lane < AUDIO_STATE_VALUES) truth.v[lane] = recs[j].at_end.v[lane];
+            if (lane == AUDIO_STATE_VALUES) truth.count = recs[j].at_end.count;
+        } else {
+            const AudioSeg s = audio_seg(e.frames, seg_len, warmup, j);
+            if (lane < AUDIO_STATE_VALUES) init[lane] = truth.v[lane];
+            __syncthreads();
+            audio_run_lanes(view, lane, lane < AUDIO_LANES, e.plane + s.start, 0, s.len, init, nullptr, &truth, ring[0], ring[1], ring[2], e.block0);
+            if (lane == 0) truth.count += s.len;
+            repaired++;
+        }
+        __syncthreads();
+    }
+    if (e.state) {
+        if (lane < AUDIO_STATE_VALUES) e.state->v[lane] = truth.v[lane];
+        if (lane == AUDIO_STATE_VALUES) e.state->count = truth.count;
+    }
+    if (lane == 0) { stats[2 * (uint64_t)blockIdx.x] = nseg; stats[2 * (uint64_t)blockIdx.x + 1] = repaired; }
+}
+
 // ---------------------------------------------------------------------------------------- host side
 struct AudioStageState {
     ntscsim_audio_params prm;
@@ -356,6 +473,9 @@ struct AudioStageState {
     uint8_t *pulses = nullptr;
     AudioSegRec *recs = nullptr;
     size_t hiss_cap = 0, pulses_cap = 0, recs_cap = 0;
+    uint64_t *track_stats = nullptr;     // device: segments, repaired per track of the last tracks call
+    size_t track_stats_cap = 0;          // in values: two per track
+    int last_tracks = 0;
     uint32_t plan_len = 0, plan_warmup = 0;   // 0: the default
     bool plan_warmup_set = false;
     RecordSlots<> slots;
@@ -379,6 +499,7 @@ void audio_state_destroy(AudioStageState *k)
     if (k->hiss) (void)hipFree(k->hiss);
     if (k->pulses) (void)hipFree(k->pulses);
     if (k->recs) (void)hipFree(k->recs);
+    if (k->track_stats) (void)hipFree(k->track_stats);
     audio_drop_marks(k);
     k->slots.release();
     k->frames.release();
@@ -559,6 +680,160 @@ int audio_blocks(ntscsim_ctx *c, const ntscsim_audio_desc *descs, int n, hipStre
     return lrc == NTSCSIM_OK ? audio_mark(v, k, st) : lrc;
 }
 
+// ntscsim_audio_tracks_device(): n independent streams in one launch of each kernel
+int audio_tracks(ntscsim_ctx *c, const ntscsim_audio_track *tracks, int n, hipStream_t st)
+{
+    CtxStageView v = ctx_stage_view(c);
+    AudioStageState *k = *v.audio;
+    const AudioCfg &cfg = k->cfg;
+    const size_t fbytes = (size_t)cfg.channels * sizeof(int16_t);
+    // every track and descriptor checked before anything is enqueued or the rand() position moves
+    std::vector<Span> srcs;
+    std::vector<uintptr_t> states;
+    uint64_t total = 0;
+    size_t m = 0;                                                               // blocks that have frames
+    for (int t = 0; t < n; t++) {
+        const ntscsim_audio_track &tr = tracks[t];
+        if (tr.n_blocks < 0 || (tr.n_blocks > 0 && !tr.blocks) || ((uintptr_t)tr.state & 7)) return NTSCSIM_E_ARG;
+        if (tr.state) states.push_back((uintptr_t)tr.state);
+        for (int i = 0; i < tr.n_blocks; i++) {
+            const ntscsim_audio_desc &d = tr.blocks[i];
+            if (d.samples == 0) continue;
+            if (!d.src || !d.dst || (((uintptr_t)d.src | (uintptr_t)d.dst) & 1)) return NTSCSIM_E_ARG;
+            srcs.push_back(Span{(uintptr_t)d.src, (uintptr_t)d.src + (size_t)d.samples * fbytes});
+            total += d.samples;
+            m++;
+        }
+    }
+    if (m > (size_t)INT32_MAX) return NTSCSIM_E_ARG;
+    std::sort(states.begin(), states.end());
+    for (size_t i = 1; i < states.size(); i++)
+        if (states[i] - states[i - 1] < sizeof(AudioState)) return NTSCSIM_E_ARG;   // two tracks would share a state
+    std::sort(srcs.begin(), srcs.end(), [](const Span &x, const Span &y) { return x.a < y.a; });
+    std::vector<uintptr_t> reach(srcs.size());                                  // the furthest end among srcs[0..i]
+    for (size_t i = 0; i < srcs.size(); i++) reach[i] = std::max(srcs[i].b, i ? reach[i - 1] : 0);
+    for (int t = 0; t < n; t++)
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_audio_desc &d = tracks[t].blocks[i];
+            if (d.samples == 0) continue;
+            const uintptr_t a = (uintptr_t)d.dst, b = a + (size_t)d.samples * fbytes;
+            const size_t at = (size_t)(std::lower_bound(srcs.begin(), srcs.end(), b, [](const Span &x, uintptr_t e) { return x.a < e; }) - srcs.begin());
+            if (at > 0 && reach[at - 1] > a) return NTSCSIM_E_ARG;              // a warm-up reads input again, in any track
+        }
+    STAGECHK(v, hipSetDevice(v.device));
+    if (2 * (size_t)n > k->track_stats_cap) {
+        int rc = k->slots.wait_all(v);                                          // launches in flight use what is replaced
+        if (rc == NTSCSIM_OK) rc = audio_grow(v, k->track_stats, k->track_stats_cap, 2 * (size_t)n);
+        if (rc != NTSCSIM_OK) return rc;
+    }
+    v.kernels->clear();
+    audio_drop_marks(k);
+    k->last_tracks = n;
+    const size_t stats_bytes = (size_t)n * 2 * sizeof(uint64_t);
+    if (!cfg.enabled) {                                                         // -nocomp: the tool does not call the chain
+        for (int t = 0; t < n; t++)
+            for (int i = 0; i < tracks[t].n_blocks; i++) {
+                const ntscsim_audio_desc &d = tracks[t].blocks[i];
+                if (d.samples) STAGECHK(v, hipMemcpyAsync(d.dst, d.src, (size_t)d.samples * fbytes, hipMemcpyDeviceToDevice, st));
+            }
+        if (n) STAGECHK(v, hipMemsetAsync(k->track_stats, 0, stats_bytes, st));
+        return NTSCSIM_OK;
+    }
+    const bool hiss = cfg.hiss_level != 0, buzz = audio_buzz_on(cfg);
+    const uint32_t L = k->plan_len ? k->plan_len : AUDIO_DEFAULT_SEG;
+    const uint32_t W = k->plan_warmup_set ? k->plan_warmup : audio_default_warmup(cfg);
+    // the rand() position moves at call time, whatever becomes of the launch: tracks in order, blocks in order
+    uint64_t pos = ntscsim_get_rng_pos(c);
+    std::vector<uint64_t> block_pos;
+    block_pos.reserve(m);
+    for (int t = 0; t < n; t++)
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_audio_desc &d = tracks[t].blocks[i];
+            if (d.rng_pos != NTSCSIM_RNG_AUTO) pos = d.rng_pos;
+            if (d.samples) block_pos.push_back(pos);
+            if (hiss) pos += (uint64_t)d.samples * (uint64_t)cfg.channels;
+        }
+    ntscsim_set_rng_pos(c, pos);
+    if (total == 0) {
+        if (n) STAGECHK(v, hipMemsetAsync(k->track_stats, 0, stats_bytes, st));
+        return NTSCSIM_OK;
+    }
+    // records: the track table, the blocks that have frames, their rand() windows
+    const size_t tab_bytes = (size_t)n * sizeof(AudioTrackEnt), blocks_bytes = m * sizeof(AudioBlock), hb_bytes = hiss ? m * sizeof(AudioHissBlock) : 0;
+    RecordSlot *slot = nullptr;
+    const int rc = k->slots.acquire(v, tab_bytes + blocks_bytes + hb_bytes, slot);
+    if (rc != NTSCSIM_OK) return rc;
+    AudioTrackEnt *tab = reinterpret_cast<AudioTrackEnt *>(slot->host);
+    AudioBlock *blocks = reinterpret_cast<AudioBlock *>(slot->host + tab_bytes);
+    AudioHissBlock *hb = reinterpret_cast<AudioHissBlock *>(slot->host + tab_bytes + blocks_bytes);
+    int o = 0;
+    uint64_t total_before = 0;                                                  // = the plane of the track, as audio_tracks_layout() sets it
+    for (int t = 0; t < n; t++) {
+        AudioTrackEnt &e = tab[t];
+        e.frames = 0;
+        e.state = reinterpret_cast<AudioState *>(tracks[t].state);
+        e.block0 = o;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_audio_desc &d = tracks[t].blocks[i];
+            if (d.samples == 0) continue;
+            blocks[o++] = AudioBlock{d.src, d.dst, total_before + e.frames, d.samples};   // first: in the plane
+            e.frames += d.samples;
+        }
+        e.nblocks = o - e.block0;
+        total_before += e.frames;
+    }
+    const uint64_t nseg = audio_tracks_layout(tab, n, L);
+    uint64_t max_items = 0, max_frames = 0;
+    if (hiss) {
+        RandSeq seq(rand_state_origin());
+        uint64_t seq_pos = UINT64_MAX;                                          // where seq stands; UINT64_MAX: nowhere
+        for (int t = 0; t < n; t++)
+            for (int b = tab[t].block0; b < tab[t].block0 + tab[t].nblocks; b++) {
+                audio_hiss_window(hb[b], seq, seq_pos, block_pos[(size_t)b], blocks[b].first * cfg.channels, blocks[b].frames * cfg.channels);
+                max_items = std::max(max_items, hb[b].items);
+            }
+    }
+    for (int t = 0; t < n; t++) max_frames = std::max(max_frames, tab[t].frames);
+    if ((hiss && total * cfg.channels > k->hiss_cap) || (buzz && total > k->pulses_cap) || nseg > k->recs_cap) {
+        int grc = k->slots.wait_all(v);                                         // launches in flight use what is replaced
+        if (grc == NTSCSIM_OK && hiss) grc = audio_grow(v, k->hiss, k->hiss_cap, (size_t)total * cfg.channels);
+        if (grc == NTSCSIM_OK && buzz) grc = audio_grow(v, k->pulses, k->pulses_cap, (size_t)total);
+        if (grc == NTSCSIM_OK) grc = audio_grow(v, k->recs, k->recs_cap, (size_t)nseg);
+        if (grc != NTSCSIM_OK) return grc;
+    }
+    STAGECHK(v, hipMemcpyAsync(slot->dev, slot->host, tab_bytes + blocks_bytes + hb_bytes, hipMemcpyHostToDevice, st));
+    AudioTracksCall call;
+    call.c = cfg;
+    call.tracks = reinterpret_cast<const AudioTrackEnt *>(slot->dev);
+    call.blocks = reinterpret_cast<const AudioBlock *>(slot->dev + tab_bytes);
+    call.hiss = hiss ? k->hiss : nullptr;
+    call.pulses = buzz ? k->pulses : nullptr;
+    call.nseg = nseg;
+    call.ntracks = n;
+    int lrc = audio_mark(v, k, st);
+    if (lrc != NTSCSIM_OK) return lrc;
+    if (hiss) {
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + tab_bytes + blocks_bytes), (int)m, max_items, k->polys, cfg.hiss_level, k->hiss, st);
+        lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
+        if (lrc != NTSCSIM_OK) return lrc;
+    }
+    if (buzz) {
+        const dim3 grid((unsigned)std::min<uint64_t>((max_frames + 255) / 256, 65535), (unsigned)std::min(n, 1024));
+        hipLaunchKernelGGL(k_audio_track_pulses, grid, dim3(256), 0, st, cfg, call.tracks, n, k->pulses);
+        lrc = stage_launched(v, nullptr, st, "k_audio_track_pulses");
+        if (lrc != NTSCSIM_OK) return lrc;
+    }
+    lrc = audio_mark(v, k, st);
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_audio_track_segments, dim3((unsigned)((nseg + AUDIO_GROUPS - 1) / AUDIO_GROUPS)), dim3(64), 0, st, call, k->recs, L, W);
+    lrc = stage_launched(v, nullptr, st, "k_audio_track_segments");
+    if (lrc == NTSCSIM_OK) lrc = audio_mark(v, k, st);
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_audio_track_verify, dim3((unsigned)n), dim3(64), 0, st, call, k->recs, L, W, k->track_stats);
+    lrc = stage_launched(v, slot, st, "k_audio_track_verify");
+    return lrc == NTSCSIM_OK ? audio_mark(v, k, st) : lrc;
+}
+
 AudioStageState *audio_of(ntscsim_ctx *c) { return c ? *ctx_stage_view(c).audio : nullptr; }
 
 } // namespace
@@ -598,6 +873,14 @@ extern "C" int ntscsim_audio_device(ntscsim_ctx *c, const ntscsim_audio_desc *de
     CtxStageView v = ctx_stage_view(c);
     if (!*v.audio) return NTSCSIM_E_ARG;                                        // ntscsim_audio_bind() first
     return audio_blocks(c, descs, n, hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream);
+}
+
+extern "C" int ntscsim_audio_tracks_device(ntscsim_ctx *c, const ntscsim_audio_track *tracks, int n_tracks, void *hip_stream)
+{
+    if (!c || n_tracks < 0 || (n_tracks > 0 && !tracks)) return NTSCSIM_E_ARG;
+    CtxStageView v = ctx_stage_view(c);
+    if (!*v.audio) return NTSCSIM_E_ARG;                                        // ntscsim_audio_bind() first
+    return audio_tracks(c, tracks, n_tracks, hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream);
 }
 
 extern "C" int ntscsim_audio_host(ntscsim_ctx *c, int16_t *audio, uint32_t samples)
@@ -678,6 +961,19 @@ extern "C" int ntscsim_audio_debug_stats(ntscsim_ctx *c, ntscsim_audio_stats *ou
     STAGECHK(v, hipMemcpy(s, k->stats, sizeof(s), hipMemcpyDeviceToHost));
     out->segments = s[0];
     out->repaired = s[1];
+    return NTSCSIM_OK;
+}
+
+extern "C" int ntscsim_audio_debug_track_stats(ntscsim_ctx *c, ntscsim_audio_stats *out, int n_tracks)
+{
+    AudioStageState *k = audio_of(c);
+    if (!k || n_tracks < 0 || n_tracks > k->last_tracks || (n_tracks && !out)) return NTSCSIM_E_ARG;
+    if (n_tracks == 0) return NTSCSIM_OK;
+    CtxStageView v = ctx_stage_view(c);
+    const int rc = audio_quiet(v);
+    if (rc != NTSCSIM_OK) return rc;
+    static_assert(sizeof(ntscsim_audio_stats) == 2 * sizeof(uint64_t), "k_audio_track_verify writes ntscsim_audio_stats");
+    STAGECHK(v, hipMemcpy(out, k->track_stats, (size_t)n_tracks * sizeof(ntscsim_audio_stats), hipMemcpyDeviceToHost));
     return NTSCSIM_OK;
 }
 

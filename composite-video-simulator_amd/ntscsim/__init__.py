@@ -1005,6 +1005,74 @@ class AudioChain:
             stream = self.sim._torch_stream()
         self._call("device", arr, len(blocks), C.c_void_p(stream))
 
+    STATE_BYTES = C.sizeof(_capi.AudioState)
+
+    def process_tracks(self, srcs, dsts, states=None, blocks=None, stream=None):
+        """ntscsim_audio_tracks_device: srcs, dsts are lists of torch int16 CUDA tensors, contiguous, one pair per
+        independent track (lengths may differ).  states: None (every track starts from zeros and its end state is
+        dropped) or a contiguous CUDA tensor of len(srcs) * STATE_BYTES bytes (zero_states()), updated in place.
+        blocks: None, or per track None or a list shaped like process()'s.  Enqueues; does not synchronise."""
+        ch, n = self.channels, len(srcs)
+        assert len(dsts) == n and (blocks is None or len(blocks) == n)
+        base = 0
+        if states is not None:
+            assert states.is_cuda and states.is_contiguous() and states.numel() * states.element_size() == n * self.STATE_BYTES
+            base = states.data_ptr()
+        tracks = (_capi.AudioTrack * max(1, n))()
+        keep = []                                                               # the block arrays, alive until the call returns
+        for t, (src, dst) in enumerate(zip(srcs, dsts)):
+            total = src.numel() // ch
+            assert src.is_contiguous() and dst.is_contiguous() and dst.numel() == src.numel()
+            cut = blocks[t] if blocks is not None and blocks[t] is not None else [(total, None)]
+            assert sum(b[0] for b in cut) == total
+            arr = (_capi.AudioDesc * max(1, len(cut)))()
+            at = 0
+            for d, (frames, pos) in zip(arr, cut):
+                d.src = src.data_ptr() + at * ch * 2
+                d.dst = dst.data_ptr() + at * ch * 2
+                d.samples = int(frames)
+                d.rng_pos = RNG_AUTO if pos is None else int(pos)
+                at += int(frames)
+            keep.append(arr)
+            tracks[t].blocks = arr
+            tracks[t].n_blocks = len(cut)
+            tracks[t].state = base + t * self.STATE_BYTES if states is not None else None
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("tracks_device", tracks, n, C.c_void_p(stream))
+
+    def track_stats(self, n):
+        """[(segments, repaired segments)] of tracks 0 .. n-1 of the last process_tracks().  Synchronises."""
+        s = (_capi.AudioStats * max(1, int(n)))()
+        self._call("debug_track_stats", s, int(n))
+        return [(int(s[t].segments), int(s[t].repaired)) for t in range(int(n))]
+
+    @classmethod
+    def zero_states(cls, n, device="cuda"):
+        """A state tensor for process_tracks(): n tracks at the tool's start (zeros, count 0)."""
+        import torch
+        return torch.zeros(int(n) * cls.STATE_BYTES, dtype=torch.uint8, device=device)
+
+    @classmethod
+    def track_state(cls, states, t):
+        """(30 filter values as a tuple, sample count) of track t of a state tensor, as the `state` property gives
+        the ctx's.  Synchronises (a copy to the host)."""
+        import torch
+        raw = states.view(torch.uint8).reshape(-1)[t * cls.STATE_BYTES:(t + 1) * cls.STATE_BYTES].cpu().numpy().tobytes()
+        s = _capi.AudioState.from_buffer_copy(raw)
+        v = [x for c in s.bandpass for x in c] + list(s.pre) + list(s.post) + list(s.boost)
+        return tuple(v), int(s.count)
+
+    @classmethod
+    def set_track_state(cls, states, t, value):
+        """Write (30 filter values, sample count) into track t of a state tensor."""
+        import numpy as np
+        import torch
+        v, count = value
+        raw = np.array(v, np.float64).tobytes() + np.array([count], np.uint64).tobytes()
+        assert len(raw) == cls.STATE_BYTES
+        states.view(torch.uint8).reshape(-1)[t * cls.STATE_BYTES:(t + 1) * cls.STATE_BYTES] = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(states.device)
+
     def host(self, array):
         """ntscsim_audio_host: composite_audio_process(array, frames) in place on a numpy int16 array whose samples
         are contiguous (any alignment).  Synchronous."""

@@ -1685,6 +1685,33 @@ int  ntscsim_audio_bind(ntscsim_ctx *ctx, const ntscsim_audio_params *ap);
  * any src of the call (a warm-up reads input again).
  */
 int  ntscsim_audio_device(ntscsim_ctx *ctx, const ntscsim_audio_desc *descs, int n, void *hip_stream);
+/*
+ * Many independent streams in one call.  A track is what one ntscsim_audio_device() call takes: blocks that form ONE
+ * continuous stream.  The call equals, in bytes, end states and the ctx's rand() position, this sequence for
+ * t = 0 .. n_tracks-1 in order: ntscsim_audio_set_state(*tracks[t].state), ntscsim_audio_device(blocks of t),
+ * ntscsim_audio_get_state(tracks[t].state) -- but the tracks run side by side in one launch of each kernel, nothing
+ * waits for the device, and the ctx's own carried state is neither read nor written.  All tracks use the parameters of
+ * the last ntscsim_audio_bind().  rand() positions: as above, each block carries its own; NTSCSIM_RNG_AUTO continues
+ * from the ctx's position, tracks in order and blocks in order within a track; the ctx's position moves at call time.
+ * A track's sample count (the sync buzz) runs from its state's count.  Tracks without frames and blocks without
+ * samples may stand anywhere; a track without frames leaves its state as it is.  With enabled == 0 the call copies,
+ * draws nothing and leaves the states alone.  `tracks` and the block arrays are host memory, consumed by the call.
+ * Enqueued on hip_stream (NULL: the ctx's own stream), returns without synchronising.
+ * Kernels: k_audio_hiss, k_audio_track_pulses (when the buzz is on), k_audio_track_segments (group g of workgroup b
+ * takes segment 3 b + g of the call and finds its track in the track table), k_audio_track_verify (one workgroup per
+ * track: the verify / repair walk over that track's records, then its state).  The result never depends on the plan.
+ * NTSCSIM_E_ARG, before anything is enqueued or the rand() position moves: no ntscsim_audio_bind() before, n_tracks
+ * < 0, a NULL `tracks` or `blocks` that should hold something, a NULL or odd pointer in a block with samples, a state
+ * that is not 8-byte aligned, two tracks whose states overlap, a dst of any track that overlaps a src of any track.
+ */
+typedef struct ntscsim_audio_track {
+    const ntscsim_audio_desc *blocks;   /* host memory: this track's blocks, ONE continuous stream                    */
+    int32_t                   n_blocks;
+    int32_t                   _pad;
+    ntscsim_audio_state      *state;    /* DEVICE pointer, 8-byte aligned, read at the start and written at the end;
+                                           NULL: start from zeros / count 0, end state discarded                     */
+} ntscsim_audio_track;
+int  ntscsim_audio_tracks_device(ntscsim_ctx *ctx, const ntscsim_audio_track *tracks, int n_tracks, void *hip_stream);
 /* Drop-in for composite_audio_process(audio, samples): HOST memory, in place, through pinned staging of the ctx.
  * Synchronous.  The rand() position is the ctx's. */
 int  ntscsim_audio_host(ntscsim_ctx *ctx, int16_t *audio, uint32_t samples);
@@ -1698,9 +1725,13 @@ int  ntscsim_audio_set_state(ntscsim_ctx *ctx, const ntscsim_audio_state *in);
  * seg_len of 0 is the default length.  seg_len >= the call's frames is the serial form.  pulses: the device's pulse counts of frames count0 .. count0+n-1 (host `out`). */
 int  ntscsim_audio_debug_set_plan(ntscsim_ctx *ctx, uint32_t seg_len, uint32_t warmup);
 int  ntscsim_audio_debug_stats(ntscsim_ctx *ctx, ntscsim_audio_stats *out);
+/* stats of tracks 0 .. n_tracks-1 of the last ntscsim_audio_tracks_device() call (n_tracks beyond that call's:
+ * NTSCSIM_E_ARG).  Waits for the device. */
+int  ntscsim_audio_debug_track_stats(ntscsim_ctx *ctx, ntscsim_audio_stats *out, int n_tracks);
 int  ntscsim_audio_debug_pulses(ntscsim_ctx *ctx, uint64_t count0, uint32_t n, uint8_t *out);
 int  ntscsim_audio_debug_time_kernels(ntscsim_ctx *ctx, int on);
-/* (k_audio_hiss + k_audio_pulses, k_audio_segments, k_audio_verify_repair) milliseconds of the last call */
+/* (k_audio_hiss + k_audio_pulses, k_audio_segments, k_audio_verify_repair) milliseconds of the last call; after a
+ * tracks call (k_audio_hiss + k_audio_track_pulses, k_audio_track_segments, k_audio_track_verify) */
 int  ntscsim_audio_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[3]);
 
 /* ------------------------------------------------------------------------------------------

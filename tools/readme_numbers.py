@@ -125,7 +125,28 @@ def pixmap_rows(path="profiles/pixmap.json"):
              "`profiles/pixmap.json`, DESIGN.md §7k")]
 
 
-for row in (led_row, filmac_row):
+def audio_tracks_row(path="profiles/audio_tracks.json"):
+    """The row of many audio tracks in one call, from tools/bench_audio_tracks.py's file."""
+    j = json.load(open(path))
+    h, s = j["cases"]["hifi"], j["cases"]["linear_sp"]
+
+    def cell(c):
+        t, b = c["tracks_call"], c["b_single_track_of_the_total_length"]
+        km = t["kernel_ms"]
+        return (t["ms"], c["times_real_time"], c["a_one_call_per_track"]["ms"], c["a_over_tracks"], b["ms"], c["tracks_over_b"],
+                km["draws_and_pulses"], km["k_audio_track_segments"], km["k_audio_track_verify"], b["kernel_ms"]["k_audio_verify_repair"], t["repaired"])
+
+    return ("many audio tracks in one call (`ntscsim_audio_tracks_device`): %d independent tracks of %g s resident in HBM, each with its own state on the device "
+            "(`tools/bench_audio_tracks.py`); (a) the same tracks as one `ntscsim_audio_device` call each with `set_state` / `get_state` between them, wall clock; "
+            "(b) one `ntscsim_audio_device` call over a single track of the same total length; all in the same run" % (j["tracks"], j["frames_per_track"] / j["rate"]),
+            "stereo Hi-Fi: **%.1f ms** (%.0f × real time); (a) %.0f ms, so the one call is worth **%.1f ×**; (b) %.1f ms, the tracks call takes %.2f × that; "
+            "kernels: draws %.2f, segments %.1f, verify %.2f ms (the single track's walk: %.2f ms); %d segments repaired.  "
+            "Linear mono SP: %.1f ms (%.0f × real time); (a) %.0f ms, %.1f ×; (b) %.1f ms, %.2f ×; kernels: draws and pulses %.2f, segments %.1f, verify %.2f ms "
+            "(the single track's: %.2f ms); %d repaired.  Bytes and end states of every track equal (a)'s" % (cell(h) + cell(s)),
+            "`profiles/audio_tracks.json`, DESIGN.md §7l")
+
+
+for row in (led_row, filmac_row, audio_tracks_row):
     try:
         rows.append(row())
     except Exception:
