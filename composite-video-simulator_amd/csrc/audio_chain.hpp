@@ -220,9 +220,11 @@ inline void audio_run_span(const AudioCfg &c, AudioState &st, const int16_t *src
 }
 
 // Run, verify, repair: what k_audio_segments and k_audio_verify_repair do, in their order.  dst must not overlap src.
+// which (may be NULL): receives the segments that were repaired, in order.
 inline void audio_run_planned(const AudioCfg &c, AudioState &st, const int16_t *src, int16_t *dst, const int32_t *hiss, uint64_t total, uint32_t L,
-                              uint32_t W, AudioPlanStats *stats)
+                              uint32_t W, AudioPlanStats *stats, std::vector<uint64_t> *which = nullptr)
 {
+    if (which) which->clear();
     if (stats) stats->segments = stats->repaired = stats->worst_convergence = 0;
     if (!c.enabled) {
         std::memcpy(dst, src, (size_t)total * (size_t)c.channels * sizeof(int16_t));
@@ -245,6 +247,7 @@ inline void audio_run_planned(const AudioCfg &c, AudioState &st, const int16_t *
         if (!audio_state_same(at_start[(size_t)j], truth)) {
             audio_run_span(c, truth, src, dst, hiss, g.start, g.len);
             if (stats) stats->repaired++;
+            if (which) which->push_back(j);
         } else {
             truth = at_end[(size_t)j];
         }

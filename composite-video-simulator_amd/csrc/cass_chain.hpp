@@ -258,10 +258,14 @@ struct CassPlanStats {
 };
 
 // Run, verify, repair: what k_cass_front, k_cass_front_verify, k_cass_conv, k_cass_back and k_cass_back_verify do, in
-// their order and with the kernels' skipping FIR.  dst must not overlap src.
+// their order and with the kernels' skipping FIR.  dst must not overlap src.  which_front / which_back (may be NULL):
+// receive the segments that each pass repaired, in order.
 inline void cass_run_planned(const CassCfg &c, CassState &st, const int16_t *src, int16_t *dst, const int32_t *hiss, const double *tf, uint64_t total,
-                             uint32_t L, uint32_t Wf, uint32_t Wb, CassPlanStats *stats)
+                             uint32_t L, uint32_t Wf, uint32_t Wb, CassPlanStats *stats, std::vector<uint64_t> *which_front = nullptr,
+                             std::vector<uint64_t> *which_back = nullptr)
 {
+    if (which_front) which_front->clear();
+    if (which_back) which_back->clear();
     if (stats) stats->segments = stats->repaired_front = stats->repaired_back = 0;
     if (L == 0) L = 1;
     const uint64_t nseg = audio_seg_count(total, L);
@@ -283,6 +287,7 @@ inline void cass_run_planned(const CassCfg &c, CassState &st, const int16_t *src
             if (!cass_front_same(at_start[(size_t)j], truth)) {
                 cass_front_span(c, truth, src, xs.data(), hiss, g.start, g.len);
                 if (stats) stats->repaired_front++;
+                if (which_front) which_front->push_back(j);
             } else {
                 truth = at_end[(size_t)j];
             }
@@ -309,6 +314,7 @@ inline void cass_run_planned(const CassCfg &c, CassState &st, const int16_t *src
             if (!cass_back_same(at_start[(size_t)j], truth)) {
                 cass_back_span(c, truth, rs.data(), dst, g.start, g.len);
                 if (stats) stats->repaired_back++;
+                if (which_back) which_back->push_back(j);
             } else {
                 truth = at_end[(size_t)j];
             }

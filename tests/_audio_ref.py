@@ -163,6 +163,39 @@ def run_checker(ap, audio, count0=0, rng_pos=0, block=0, build="plain"):
     return out, (vals, count), pos
 
 
+def block_spec(blocks):
+    """[(frames, rand() position or None), ...] as the checkers read it behind blocks="""
+    return ",".join("%d:%s" % (n, "a" if p is None else p) for n, p in blocks)
+
+
+def run_tracks_checker(ap, tracks, counts=None, pos=0, blocks=None, build="plain"):
+    """run_checker per track, each from zeros at its count, the rand() position running through, in ONE run of the
+    checker (its `tracks` mode; tests/test_audio_limits_host.py holds it against run_checker per track):
+    ([(output, (30 state values, count))], rand() position behind the last)."""
+    ch = ap.channels
+    frames = [len(a) for a in tracks]
+    whole = np.concatenate([np.ascontiguousarray(a).reshape(-1, ch) for a in tracks]) if tracks else np.zeros((0, ch), np.int16)
+    with tempfile.TemporaryDirectory(prefix="audio_run_") as d:
+        cfg, inp, outp, spec = os.path.join(d, "cfg"), os.path.join(d, "in"), os.path.join(d, "out"), os.path.join(d, "spec")
+        write_cfg(cfg, ap)
+        whole.tofile(inp)
+        with open(spec, "w") as f:
+            for t, n in enumerate(frames):
+                f.write("%d %d %s\n" % (n, counts[t] if counts else 0, block_spec(blocks[t]) if blocks is not None and blocks[t] is not None else "-"))
+        r = subprocess.run([checker(build), "tracks", cfg, inp, outp, str(pos), spec], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout
+        out = np.fromfile(outp, np.int16).reshape(-1, ch)
+    lines = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("state ")]
+    assert len(lines) == len(frames), r.stdout
+    res, at = [], 0
+    for n, ln in zip(frames, lines):
+        vals = np.array([int(x, 16) for x in ln[1:31]], np.uint64).view(np.float64)
+        res.append((out[at:at + n], (tuple(float(v) for v in vals), int(ln[32]))))
+        pos = int(ln[34])
+        at += n
+    return res, pos
+
+
 def run_checker_mode(mode, ap, audio, *args, build="plain"):
     """planned / converge: (return code, output text)."""
     with tempfile.TemporaryDirectory(prefix="audio_run_") as d:
@@ -171,6 +204,29 @@ def run_checker_mode(mode, ap, audio, *args, build="plain"):
         np.ascontiguousarray(audio).tofile(inp)
         r = subprocess.run([checker(build), mode, cfg, inp] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     return r.returncode, r.stdout
+
+
+def plan(ap, audio, seg_len, warmup, count0=0, rng_pos=0, build="plain"):
+    """((segments, repaired), [the repaired segments]) of one planned call on the host (audio_run_planned)."""
+    rc, out = run_checker_mode("plan", ap, audio, count0, rng_pos, seg_len, warmup, build=build)
+    assert rc == 0, out
+    w = out.split()
+    assert w[0] == "plan:" and w[5] == "which", out
+    which = [int(x) for x in w[6:]]
+    assert len(which) == int(w[4]), out
+    return (int(w[2]), int(w[4])), which
+
+
+def plan_stats(ap, audio, seg_len, warmup, count0=0, rng_pos=0):
+    """(segments, repaired) of one planned call on the host: what the device's stats must say for the same plan."""
+    return plan(ap, audio, seg_len, warmup, count0, rng_pos)[0]
+
+
+def mixed_repairs(segments, which):
+    """The condition of a mixed plan: some segments are repaired, not all that could be (the first never is), and at
+    least one accepted segment directly follows a repaired one -- it is accepted against the truth a repair produced."""
+    w = set(which)
+    return 0 < len(w) < segments - 1 and any(j + 1 < segments and j + 1 not in w for j in w)
 
 
 def host_pulses(ap, count0, n):

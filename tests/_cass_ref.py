@@ -174,3 +174,15 @@ def plan_stats(cp, audio, seg_len, warmup_front, warmup_back, count0=0, rng_pos=
     assert rc == 0, out
     w = out.split()
     return int(w[2]), int(w[4]), int(w[6])
+
+
+def plan(cp, audio, seg_len, warmup_front, warmup_back, count0=0, rng_pos=0, build="plain"):
+    """(plan_stats, [segments the front repaired], [segments the back repaired]) of one planned call on the host."""
+    rc, out = run_checker_mode("plan", cp, audio, count0, rng_pos, seg_len, warmup_front, warmup_back, build=build)
+    assert rc == 0, out
+    w = out.split()
+    assert w[0] == "plan:" and w[7] == "which_front" and "which_back" in w, out
+    b = w.index("which_back")
+    front, back = [int(x) for x in w[8:b]], [int(x) for x in w[b + 1:]]
+    assert len(front) == int(w[4]) and len(back) == int(w[6]), out
+    return (int(w[2]), int(w[4]), int(w[6])), front, back

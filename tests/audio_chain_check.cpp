@@ -7,6 +7,12 @@
 //                                                               prints the final state, the sample count and the rand() position
 //   audio_chain_check planned  CFG IN COUNT0 RNGPOS NONSILENT   plan + run + verify + repair for L x W, over calls of unequal
 //                                                               length, against the serial run; prints "<n> bad"
+//   audio_chain_check tracks   CFG IN OUT RNGPOS SPEC           `serial` per track, each from zeros: the tracks lie back to back
+//                                                               in IN, SPEC is a file with a line "FRAMES COUNT0 BLOCKS" per track
+//                                                               (BLOCKS as behind blocks=, or - for one block); the rand() position
+//                                                               runs through; prints a state line per track
+//   audio_chain_check plan     CFG IN COUNT0 RNGPOS L W         one planned call; prints its segments, its repairs and which
+//                                                               segments were repaired
 //   audio_chain_check converge CFG IN COUNT0 RNGPOS             frames a zero-state run needs to meet the true states bit for
 //                                                               bit, from 24 start points; prints the worst and the default W
 //   audio_chain_check pulses   CFG COUNT0 N OUT                 audio_pulse_count() of N frames as bytes
@@ -65,6 +71,30 @@ static void print_state(const AudioState &st, uint64_t pos)
     std::printf(" count %" PRIu64 " pos %" PRIu64 "\n", st.count, pos);
 }
 
+// FRAMES:POS,... -- the chain serially over `frames` frames at a, a call per block; POS "a": where the stream stands
+static bool run_blocks(const AudioCfg &c, AudioState &st, int16_t *a, uint64_t frames, const char *spec, uint64_t &pos)
+{
+    RandSeq seq(rand_state_at(pos));
+    uint64_t f = 0;
+    for (const char *p = spec; *p;) {
+        char *e;
+        const uint64_t n = std::strtoull(p, &e, 10);
+        if (*e != ':' || f + n > frames) return false;
+        p = e + 1;
+        if (*p == 'a') p++;
+        else {
+            pos = std::strtoull(p, &e, 10);
+            seq = RandSeq(rand_state_at(pos));
+            p = e;
+        }
+        if (*p == ',') p++;
+        int16_t *q = a + f * c.channels;
+        audio_run_serial(c, st, q, q, n, [&]() { pos++; return seq.next(); });
+        f += n;
+    }
+    return f == frames;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 3) return 2;
@@ -91,27 +121,10 @@ int main(int argc, char **argv)
         std::memset(&st, 0, sizeof(st));
         st.count = std::strtoull(argv[5], nullptr, 10);
         uint64_t pos = std::strtoull(argv[6], nullptr, 10);
-        RandSeq seq(rand_state_at(pos));
-        if (!std::strncmp(argv[7], "blocks=", 7)) {                             // FRAMES:POS,... -- POS "a": where the stream stands
-            uint64_t f = 0;
-            for (const char *p = argv[7] + 7; *p;) {
-                char *e;
-                const uint64_t n = std::strtoull(p, &e, 10);
-                if (*e != ':' || f + n > frames) return 2;
-                p = e + 1;
-                if (*p == 'a') p++;
-                else {
-                    pos = std::strtoull(p, &e, 10);
-                    seq = RandSeq(rand_state_at(pos));
-                    p = e;
-                }
-                if (*p == ',') p++;
-                int16_t *q = a.data() + f * c.channels;
-                audio_run_serial(c, st, q, q, n, [&]() { pos++; return seq.next(); });
-                f += n;
-            }
-            if (f != frames) return 2;
+        if (!std::strncmp(argv[7], "blocks=", 7)) {
+            if (!run_blocks(c, st, a.data(), frames, argv[7] + 7, pos)) return 2;
         } else {
+            RandSeq seq(rand_state_at(pos));
             uint64_t block = std::strtoull(argv[7], nullptr, 10);
             if (block == 0) block = frames ? frames : 1;
             for (uint64_t f = 0; f < frames; f += block) {
@@ -125,6 +138,56 @@ int main(int argc, char **argv)
         std::fwrite(a.data(), 2, (size_t)frames * c.channels, f);
         std::fclose(f);
         print_state(st, pos);
+        return 0;
+    }
+    if (mode == "tracks" && argc == 7) {                                        // `serial` per track, the tracks back to back in IN
+        std::vector<int16_t> a = read_s16(argv[3]);
+        const uint64_t frames = a.size() / c.channels;
+        uint64_t pos = std::strtoull(argv[5], nullptr, 10), at = 0;
+        FILE *spec = std::fopen(argv[6], "r");
+        if (!spec) return 2;
+        std::vector<char> blocks(1 << 20);
+        unsigned long long n, count0;
+        while (std::fscanf(spec, "%llu %llu %1048575s", &n, &count0, blocks.data()) == 3) {
+            AudioState st;
+            std::memset(&st, 0, sizeof(st));
+            st.count = count0;
+            const std::string one = std::to_string(n) + ":a";
+            if (at + n > frames || !run_blocks(c, st, a.data() + at * c.channels, n, blocks[0] == '-' ? one.c_str() : blocks.data(), pos)) {
+                std::fclose(spec);
+                return 2;
+            }
+            at += n;
+            print_state(st, pos);
+        }
+        std::fclose(spec);
+        if (at != frames) return 2;
+        FILE *f = std::fopen(argv[4], "wb");
+        if (!f) return 2;
+        std::fwrite(a.data(), 2, (size_t)frames * c.channels, f);
+        std::fclose(f);
+        return 0;
+    }
+    if (mode == "plan" && argc == 8) {                                          // one planned call: what the device's stats must say
+        const std::vector<int16_t> in = read_s16(argv[3]);
+        const uint64_t frames = in.size() / c.channels;
+        AudioState st;
+        std::memset(&st, 0, sizeof(st));
+        st.count = std::strtoull(argv[4], nullptr, 10);
+        std::vector<int32_t> hiss;
+        if (c.hiss_level != 0 && c.enabled) {
+            RandSeq seq(rand_state_at(std::strtoull(argv[5], nullptr, 10)));
+            hiss.resize((size_t)frames * c.channels);
+            for (int32_t &h : hiss) h = audio_hiss_num(seq.next(), c.hiss_level);
+        }
+        std::vector<int16_t> out(in.size() + 1);
+        AudioPlanStats ps;
+        std::vector<uint64_t> which;
+        audio_run_planned(c, st, in.data(), out.data(), hiss.empty() ? nullptr : hiss.data(), frames, (uint32_t)std::strtoul(argv[6], nullptr, 10),
+                          (uint32_t)std::strtoul(argv[7], nullptr, 10), &ps, &which);
+        std::printf("plan: segments %" PRIu64 " repaired %" PRIu64 " which", ps.segments, ps.repaired);
+        for (uint64_t j : which) std::printf(" %" PRIu64, j);
+        std::printf("\n");
         return 0;
     }
     if ((mode == "planned" && argc == 7) || (mode == "converge" && argc == 6)) {

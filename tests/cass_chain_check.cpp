@@ -7,7 +7,8 @@
 //                                                                    block, a = as it stands); prints the final state
 //   cass_chain_check planned  CFG IN COUNT0 RNGPOS NONSILENT SINES   plan + run + verify + repair for L x (Wf, Wb), over calls of
 //                                                                    unequal length, against the serial run; prints "<n> bad"
-//   cass_chain_check plan     CFG IN COUNT0 RNGPOS L WF WB SINES     one planned call; prints its segments and repairs
+//   cass_chain_check plan     CFG IN COUNT0 RNGPOS L WF WB SINES     one planned call; prints its segments, its repairs and
+//                                                                    which segments each pass repaired
 //   cass_chain_check converge CFG IN COUNT0 RNGPOS SINES            frames a zero-state run of the front and of the back needs to
 //                                                                    meet the true states bit for bit; prints the worst of each
 //   cass_chain_check sines    CFG COUNT0 N OUT                       this host's sin() of N frames from COUNT0, as doubles
@@ -177,9 +178,14 @@ int main(int argc, char **argv)
         }
         std::vector<int16_t> out(in.size() + 1);
         CassPlanStats ps;
+        std::vector<uint64_t> which_front, which_back;
         cass_run_planned(c, st[0], in.data(), out.data(), hiss.empty() ? nullptr : hiss.data(), tf.data(), frames, (uint32_t)std::strtoul(argv[6], nullptr, 10),
-                         (uint32_t)std::strtoul(argv[7], nullptr, 10), (uint32_t)std::strtoul(argv[8], nullptr, 10), &ps);
-        std::printf("plan: segments %" PRIu64 " front %" PRIu64 " back %" PRIu64 "\n", ps.segments, ps.repaired_front, ps.repaired_back);
+                         (uint32_t)std::strtoul(argv[7], nullptr, 10), (uint32_t)std::strtoul(argv[8], nullptr, 10), &ps, &which_front, &which_back);
+        std::printf("plan: segments %" PRIu64 " front %" PRIu64 " back %" PRIu64 " which_front", ps.segments, ps.repaired_front, ps.repaired_back);
+        for (uint64_t j : which_front) std::printf(" %" PRIu64, j);
+        std::printf(" which_back");
+        for (uint64_t j : which_back) std::printf(" %" PRIu64, j);
+        std::printf("\n");
         return 0;
     }
     if ((mode == "planned" && argc == 8) || (mode == "converge" && argc == 7)) {

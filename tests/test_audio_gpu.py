@@ -107,6 +107,7 @@ def test_stage_pipeline_edges(sim, which):
             assert_same(chain, got, want, st, "L %d W %d" % (seg, warm))
             assert sim.rng_pos == pos
             assert chain.stats()[0] == (3000 + seg - 1) // seg
+            assert chain.stats() == A.plan_stats(ap, a, seg, warm, rng_pos=3), "L %d W %d" % (seg, warm)
     # 1, 2, 3, 4 and 7 segments in wavefronts of three, the last of one frame
     for frames in (64, 128, 192, 193, 6 * 64 + 1):
         w2, s2, _ = A.run_checker(ap, a[:frames], rng_pos=3)
@@ -116,6 +117,7 @@ def test_stage_pipeline_edges(sim, which):
         got = run_device(chain, a[:frames])
         assert_same(chain, got, w2, s2, "%d frames" % frames)
         assert chain.stats()[0] == (frames + 63) // 64
+        assert chain.stats() == A.plan_stats(ap, a[:frames], 64, 20, rng_pos=3), "%d frames" % frames
 
 
 def test_repair_path(sim):
@@ -129,6 +131,7 @@ def test_repair_path(sim):
     assert_same(chain, got, want, st)
     segments, repaired = chain.stats()
     assert segments == 12 and repaired == segments - 1
+    assert (segments, repaired) == A.plan_stats(ap, a, 256, 0)
     # silence without hiss: a zero state IS the true state, nothing to repair
     ap0 = params(["-audio-hiss", "-200"])
     assert ap0.hiss_level == 0
@@ -137,7 +140,7 @@ def test_repair_path(sim):
     chain0.set_plan(256, 0)
     got = run_device(chain0, z)
     assert not got.any()
-    assert chain0.stats() == (12, 0)
+    assert chain0.stats() == (12, 0) == A.plan_stats(ap0, z, 256, 0)
 
 
 def test_blocks_calls_and_resume(sim):
