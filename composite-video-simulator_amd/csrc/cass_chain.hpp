@@ -9,7 +9,9 @@
 // de-emphasis states by the back alone and the FIR has a delay line per channel, so running the three as passes over a
 // call's frames computes what the interleaved loop computes, draw for draw.  DESIGN.md 7m.
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <utility>
 
 #include "audio_chain.hpp"
 
@@ -323,6 +325,246 @@ inline void cass_run_planned(const CassCfg &c, CassState &st, const int16_t *src
     }
     cass_plane_end(c, st, xs, total);
     if (stats) stats->segments = nseg;
+}
+
+// ------------------------------------------------------------------------------------------------ many tracks
+// A tracks call (ntscsim_cass_tracks_device) puts independent streams side by side, as audio_chain.hpp's does: each track
+// is planned on its own, exactly as a call of its frames alone would be, and the segments of all tracks -- and the FIR's
+// tiles -- are numbered through, so that one launch of each kernel runs them.  What the cassette adds: a delay line per
+// track (every track has a section of the x plane of its own: its taps - 1 history frames, then its frames), tiles that
+// never cross a track, and one table of head_tilt_final over the UNION of the tracks' sample counts.
+
+constexpr uint32_t CASS_TILE_FRAMES = 256;   // frames of a tile of the FIR (a workgroup of k_cass_conv / k_cass_track_conv)
+
+struct CassTrackEnt {
+    uint64_t frames;                     // of the track
+    uint64_t plane;                      // its first frame in the PLANE: the frames of all tracks numbered through, which the
+                                         // call's hiss and r scratch and the blocks' `first` are indexed by
+    uint64_t seg0;                       // its first segment in the call-wide numbering
+    uint64_t tile0;                      // its first FIR tile in the call-wide numbering
+    uint64_t xs;                         // frame offset of its section of the x plane: taps - 1 history frames, then its frames
+    uint64_t tilt;                       // offset of its first frame in the call's tilt table
+    uint64_t count;                      // audio_proc_count of its first frame: the HOST's, never read from the state
+    CassState *state;                    // carried state: read at the start, written at the end; NULL: zeros, end discarded
+    int32_t block0, nblocks;             // its blocks in the call's block array (a block's `first` counts in the plane)
+};
+
+struct CassTracksTotals {
+    uint64_t frames, segments, tiles, xs_frames;   // of the call; xs_frames: the x plane, histories included
+};
+
+// fills plane, seg0, tile0 and xs of tab[0..n) from the frames.  Every track has a section of the x plane, one without
+// frames too (its history alone: nothing reads it).
+inline CassTracksTotals cass_tracks_layout(CassTrackEnt *tab, int n, uint32_t L, int taps)
+{
+    CassTracksTotals z{0, 0, 0, 0};
+    for (int t = 0; t < n; t++) {
+        tab[t].plane = z.frames;
+        tab[t].seg0 = z.segments;
+        tab[t].tile0 = z.tiles;
+        tab[t].xs = z.xs_frames;
+        z.frames += tab[t].frames;
+        z.segments += audio_seg_count(tab[t].frames, L);
+        z.tiles += audio_seg_count(tab[t].frames, CASS_TILE_FRAMES);
+        z.xs_frames += (uint64_t)(taps - 1) + tab[t].frames;
+    }
+    return z;
+}
+
+// The track of call-wide segment j / of call-wide tile i (below the call's totals): the LAST t whose seg0 / tile0 is not
+// above it, as audio_track_of().  Tracks without frames share their index with the track behind them, so the last one is
+// the one that owns it.
+AUDIO_HD int cass_track_of_seg(const CassTrackEnt *tab, int n, uint64_t j)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (tab[mid].seg0 <= j) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+AUDIO_HD int cass_track_of_tile(const CassTrackEnt *tab, int n, uint64_t i)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (tab[mid].tile0 <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The tilt table holds head_tilt_final of every sample count that some track covers, once: the tracks' ranges
+// [count, count + frames) merged into disjoint runs in ascending order, the runs back to back in the table.
+struct CassTiltRun {
+    uint64_t count0, n, at;              // counts [count0, count0 + n) stand at table entries [at, at + n)
+};
+
+// Fills tab[t].tilt (0 for a track without frames) and the runs; *total: entries of the table = sines to evaluate.
+// false: count + frames of a track overflows 64 bits (nothing is filled in then).
+inline bool cass_tilt_layout(CassTrackEnt *tab, int n, std::vector<CassTiltRun> &runs, uint64_t *total)
+{
+    runs.clear();
+    *total = 0;
+    std::vector<std::pair<uint64_t, int>> order;                                // (count, track) of the tracks that have frames
+    for (int t = 0; t < n; t++) {
+        if (tab[t].count + tab[t].frames < tab[t].count) return false;
+        if (tab[t].frames) order.push_back({tab[t].count, t});
+    }
+    std::sort(order.begin(), order.end());
+    for (const std::pair<uint64_t, int> &o : order) {
+        const int t = o.second;
+        const uint64_t a = tab[t].count, b = a + tab[t].frames;
+        if (runs.empty() || a > runs.back().count0 + runs.back().n) runs.push_back(CassTiltRun{a, b - a, *total});
+        else if (b > runs.back().count0 + runs.back().n) runs.back().n = b - runs.back().count0;
+        *total = runs.back().at + runs.back().n;
+        tab[t].tilt = runs.back().at + (a - runs.back().count0);
+    }
+    for (int t = 0; t < n; t++)
+        if (!tab[t].frames) tab[t].tilt = 0;
+    return true;
+}
+
+// entries [at, at + n) of the table: what one thread of the fill evaluates
+inline void cass_fill_tilt_part(const CassCfg &c, const CassTiltRun *runs, size_t nruns, uint64_t at, uint64_t n, double *tf)
+{
+    for (size_t r = 0; r < nruns && n; r++) {
+        if (runs[r].at + runs[r].n <= at) continue;
+        const uint64_t skip = at - runs[r].at, m = runs[r].n - skip < n ? runs[r].n - skip : n;
+        cass_fill_tilt(c, runs[r].count0 + skip, m, tf + at);
+        at += m;
+        n -= m;
+    }
+}
+
+inline CassState cass_track_carried(const CassTrackEnt &e)
+{
+    CassState z;
+    if (e.state) z = *e.state;
+    else std::memset(&z, 0, sizeof(z));
+    z.front.count = e.count;                                                    // the state's own count is not read
+    return z;
+}
+
+struct CassTrackIO {                     // host: one track of cass_run_tracks_planned()
+    const int16_t *src;
+    int16_t *dst;                        // must not overlap any src
+    const int32_t *hiss;                 // numerators of the track (NULL: no hiss)
+    uint64_t frames, count;
+    CassState *state;                    // as CassTrackEnt's
+};
+
+// Run, verify, repair over a set of tracks: what k_cass_track_front (every call-wide segment, found through
+// cass_track_of_seg), k_cass_track_front_verify (each track's records walked from its own true state, its history laid
+// in front of its section), k_cass_track_conv (every call-wide tile, found through cass_track_of_tile, the tilt through
+// the track's table offset; the track's new history), k_cass_track_back and k_cass_track_back_verify do, in their
+// order.  stats[t]: of track t.  tilt_frames (may be NULL): the sines evaluated.  false: a count overflows; nothing ran.
+inline bool cass_run_tracks_planned(const CassCfg &c, const CassTrackIO *tracks, int n, uint32_t L, uint32_t Wf, uint32_t Wb, CassPlanStats *stats,
+                                    uint64_t *tilt_frames = nullptr)
+{
+    for (int t = 0; t < n; t++) stats[t].segments = stats[t].repaired_front = stats[t].repaired_back = 0;
+    if (L == 0) L = 1;
+    const uint64_t h = (uint64_t)(c.taps - 1);
+    std::vector<CassTrackEnt> tab((size_t)n);
+    for (int t = 0; t < n; t++) {
+        std::memset(&tab[(size_t)t], 0, sizeof(CassTrackEnt));
+        tab[(size_t)t].frames = tracks[t].frames;
+        tab[(size_t)t].count = tracks[t].count;
+        tab[(size_t)t].state = tracks[t].state;
+        tab[(size_t)t].block0 = t;                                              // the host has one block per track
+        tab[(size_t)t].nblocks = 1;
+    }
+    std::vector<CassTiltRun> runs;
+    uint64_t tilt_total = 0;
+    if (!cass_tilt_layout(tab.data(), n, runs, &tilt_total)) return false;
+    if (tilt_frames) *tilt_frames = tilt_total;
+    const CassTracksTotals z = cass_tracks_layout(tab.data(), n, L, c.taps);
+    std::vector<double> tf((size_t)tilt_total + 1), xs((size_t)z.xs_frames * 2 + 2, 0.0), rs((size_t)z.frames * 2 + 2);
+    cass_fill_tilt_part(c, runs.data(), runs.size(), 0, tilt_total, tf.data());
+    {
+        std::vector<CassFront> at_start((size_t)z.segments), at_end((size_t)z.segments);
+        for (uint64_t j = 0; j < z.segments; j++) {                             // the speculative front
+            const int t = cass_track_of_seg(tab.data(), n, j);
+            const CassTrackEnt &e = tab[(size_t)t];
+            const AudioSeg g = audio_seg(e.frames, L, Wf, j - e.seg0);
+            const CassFront carried = cass_track_carried(e).front;
+            CassFront s = g.run_start == 0 ? carried : cass_front_spec(c, carried, g.run_start);
+            cass_front_span(c, s, tracks[t].src, nullptr, tracks[t].hiss, g.run_start, g.start - g.run_start);
+            at_start[(size_t)j] = s;
+            cass_front_span(c, s, tracks[t].src, xs.data() + e.xs * 2, tracks[t].hiss, g.start, g.len);
+            at_end[(size_t)j] = s;
+        }
+        for (int t = 0; t < n; t++) {                                           // verify, repair: per track
+            const CassTrackEnt &e = tab[(size_t)t];
+            if (!e.frames) continue;
+            const CassState carried = cass_track_carried(e);
+            for (uint64_t k = 0; k < h; k++)
+                for (int ch = 0; ch < CASS_CHANNELS; ch++) xs[(size_t)(e.xs + k) * 2 + ch] = carried.hist[k][ch];
+            const uint64_t nt = audio_seg_count(e.frames, L);
+            CassFront truth = carried.front;
+            for (uint64_t j = 0; j < nt; j++) {
+                const AudioSeg g = audio_seg(e.frames, L, Wf, j);
+                if (!cass_front_same(at_start[(size_t)(e.seg0 + j)], truth)) {
+                    cass_front_span(c, truth, tracks[t].src, xs.data() + e.xs * 2, tracks[t].hiss, g.start, g.len);
+                    stats[t].repaired_front++;
+                } else {
+                    truth = at_end[(size_t)(e.seg0 + j)];
+                }
+            }
+            if (e.state) e.state->front = truth;                               // count: e.count + e.frames by now
+            stats[t].segments = nt;
+        }
+    }
+    for (uint64_t i = 0; i < z.tiles; i++) {                                    // the FIR by tile
+        const CassTrackEnt &e = tab[(size_t)cass_track_of_tile(tab.data(), n, i)];
+        const uint64_t first = (i - e.tile0) * CASS_TILE_FRAMES, own = e.frames - first < CASS_TILE_FRAMES ? e.frames - first : CASS_TILE_FRAMES;
+        cass_conv_span<true>(c, xs.data() + e.xs * 2, tf.data() + e.tilt, rs.data() + e.plane * 2, first, own);
+    }
+    if (!c.post) {
+        for (int t = 0; t < n; t++) {
+            CassBack none = cass_track_carried(tab[(size_t)t]).back;
+            cass_back_span(c, none, rs.data() + tab[(size_t)t].plane * 2, tracks[t].dst, 0, tab[(size_t)t].frames);
+        }
+    } else {
+        std::vector<CassBack> at_start((size_t)z.segments), at_end((size_t)z.segments);
+        for (uint64_t j = 0; j < z.segments; j++) {                             // the speculative back
+            const int t = cass_track_of_seg(tab.data(), n, j);
+            const CassTrackEnt &e = tab[(size_t)t];
+            const AudioSeg g = audio_seg(e.frames, L, Wb, j - e.seg0);
+            CassBack s = cass_track_carried(e).back;
+            if (g.run_start != 0) s.post[0] = s.post[1] = 0;
+            cass_back_span(c, s, rs.data() + e.plane * 2, nullptr, g.run_start, g.start - g.run_start);
+            at_start[(size_t)j] = s;
+            cass_back_span(c, s, rs.data() + e.plane * 2, tracks[t].dst, g.start, g.len);
+            at_end[(size_t)j] = s;
+        }
+        for (int t = 0; t < n; t++) {
+            const CassTrackEnt &e = tab[(size_t)t];
+            if (!e.frames) continue;
+            const uint64_t nt = audio_seg_count(e.frames, L);
+            CassBack truth = cass_track_carried(e).back;
+            for (uint64_t j = 0; j < nt; j++) {
+                const AudioSeg g = audio_seg(e.frames, L, Wb, j);
+                if (!cass_back_same(at_start[(size_t)(e.seg0 + j)], truth)) {
+                    cass_back_span(c, truth, rs.data() + e.plane * 2, tracks[t].dst, g.start, g.len);
+                    stats[t].repaired_back++;
+                } else {
+                    truth = at_end[(size_t)(e.seg0 + j)];
+                }
+            }
+            if (e.state) e.state->back = truth;
+        }
+    }
+    for (int t = 0; t < n; t++) {                                               // the history, the count, the taps
+        const CassTrackEnt &e = tab[(size_t)t];
+        if (!e.frames || !e.state) continue;
+        for (uint64_t k = 0; k < h; k++)
+            for (int ch = 0; ch < CASS_CHANNELS; ch++) e.state->hist[k][ch] = xs[(size_t)(e.xs + e.frames + k) * 2 + ch];
+        e.state->front.count = e.count + e.frames;
+        e.state->taps = (uint32_t)c.taps;
+    }
+    return true;
 }
 
 } // namespace ntscsim

@@ -8,6 +8,7 @@
 // sits on the beat of the lane pipeline.  BACK (the two shared de-emphasis poles, pack, downmix) is a recurrence of two
 // values: one lane per segment, a short warm-up, k_cass_back_verify behind it.  head_tilt_final of every frame comes
 // from the host (libm sin), never from the device.
+// ntscsim_cass_tracks_device() runs many such streams side by side through a track table (k_cass_track_*).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -364,6 +365,209 @@ __global__ __launch_bounds__(64) void k_cass_back_verify(CassCall k, const doubl
     stats[2] = repaired;
 }
 
+// ---------------------------------------------------------------------------------------- many tracks
+// ntscsim_cass_tracks_device(): independent streams side by side (the track table of cass_chain.hpp).  The kernels above
+// stay the single stream's; these hand the same cass_run_lanes / cass_back_run a track's VIEW.  The tracks are laid into
+// one frame numbering, the PLANE (track t owns frames [plane_t, plane_t + frames_t) of it): the hiss and r scratch and
+// the blocks' `first` are indexed by it.  The x plane is not: every track has a section of its own there, its taps - 1
+// history frames in front of its frames, so a view's xs is shifted until the plane's numbering lands in that section.
+static_assert(CASS_TILE == (int)CASS_TILE_FRAMES, "the tiles of the track table are k_cass_track_conv's");
+
+struct CassTracksCall {
+    CassCfg c;
+    const CassTrackEnt *tracks;
+    const CassBlock *blocks;             // of all tracks, `first` in the plane
+    const int32_t *hiss;                 // per channel-sample of the plane, NULL without hiss
+    double *xs;                          // the tracks' sections
+    uint64_t nseg;                       // segments of the call
+    int ntracks;
+};
+
+__device__ __forceinline__ CassCall cass_track_view(const CassTracksCall &k, const CassTrackEnt &e)
+{
+    CassCall v;
+    v.c = k.c;
+    v.blocks = k.blocks + e.block0;                                             // cass_seek and cass_find stay inside the track
+    v.hiss = k.hiss;
+    v.xs = k.xs + ((int64_t)e.xs - (int64_t)e.plane) * 2;                       // plane frame plane_t + f: entry taps - 1 + f of the section
+    v.total = e.plane + e.frames;                                               // where the track ends in the plane
+    v.nblocks = e.nblocks;
+    return v;
+}
+
+// One wavefront per workgroup; group g of workgroup b takes call-wide segment 3 b + g, whatever track it belongs to.
+__global__ __launch_bounds__(64) void k_cass_track_front(CassTracksCall k, CassFrontRec *__restrict__ recs, uint32_t seg_len, uint32_t warmup)
+{
+    __shared__ int32_t ring[CASS_GROUPS + 1][2][CASS_RING];
+    __shared__ double init[CASS_GROUPS + 1][CASS_FRONT_VALUES];
+    const int lane = (int)threadIdx.x, g = lane / CASS_LANES, r = lane - g * CASS_LANES;
+    const uint64_t j = (uint64_t)blockIdx.x * CASS_GROUPS + (uint64_t)g;
+    const bool live = g < CASS_GROUPS && j < k.nseg;
+    CassTrackEnt e{0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0};
+    AudioSeg s{0, 0, 0};
+    if (live) {
+        e = k.tracks[cass_track_of_seg(k.tracks, k.ntracks, j)];
+        s = audio_seg(e.frames, seg_len, warmup, j - e.seg0);                    // clamps at frame 0 of this track
+        const bool spec = s.run_start != 0;
+        for (int i = r; i < CASS_FRONT_VALUES; i += CASS_LANES) {
+            const double v = (spec && cass_front_live(k.c, i)) || !e.state ? 0.0 : e.state->front.v[i];
+            init[g][i] = v;
+            recs[j].at_start.v[i] = v;
+            recs[j].at_end.v[i] = v;
+        }
+        if (r == 0) {
+            recs[j].at_start.count = e.count + s.start;                         // the table's count, not the state's
+            recs[j].at_end.count = e.count + s.start + s.len;
+        }
+    }
+    __syncthreads();
+    const CassCall view = cass_track_view(k, e);
+    cass_run_lanes(view, r, live, e.plane + s.run_start, s.start - s.run_start, s.len, init[g], live ? &recs[j].at_start : nullptr,
+                   live ? &recs[j].at_end : nullptr, ring[g][0], ring[g][1]);
+}
+
+// One workgroup (one wavefront) per track: the walk of k_cass_front_verify over that track's records, from that track's
+// true state, behind laying that track's carried history in front of its section.  A track without frames is left alone.
+__global__ __launch_bounds__(64) void k_cass_track_front_verify(CassTracksCall k, const CassFrontRec *__restrict__ recs, uint32_t seg_len, uint32_t warmup,
+                                                                uint64_t *__restrict__ stats)
+{
+    __shared__ int32_t ring[2][CASS_RING];
+    __shared__ CassFront truth;
+    __shared__ double init[CASS_FRONT_VALUES];
+    const int lane = (int)threadIdx.x;
+    const CassTrackEnt e = k.tracks[blockIdx.x];
+    if (e.frames == 0) return;
+    const CassCall view = cass_track_view(k, e);
+    const uint64_t nseg = audio_seg_count(e.frames, seg_len);
+    recs += e.seg0;
+    double *const sec = k.xs + e.xs * 2;
+    for (int i = lane; i < (k.c.taps - 1) * 2; i += 64) sec[i] = e.state ? e.state->hist[i >> 1][i & 1] : 0.0;
+    if (lane < CASS_FRONT_VALUES) truth.v[lane] = e.state ? e.state->front.v[lane] : 0.0;
+    if (lane == CASS_FRONT_VALUES) truth.count = e.count;
+    __syncthreads();
+    uint64_t repaired = 0;
+    for (uint64_t j = 0; j < nseg; j++) {
+        bool same = true;
+        if (lane < CASS_FRONT_VALUES) same = __double_as_longlong(recs[j].at_start.v[lane]) == __double_as_longlong(truth.v[lane]);
+        if (lane == CASS_FRONT_VALUES) same = recs[j].at_start.count == truth.count;
+        const bool ok = __all(same);
+        __syncthreads();
+        if (ok) {
+            if (lane < CASS_FRONT_VALUES) truth.v[lane] = recs[j].at_end.v[lane];
+            if (lane == CASS_FRONT_VALUES) truth.count = recs[j].at_end.count;
+        } else {
+            const AudioSeg s = audio_seg(e.frames, seg_len, warmup, j);
+            if (lane < CASS_FRONT_VALUES) init[lane] = truth.v[lane];
+            __syncthreads();
+            cass_run_lanes(view, lane, lane < CASS_LANES, e.plane + s.start, 0, s.len, init, nullptr, &truth, ring[0], ring[1]);
+            if (lane == 0) truth.count += s.len;
+            repaired++;
+        }
+        __syncthreads();
+    }
+    if (e.state && lane < CASS_FRONT_VALUES) e.state->front.v[lane] = truth.v[lane];
+    if (lane == 0) stats[CASS_STAT_VALUES * (uint64_t)blockIdx.x + 1] = repaired;
+}
+
+// what the last kernel of a track leaves behind the filter values: the count, the taps, the segments
+__device__ __forceinline__ void cass_track_close(const CassCfg &c, const CassTrackEnt &e, uint32_t seg_len, uint64_t *__restrict__ stats, uint64_t t)
+{
+    if (e.state) {
+        e.state->front.count = e.count + e.frames;
+        e.state->taps = (uint32_t)c.taps;
+    }
+    stats[CASS_STAT_VALUES * t] = audio_seg_count(e.frames, seg_len);
+}
+
+// One workgroup per call-wide tile, found through the track table: a tile never crosses a track, and the taps - 1
+// frames in front of a track's first tile are that track's history.  The tilt is read through the track's offset in the
+// table.  The first tile of a track also makes the last taps - 1 entries of the section the track's history -- for a track
+// shorter than that, part of them are the old history that k_cass_track_front_verify laid there -- and, when no back
+// follows, closes the track.
+__global__ __launch_bounds__(CASS_TILE) void k_cass_track_conv(CassTracksCall k, const double *__restrict__ tf, double *__restrict__ rs, uint32_t seg_len,
+                                                               uint64_t *__restrict__ stats)
+{
+    __shared__ double tile[2][CASS_TILE + CASS_HIST];
+    const int t = (int)threadIdx.x, taps = k.c.taps;
+    const int tr = cass_track_of_tile(k.tracks, k.ntracks, (uint64_t)blockIdx.x);
+    const CassTrackEnt e = k.tracks[tr];
+    const uint64_t tile0 = ((uint64_t)blockIdx.x - e.tile0) * CASS_TILE;        // in the track
+    const int own = (int)(e.frames - tile0 < CASS_TILE ? e.frames - tile0 : CASS_TILE);
+    const double *sec = k.xs + e.xs * 2;
+    const double *src = sec + tile0 * 2;                                        // section entry tile0 is frame tile0 - (taps - 1)
+    for (int i = t; i < (own + taps - 1) * 2; i += CASS_TILE) tile[i & 1][i >> 1] = src[i];
+    __syncthreads();
+    if (t < own) {
+        const uint64_t f = tile0 + (uint64_t)t;
+        const double h = tf[e.tilt + f];
+        const double r0 = cass_conv<true>(taps, h, 0, &tile[0][t], 1);
+        const double r1 = cass_conv<true>(taps, h, 1, &tile[1][t], 1);
+        if (rs) {
+            rs[(e.plane + f) * 2] = r0;
+            rs[(e.plane + f) * 2 + 1] = r1;
+        } else {
+            int16_t o0 = audio_pack(r0), o1 = audio_pack(r1);
+            cass_downmix(k.c, o0, o1);
+            const CassCall view = cass_track_view(k, e);
+            const CassBlock &b = view.blocks[cass_find(view, e.plane + f)];
+            int16_t *d = b.dst + (e.plane + f - b.first) * 2;
+            d[0] = o0;
+            d[1] = o1;
+        }
+    }
+    if (tile0 == 0) {
+        if (e.state)
+            for (int i = t; i < (taps - 1) * 2; i += CASS_TILE) e.state->hist[i >> 1][i & 1] = sec[e.frames * 2 + (uint64_t)i];
+        if (!rs && t == 0) cass_track_close(k.c, e, seg_len, stats, (uint64_t)tr);
+    }
+}
+
+// one lane per call-wide segment
+__global__ __launch_bounds__(64) void k_cass_track_back(CassTracksCall k, const double *__restrict__ rs, CassBackRec *__restrict__ recs, uint32_t seg_len,
+                                                        uint32_t warmup)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k.nseg) return;
+    const CassTrackEnt e = k.tracks[cass_track_of_seg(k.tracks, k.ntracks, j)];
+    const CassCall view = cass_track_view(k, e);
+    const AudioSeg s = audio_seg(e.frames, seg_len, warmup, j - e.seg0);
+    CassBack b{{0.0, 0.0}};
+    if (e.state && s.run_start == 0) b = e.state->back;
+    cass_back_run(view, b, rs, e.plane + s.run_start, s.start - s.run_start, false);
+    recs[j].at_start = b;
+    cass_back_run(view, b, rs, e.plane + s.start, s.len, true);
+    recs[j].at_end = b;
+}
+
+// one lane per track: the ordered walk of k_cass_back_verify over that track's records; it closes the track
+__global__ __launch_bounds__(64) void k_cass_track_back_verify(CassTracksCall k, const double *__restrict__ rs, const CassBackRec *__restrict__ recs,
+                                                               uint32_t seg_len, uint32_t warmup, uint64_t *__restrict__ stats)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)k.ntracks) return;
+    const CassTrackEnt e = k.tracks[t];
+    if (e.frames == 0) return;
+    const CassCall view = cass_track_view(k, e);
+    const uint64_t nseg = audio_seg_count(e.frames, seg_len);
+    recs += e.seg0;
+    CassBack truth{{0.0, 0.0}};
+    if (e.state) truth = e.state->back;
+    uint64_t repaired = 0;
+    for (uint64_t j = 0; j < nseg; j++) {
+        const CassBackRec rec = recs[j];
+        if (cass_back_same(rec.at_start, truth)) {
+            truth = rec.at_end;
+        } else {
+            const AudioSeg s = audio_seg(e.frames, seg_len, warmup, j);
+            cass_back_run(view, truth, rs, e.plane + s.start, s.len, true);
+            repaired++;
+        }
+    }
+    if (e.state) e.state->back = truth;
+    stats[CASS_STAT_VALUES * t + 2] = repaired;
+    cass_track_close(k.c, e, seg_len, stats, t);
+}
+
 // ---------------------------------------------------------------------------------------- host side
 constexpr int CASS_MARKS = 9;
 constexpr int CASS_FILL_THREADS = 4;     // of the sin() fill of a long call; fixed, whatever the host has
@@ -376,6 +580,10 @@ struct CassStageState {
     uint64_t count = 0;                  // the host's copy of its sample count: the sines are made here
     uint32_t *polys = nullptr;           // device: HISS_POLYS polynomials
     uint64_t *stats = nullptr;           // device: segments, repaired front, repaired back of the last call
+    uint64_t *track_stats = nullptr;     // device: the same three per track of the last tracks call
+    size_t track_stats_cap = 0;          // in values
+    int last_tracks = 0;
+    uint64_t tilt_frames = 0;            // sines the last call's fill evaluated
     int32_t *hiss = nullptr;
     double *xs = nullptr, *rs = nullptr, *tf = nullptr;
     CassFrontRec *frecs = nullptr;
@@ -406,6 +614,7 @@ void cass_state_destroy(CassStageState *k)
     if (k->state) (void)hipFree(k->state);
     if (k->polys) (void)hipFree(k->polys);
     if (k->stats) (void)hipFree(k->stats);
+    if (k->track_stats) (void)hipFree(k->track_stats);
     if (k->hiss) (void)hipFree(k->hiss);
     if (k->xs) (void)hipFree(k->xs);
     if (k->rs) (void)hipFree(k->rs);
@@ -474,9 +683,9 @@ int cass_mark(const CtxStageView &v, CassStageState *k, hipStream_t st)
     return NTSCSIM_OK;
 }
 
-// head_tilt_final of the call's frames into the pinned staging (frames are independent: a long call is split over a
-// fixed number of threads), then up on the call's stream
-int cass_upload_tilt(const CtxStageView &v, CassStageState *k, uint64_t total, hipStream_t st)
+// head_tilt_final of the `total` table entries that the runs describe into the pinned staging (entries are independent: a
+// long table is split over a fixed number of threads), then up on the call's stream
+int cass_upload_tilt_runs(const CtxStageView &v, CassStageState *k, const CassTiltRun *runs, size_t nruns, uint64_t total, hipStream_t st)
 {
     if (k->tf_used) STAGECHK(v, hipEventSynchronize(k->tf_done));                // the last upload still reads the staging
     if (total > k->tf_host_cap) {
@@ -488,17 +697,18 @@ int cass_upload_tilt(const CtxStageView &v, CassStageState *k, uint64_t total, h
     if (!k->tf_done) STAGECHK(v, hipEventCreateWithFlags(&k->tf_done, hipEventDisableTiming));
     const auto t0 = std::chrono::steady_clock::now();
     if (total < CASS_FILL_SPLIT) {
-        cass_fill_tilt(k->cfg, k->count, total, k->tf_host);
+        cass_fill_tilt_part(k->cfg, runs, nruns, 0, total, k->tf_host);
     } else {
         std::thread helpers[CASS_FILL_THREADS - 1];
         const uint64_t part = (total + CASS_FILL_THREADS - 1) / CASS_FILL_THREADS;
         for (int i = 1; i < CASS_FILL_THREADS; i++) {
             const uint64_t at = std::min<uint64_t>(part * (uint64_t)i, total), n = std::min<uint64_t>(part, total - at);
-            helpers[i - 1] = std::thread([k, at, n]() { cass_fill_tilt(k->cfg, k->count + at, n, k->tf_host + at); });
+            helpers[i - 1] = std::thread([k, runs, nruns, at, n]() { cass_fill_tilt_part(k->cfg, runs, nruns, at, n, k->tf_host); });
         }
-        cass_fill_tilt(k->cfg, k->count, std::min<uint64_t>(part, total), k->tf_host);
+        cass_fill_tilt_part(k->cfg, runs, nruns, 0, std::min<uint64_t>(part, total), k->tf_host);
         for (std::thread &h : helpers) h.join();
     }
+    k->tilt_frames = total;
     k->fill_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     int rc = cass_mark(v, k, st);
     if (rc != NTSCSIM_OK) return rc;
@@ -506,6 +716,13 @@ int cass_upload_tilt(const CtxStageView &v, CassStageState *k, uint64_t total, h
     STAGECHK(v, hipEventRecord(k->tf_done, st));
     k->tf_used = true;
     return cass_mark(v, k, st);
+}
+
+// the single stream's table: one run from the host's copy of the count
+int cass_upload_tilt(const CtxStageView &v, CassStageState *k, uint64_t total, hipStream_t st)
+{
+    const CassTiltRun one{k->count, total, 0};
+    return cass_upload_tilt_runs(v, k, &one, 1, total, st);
 }
 
 int cass_blocks(ntscsim_ctx *c, const ntscsim_cass_desc *descs, int n, hipStream_t st)
@@ -637,6 +854,175 @@ int cass_blocks(ntscsim_ctx *c, const ntscsim_cass_desc *descs, int n, hipStream
     return lrc;
 }
 
+// ntscsim_cass_tracks_device(): n independent streams in one launch of each kernel
+int cass_tracks(ntscsim_ctx *c, const ntscsim_cass_track *tracks, int n, hipStream_t st)
+{
+    CtxStageView v = ctx_stage_view(c);
+    CassStageState *k = *v.cass;
+    const CassCfg &cfg = k->cfg;
+    const size_t fbytes = 2 * sizeof(int16_t);
+    // every track and descriptor checked before anything is enqueued or the rand() position moves
+    std::vector<Span> srcs;
+    std::vector<uintptr_t> states;
+    uint64_t total = 0;
+    size_t m = 0;                                                               // blocks that have frames
+    for (int t = 0; t < n; t++) {
+        const ntscsim_cass_track &tr = tracks[t];
+        if (tr.n_blocks < 0 || (tr.n_blocks > 0 && !tr.blocks) || ((uintptr_t)tr.state & 7)) return NTSCSIM_E_ARG;
+        if (tr.state) states.push_back((uintptr_t)tr.state);
+        uint64_t frames = 0;
+        for (int i = 0; i < tr.n_blocks; i++) {
+            const ntscsim_cass_desc &d = tr.blocks[i];
+            if (d.samples == 0) continue;
+            if (!d.src || !d.dst || (((uintptr_t)d.src | (uintptr_t)d.dst) & 1)) return NTSCSIM_E_ARG;
+            srcs.push_back(Span{(uintptr_t)d.src, (uintptr_t)d.src + (size_t)d.samples * fbytes});
+            frames += d.samples;
+            m++;
+        }
+        if (tr.count + frames < tr.count) return NTSCSIM_E_ARG;                 // the count would wrap inside the track
+        total += frames;
+    }
+    if (m > (size_t)INT32_MAX) return NTSCSIM_E_ARG;
+    std::sort(states.begin(), states.end());
+    for (size_t i = 1; i < states.size(); i++)
+        if (states[i] - states[i - 1] < sizeof(CassState)) return NTSCSIM_E_ARG;    // two tracks would share a state
+    std::sort(srcs.begin(), srcs.end(), [](const Span &x, const Span &y) { return x.a < y.a; });
+    std::vector<uintptr_t> reach(srcs.size());                                  // the furthest end among srcs[0..i]
+    for (size_t i = 0; i < srcs.size(); i++) reach[i] = std::max(srcs[i].b, i ? reach[i - 1] : 0);
+    for (int t = 0; t < n; t++)
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_cass_desc &d = tracks[t].blocks[i];
+            if (d.samples == 0) continue;
+            const uintptr_t a = (uintptr_t)d.dst, b = a + (size_t)d.samples * fbytes;
+            const size_t at = (size_t)(std::lower_bound(srcs.begin(), srcs.end(), b, [](const Span &x, uintptr_t e) { return x.a < e; }) - srcs.begin());
+            if (at > 0 && reach[at - 1] > a) return NTSCSIM_E_ARG;              // a warm-up reads input again, in any track
+        }
+    STAGECHK(v, hipSetDevice(v.device));
+    if ((size_t)CASS_STAT_VALUES * (size_t)n > k->track_stats_cap) {
+        int rc = k->slots.wait_all(v);                                          // launches in flight use what is replaced
+        if (rc == NTSCSIM_OK) rc = cass_grow(v, k->track_stats, k->track_stats_cap, (size_t)CASS_STAT_VALUES * (size_t)n);
+        if (rc != NTSCSIM_OK) return rc;
+    }
+    v.kernels->clear();
+    cass_drop_marks(k);
+    k->last_tracks = n;
+    k->tilt_frames = 0;
+    const bool hiss = cfg.hiss_level != 0, post = cfg.post != 0;
+    const uint32_t L = k->plan_len ? k->plan_len : AUDIO_DEFAULT_SEG;
+    const uint32_t Wf = k->plan_set ? k->plan_front : cass_default_front_warmup(cfg);
+    const uint32_t Wb = k->plan_set ? k->plan_back : CASS_DEFAULT_BACK_WARMUP;
+    // the rand() position moves at call time, whatever becomes of the launch: tracks in order, blocks in order
+    uint64_t pos = ntscsim_get_rng_pos(c);
+    std::vector<uint64_t> block_pos;
+    block_pos.reserve(m);
+    for (int t = 0; t < n; t++)
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_cass_desc &d = tracks[t].blocks[i];
+            if (d.rng_pos != NTSCSIM_RNG_AUTO) pos = d.rng_pos;
+            if (d.samples) block_pos.push_back(pos);
+            if (hiss) pos += (uint64_t)d.samples * 2;
+        }
+    ntscsim_set_rng_pos(c, pos);
+    if (n) STAGECHK(v, hipMemsetAsync(k->track_stats, 0, (size_t)n * CASS_STAT_VALUES * sizeof(uint64_t), st));
+    if (total == 0) return NTSCSIM_OK;
+    // records: the track table, the blocks that have frames, their rand() windows
+    const size_t tab_bytes = (size_t)n * sizeof(CassTrackEnt), blocks_bytes = m * sizeof(CassBlock), hb_bytes = hiss ? m * sizeof(AudioHissBlock) : 0;
+    RecordSlot *slot = nullptr;
+    const int rc = k->slots.acquire(v, tab_bytes + blocks_bytes + hb_bytes, slot);
+    if (rc != NTSCSIM_OK) return rc;
+    CassTrackEnt *tab = reinterpret_cast<CassTrackEnt *>(slot->host);
+    CassBlock *blocks = reinterpret_cast<CassBlock *>(slot->host + tab_bytes);
+    AudioHissBlock *hb = reinterpret_cast<AudioHissBlock *>(slot->host + tab_bytes + blocks_bytes);
+    int o = 0;
+    uint64_t total_before = 0;                                                  // = the plane of the track, as cass_tracks_layout() sets it
+    for (int t = 0; t < n; t++) {
+        CassTrackEnt &e = tab[t];
+        std::memset(&e, 0, sizeof(e));
+        e.count = tracks[t].count;
+        e.state = reinterpret_cast<CassState *>(tracks[t].state);
+        e.block0 = o;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_cass_desc &d = tracks[t].blocks[i];
+            if (d.samples == 0) continue;
+            blocks[o++] = CassBlock{d.src, d.dst, total_before + e.frames, d.samples};   // first: in the plane
+            e.frames += d.samples;
+        }
+        e.nblocks = o - e.block0;
+        total_before += e.frames;
+    }
+    const CassTracksTotals z = cass_tracks_layout(tab, n, L, cfg.taps);
+    std::vector<CassTiltRun> runs;
+    uint64_t tilt_total = 0;
+    if (!cass_tilt_layout(tab, n, runs, &tilt_total)) return NTSCSIM_E_ARG;      // checked above: not reached
+    uint64_t max_items = 0;
+    if (hiss) {
+        RandSeq seq(rand_state_origin());
+        uint64_t seq_pos = UINT64_MAX;                                          // where seq stands; UINT64_MAX: nowhere
+        for (size_t b = 0; b < m; b++) {
+            audio_hiss_window(hb[b], seq, seq_pos, block_pos[b], blocks[b].first * 2, blocks[b].frames * 2);
+            max_items = std::max(max_items, hb[b].items);
+        }
+    }
+    if ((hiss && z.frames * 2 > k->hiss_cap) || z.xs_frames * 2 > k->xs_cap || (post && z.frames * 2 > k->rs_cap) || tilt_total > k->tf_cap ||
+        z.segments > k->frecs_cap || (post && z.segments > k->brecs_cap)) {
+        int grc = k->slots.wait_all(v);                                         // launches in flight use what is replaced
+        if (grc == NTSCSIM_OK && hiss) grc = cass_grow(v, k->hiss, k->hiss_cap, (size_t)z.frames * 2);
+        if (grc == NTSCSIM_OK) grc = cass_grow(v, k->xs, k->xs_cap, (size_t)z.xs_frames * 2);
+        if (grc == NTSCSIM_OK && post) grc = cass_grow(v, k->rs, k->rs_cap, (size_t)z.frames * 2);
+        if (grc == NTSCSIM_OK) grc = cass_grow(v, k->tf, k->tf_cap, (size_t)tilt_total);
+        if (grc == NTSCSIM_OK) grc = cass_grow(v, k->frecs, k->frecs_cap, (size_t)z.segments);
+        if (grc == NTSCSIM_OK && post) grc = cass_grow(v, k->brecs, k->brecs_cap, (size_t)z.segments);
+        if (grc != NTSCSIM_OK) return grc;
+    }
+    STAGECHK(v, hipMemcpyAsync(slot->dev, slot->host, tab_bytes + blocks_bytes + hb_bytes, hipMemcpyHostToDevice, st));
+    CassTracksCall call;
+    call.c = cfg;
+    call.tracks = reinterpret_cast<const CassTrackEnt *>(slot->dev);
+    call.blocks = reinterpret_cast<const CassBlock *>(slot->dev + tab_bytes);
+    call.hiss = hiss ? k->hiss : nullptr;
+    call.xs = k->xs;
+    call.nseg = z.segments;
+    call.ntracks = n;
+    int lrc = cass_mark(v, k, st);                                              // 0
+    if (lrc != NTSCSIM_OK) return lrc;
+    if (hiss) {
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + tab_bytes + blocks_bytes), (int)m, max_items, k->polys, cfg.hiss_level, k->hiss, st);
+        lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
+        if (lrc != NTSCSIM_OK) return lrc;
+    }
+    lrc = cass_mark(v, k, st);                                                  // 1
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_cass_track_front, dim3((unsigned)((z.segments + CASS_GROUPS - 1) / CASS_GROUPS)), dim3(64), 0, st, call, k->frecs, L, Wf);
+    lrc = stage_launched(v, nullptr, st, "k_cass_track_front");
+    if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                           // 2
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_cass_track_front_verify, dim3((unsigned)n), dim3(64), 0, st, call, k->frecs, L, Wf, k->track_stats);
+    lrc = stage_launched(v, nullptr, st, "k_cass_track_front_verify");
+    if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                           // 3
+    if (lrc != NTSCSIM_OK) return lrc;
+    // only the FIR reads the head tilt: the host's sin() fill -- over the union of the tracks' counts, which the host knows
+    // without asking the device -- runs while the front is at work there
+    lrc = cass_upload_tilt_runs(v, k, runs.data(), runs.size(), tilt_total, st);   // 4, 5
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_cass_track_conv, dim3((unsigned)z.tiles), dim3(CASS_TILE), 0, st, call, k->tf, post ? k->rs : (double *)nullptr, L, k->track_stats);
+    lrc = stage_launched(v, post ? nullptr : slot, st, "k_cass_track_conv");
+    if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                           // 6
+    if (lrc != NTSCSIM_OK) return lrc;
+    if (post) {
+        hipLaunchKernelGGL(k_cass_track_back, dim3((unsigned)((z.segments + 63) / 64)), dim3(64), 0, st, call, k->rs, k->brecs, L, Wb);
+        lrc = stage_launched(v, nullptr, st, "k_cass_track_back");
+        if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                       // 7
+        if (lrc != NTSCSIM_OK) return lrc;
+        hipLaunchKernelGGL(k_cass_track_back_verify, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, call, k->rs, k->brecs, L, Wb, k->track_stats);
+        lrc = stage_launched(v, slot, st, "k_cass_track_back_verify");
+        if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                       // 8
+    } else {
+        lrc = cass_mark(v, k, st);
+        if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);
+    }
+    return lrc;
+}
+
 CassStageState *cass_of(ntscsim_ctx *c) { return c ? *ctx_stage_view(c).cass : nullptr; }
 
 int cass_put_state(const CtxStageView &v, CassStageState *k, const CassState &s)
@@ -684,6 +1070,17 @@ extern "C" int ntscsim_cass_device(ntscsim_ctx *c, const ntscsim_cass_desc *desc
     CtxStageView v = ctx_stage_view(c);
     if (!*v.cass) return NTSCSIM_E_ARG;                                         // ntscsim_cass_bind() first
     return cass_blocks(c, descs, n, hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream);
+}
+
+static_assert(sizeof(ntscsim_cass_track) == 32 && offsetof(ntscsim_cass_track, count) == 16 && offsetof(ntscsim_cass_track, state) == 24,
+              "ntscsim_cass_track is what ntscsim/_capi.py mirrors");
+
+extern "C" int ntscsim_cass_tracks_device(ntscsim_ctx *c, const ntscsim_cass_track *tracks, int n_tracks, void *hip_stream)
+{
+    if (!c || n_tracks < 0 || (n_tracks > 0 && !tracks)) return NTSCSIM_E_ARG;
+    CtxStageView v = ctx_stage_view(c);
+    if (!*v.cass) return NTSCSIM_E_ARG;                                         // ntscsim_cass_bind() first
+    return cass_tracks(c, tracks, n_tracks, hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream);
 }
 
 extern "C" int ntscsim_cass_host(ntscsim_ctx *c, int16_t *audio, uint32_t samples)
@@ -770,6 +1167,27 @@ extern "C" int ntscsim_cass_debug_stats(ntscsim_ctx *c, ntscsim_cass_stats *out)
     out->segments = s[0];
     out->repaired_front = s[1];
     out->repaired_back = s[2];
+    return NTSCSIM_OK;
+}
+
+extern "C" int ntscsim_cass_debug_track_stats(ntscsim_ctx *c, ntscsim_cass_stats *out, int n_tracks)
+{
+    CassStageState *k = cass_of(c);
+    if (!k || n_tracks < 0 || n_tracks > k->last_tracks || (n_tracks && !out)) return NTSCSIM_E_ARG;
+    if (n_tracks == 0) return NTSCSIM_OK;
+    CtxStageView v = ctx_stage_view(c);
+    const int rc = cass_quiet(v);
+    if (rc != NTSCSIM_OK) return rc;
+    static_assert(sizeof(ntscsim_cass_stats) == CASS_STAT_VALUES * sizeof(uint64_t), "the track kernels write ntscsim_cass_stats");
+    STAGECHK(v, hipMemcpy(out, k->track_stats, (size_t)n_tracks * sizeof(ntscsim_cass_stats), hipMemcpyDeviceToHost));
+    return NTSCSIM_OK;
+}
+
+extern "C" int ntscsim_cass_debug_tilt_frames(ntscsim_ctx *c, uint64_t *evaluated)
+{
+    CassStageState *k = cass_of(c);
+    if (!k || !evaluated) return NTSCSIM_E_ARG;
+    *evaluated = k->tilt_frames;
     return NTSCSIM_OK;
 }
 

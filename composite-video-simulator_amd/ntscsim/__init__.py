@@ -1192,6 +1192,90 @@ class Cassette:
             stream = self.sim._torch_stream()
         self._call("device", arr, len(blocks), C.c_void_p(stream))
 
+    STATE_BYTES = C.sizeof(_capi.CassState)
+
+    def process_tracks(self, srcs, dsts, counts, states=None, blocks=None, stream=None):
+        """ntscsim_cass_tracks_device: srcs, dsts are lists of torch int16 CUDA tensors, contiguous, one pair per
+        independent track (lengths may differ).  counts: the sample count of every track's first frame, which the caller
+        keeps (the sines are made from it on the host; the count inside a state is not read).  states: None (every
+        track starts from zeros and its end state is dropped) or a contiguous CUDA tensor of len(srcs) * STATE_BYTES
+        bytes (zero_states()), updated in place.  blocks: None, or per track None or a list shaped like process()'s.
+        Enqueues; does not synchronise."""
+        n = len(srcs)
+        assert len(dsts) == n and len(counts) == n and (blocks is None or len(blocks) == n)
+        base = 0
+        if states is not None:
+            assert states.is_cuda and states.is_contiguous() and states.numel() * states.element_size() == n * self.STATE_BYTES
+            base = states.data_ptr()
+        tracks = (_capi.CassTrack * max(1, n))()
+        keep = []                                                               # the block arrays, alive until the call returns
+        for t, (src, dst) in enumerate(zip(srcs, dsts)):
+            total = src.numel() // 2
+            assert src.is_contiguous() and dst.is_contiguous() and dst.numel() == src.numel()
+            cut = blocks[t] if blocks is not None and blocks[t] is not None else [(total, None)]
+            assert sum(b[0] for b in cut) == total
+            arr = (_capi.CassDesc * max(1, len(cut)))()
+            at = 0
+            for d, (frames, pos) in zip(arr, cut):
+                d.src = src.data_ptr() + at * 4
+                d.dst = dst.data_ptr() + at * 4
+                d.samples = int(frames)
+                d.rng_pos = RNG_AUTO if pos is None else int(pos)
+                at += int(frames)
+            keep.append(arr)
+            tracks[t].blocks = arr
+            tracks[t].n_blocks = len(cut)
+            tracks[t].count = int(counts[t])
+            tracks[t].state = base + t * self.STATE_BYTES if states is not None else None
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("tracks_device", tracks, n, C.c_void_p(stream))
+
+    def track_stats(self, n):
+        """[(segments, segments the front repaired, segments the back repaired)] of tracks 0 .. n-1 of the last
+        process_tracks().  Synchronises."""
+        s = (_capi.CassStats * max(1, int(n)))()
+        self._call("debug_track_stats", s, int(n))
+        return [(int(s[t].segments), int(s[t].repaired_front), int(s[t].repaired_back)) for t in range(int(n))]
+
+    def tilt_frames(self):
+        """Sines the last call's host fill evaluated: for process_tracks() the union of the tracks' count ranges."""
+        out = C.c_uint64(0)
+        self._call("debug_tilt_frames", C.byref(out))
+        return int(out.value)
+
+    @classmethod
+    def zero_states(cls, n, device="cuda"):
+        """A state tensor for process_tracks(): n tracks at the tool's start (zeros)."""
+        import torch
+        return torch.zeros(int(n) * cls.STATE_BYTES, dtype=torch.uint8, device=device)
+
+    def track_state(self, states, t):
+        """(28 filter values, sample count, history of taps - 1 pairs) of track t of a state tensor, as the `state`
+        property gives the ctx's.  Synchronises (a copy to the host)."""
+        import torch
+        raw = states.view(torch.uint8).reshape(-1)[t * self.STATE_BYTES:(t + 1) * self.STATE_BYTES].cpu().numpy().tobytes()
+        s = _capi.CassState.from_buffer_copy(raw)
+        v = [x for c in s.bandpass for x in c] + list(s.pre) + list(s.post)
+        return tuple(v), int(s.count), tuple((s.history[k][0], s.history[k][1]) for k in range(self.taps - 1))
+
+    def set_track_state(self, states, t, value):
+        """Write (28 filter values, sample count, history pairs) into track t of a state tensor; the rest of the
+        history is zeroed and taps is the bound one."""
+        import torch
+        v, count, hist = value
+        s = _capi.CassState()
+        for c in range(2):
+            for i in range(12):
+                s.bandpass[c][i] = v[c * 12 + i]
+        for i in range(2):
+            s.pre[i], s.post[i] = v[24 + i], v[26 + i]
+        s.count = int(count)
+        s.taps = self.taps
+        for k, (a, b) in enumerate(hist):
+            s.history[k][0], s.history[k][1] = a, b
+        states.view(torch.uint8).reshape(-1)[t * self.STATE_BYTES:(t + 1) * self.STATE_BYTES] = torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(states.device)
+
     def host(self, array):
         """ntscsim_cass_host: composite_audio_process(array, frames) in place on a numpy int16 array whose samples are
         contiguous (any alignment).  Synchronous."""
@@ -1246,7 +1330,8 @@ class Cassette:
 
     def kernel_ms(self):
         """(host sin fill, its upload, k_audio_hiss, k_cass_front, k_cass_front_verify, k_cass_conv, k_cass_back,
-        k_cass_back_verify) milliseconds of the last call."""
+        k_cass_back_verify) milliseconds of the last call; after process_tracks() the same slots hold the
+        k_cass_track_* kernels'."""
         out = (C.c_float * 8)()
         self._call("debug_kernel_ms", out)
         return tuple(float(v) for v in out)

@@ -76,6 +76,7 @@ EXPORTS = (
     "ntscsim_cass_params_init", "ntscsim_cass_parse_argv", "ntscsim_cass_params_derive", "ntscsim_cass_bind", "ntscsim_cass_device",
     "ntscsim_cass_host", "ntscsim_cass_reset", "ntscsim_cass_get_state", "ntscsim_cass_set_state", "ntscsim_cass_debug_set_plan",
     "ntscsim_cass_debug_stats", "ntscsim_cass_debug_time_kernels", "ntscsim_cass_debug_kernel_ms",
+    "ntscsim_cass_tracks_device", "ntscsim_cass_debug_track_stats", "ntscsim_cass_debug_tilt_frames",
 )
 
 
@@ -487,6 +488,12 @@ class CassStats(C.Structure):
     _fields_ = [("segments", C.c_uint64), ("repaired_front", C.c_uint64), ("repaired_back", C.c_uint64)]
 
 
+class CassTrack(C.Structure):
+    """struct ntscsim_cass_track"""
+    _fields_ = [("blocks", C.POINTER(CassDesc)), ("n_blocks", C.c_int32), ("_pad", C.c_int32), ("count", C.c_uint64),
+                ("state", C.c_void_p)]
+
+
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
 
@@ -873,6 +880,12 @@ def lib():
     L.ntscsim_cass_debug_time_kernels.restype = C.c_int
     L.ntscsim_cass_debug_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.ntscsim_cass_debug_kernel_ms.restype = C.c_int
+    L.ntscsim_cass_tracks_device.argtypes = [C.c_void_p, C.POINTER(CassTrack), C.c_int, C.c_void_p]
+    L.ntscsim_cass_tracks_device.restype = C.c_int
+    L.ntscsim_cass_debug_track_stats.argtypes = [C.c_void_p, C.POINTER(CassStats), C.c_int]
+    L.ntscsim_cass_debug_track_stats.restype = C.c_int
+    L.ntscsim_cass_debug_tilt_frames.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ntscsim_cass_debug_tilt_frames.restype = C.c_int
     L.ntscsim_pixmap_params_init.argtypes = [C.POINTER(PixmapParams)]
     L.ntscsim_pixmap_params_init.restype = None
     L.ntscsim_pixmap_params_free.argtypes = [C.POINTER(PixmapParams)]

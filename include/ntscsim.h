@@ -1817,6 +1817,46 @@ int  ntscsim_cass_bind(ntscsim_ctx *ctx, const ntscsim_cass_params *cp);
  * src of the call.
  */
 int  ntscsim_cass_device(ntscsim_ctx *ctx, const ntscsim_cass_desc *descs, int n, void *hip_stream);
+/*
+ * Many independent tapes in one call.  A track is what one ntscsim_cass_device() call takes: blocks that form ONE
+ * continuous stream.  The call equals, in output bytes, end states (the FIR's history included) and the ctx's rand()
+ * position, this sequence for t = 0 .. n_tracks-1 in order: ntscsim_cass_set_state(*tracks[t].state with its count set
+ * to tracks[t].count and its taps to the bound ones), ntscsim_cass_device(blocks of t),
+ * ntscsim_cass_get_state(tracks[t].state) -- but the tracks run side by side in one launch of each kernel, nothing
+ * waits for the device, and the ctx's own carried state and its host-side count are neither read nor written.  All
+ * tracks use the parameters of the last ntscsim_cass_bind().
+ * State on entry and exit: the `count` and `taps` fields of a state are IGNORED on entry -- the sines of a track are
+ * the host's, made from tracks[t].count, which the host knows without asking the device; that is also what makes a
+ * zero-filled device buffer a fresh track -- and written on exit as count + frames and the bound taps.  A track shorter
+ * than taps - 1 frames keeps the rest of its old history, as a short call does.  Tracks without frames and blocks
+ * without samples may stand anywhere; a track without frames leaves its state as it is, count and taps included.
+ * rand() positions: as above, each block carries its own; NTSCSIM_RNG_AUTO continues from the ctx's position, tracks in
+ * order and blocks in order within a track; the ctx's position moves at call time, by 2 * samples per block when
+ * hiss_level != 0.  The tilt table is made once over the UNION of the tracks' ranges [count, count + frames): tracks
+ * that cover the same counts share their sines (ntscsim_cass_debug_tilt_frames).  The cassette parameters have no
+ * `enabled`: there is no copying mode.  `tracks` and the block arrays are host memory, consumed by the call.
+ * Enqueued on hip_stream (NULL: the ctx's own stream), returns without synchronising.
+ * Kernels: k_audio_hiss, k_cass_track_front (group g of workgroup b takes segment 3 b + g of the call and finds its
+ * track in the track table), k_cass_track_front_verify (one workgroup per track: its history laid in front of its
+ * section of x, the verify / repair walk over its records), k_cass_track_conv (one workgroup per tile of the call; a
+ * tile never crosses a track; the first tile of a track writes its new history), and with de-emphasis
+ * k_cass_track_back (one lane per segment of the call) + k_cass_track_back_verify (one lane per track).  The result
+ * never depends on the plan.
+ * NTSCSIM_E_ARG, before anything is enqueued or the rand() position moves: no ntscsim_cass_bind() before, n_tracks
+ * < 0, a NULL `tracks` or `blocks` that should hold something, a NULL or odd pointer in a block with samples, a state
+ * that is not 8-byte aligned, two tracks whose states overlap, a dst of any track that overlaps a src of any track,
+ * count + frames of a track overflowing 64 bits.
+ */
+typedef struct ntscsim_cass_track {
+    const ntscsim_cass_desc *blocks;   /* host memory: this track's blocks, ONE continuous stream                     */
+    int32_t                  n_blocks;
+    int32_t                  _pad;
+    uint64_t                 count;    /* audio_proc_count of the track's first frame: the HOST's knowledge, used for
+                                          the sines and for the state's count                                         */
+    ntscsim_cass_state      *state;    /* DEVICE pointer, 8-byte aligned, read at the start and written at the end;
+                                          NULL: start from zeros, end state discarded                                 */
+} ntscsim_cass_track;
+int  ntscsim_cass_tracks_device(ntscsim_ctx *ctx, const ntscsim_cass_track *tracks, int n_tracks, void *hip_stream);
 /* Drop-in for composite_audio_process(audio, samples): HOST memory, in place, any alignment.  Synchronous. */
 int  ntscsim_cass_host(ntscsim_ctx *ctx, int16_t *audio, uint32_t samples);
 /* reset: the tool's start.  get / set: a track processed in pieces, or started at any sample count.  set refuses a
@@ -1828,9 +1868,15 @@ int  ntscsim_cass_set_state(ntscsim_ctx *ctx, const ntscsim_cass_state *in);
  * 72 time constants of the high-pass for the front, 64 frames for the back); any other triple is taken as given. */
 int  ntscsim_cass_debug_set_plan(ntscsim_ctx *ctx, uint32_t seg_len, uint32_t warmup_front, uint32_t warmup_back);
 int  ntscsim_cass_debug_stats(ntscsim_ctx *ctx, ntscsim_cass_stats *out);
+/* stats of tracks 0 .. n_tracks-1 of the last ntscsim_cass_tracks_device() call (n_tracks beyond that call's:
+ * NTSCSIM_E_ARG).  Waits for the device.  set_plan applies to a tracks call as it does to the single call. */
+int  ntscsim_cass_debug_track_stats(ntscsim_ctx *ctx, ntscsim_cass_stats *out, int n_tracks);
+/* sines the last call's host fill evaluated: a single call's frames; a tracks call's union of [count, count + frames) */
+int  ntscsim_cass_debug_tilt_frames(ntscsim_ctx *ctx, uint64_t *evaluated);
 int  ntscsim_cass_debug_time_kernels(ntscsim_ctx *ctx, int on);
 /* milliseconds of the last call: [0] the host's sin fill (CPU clock), [1] its upload, [2] k_audio_hiss, [3] k_cass_front,
- * [4] k_cass_front_verify, [5] k_cass_conv, [6] k_cass_back, [7] k_cass_back_verify */
+ * [4] k_cass_front_verify, [5] k_cass_conv, [6] k_cass_back, [7] k_cass_back_verify; after a tracks call the same
+ * eight slots hold the k_cass_track_* kernel of the same name */
 int  ntscsim_cass_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[8]);
 
 #ifdef __cplusplus

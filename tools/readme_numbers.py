@@ -146,7 +146,35 @@ def audio_tracks_row(path="profiles/audio_tracks.json"):
             "`profiles/audio_tracks.json`, DESIGN.md §7l")
 
 
-for row in (led_row, filmac_row, audio_tracks_row):
+def cass_tracks_row(path="profiles/cass_tracks.json"):
+    """The row of many cassette tracks in one call, from tools/bench_cass_tracks.py's file."""
+    j = json.load(open(path))
+    c = j["cases"]
+
+    def cell(x):
+        t, b = x["tracks_call"], x["b_single_track_of_the_total_length"]
+        return (t["ms"], x["times_real_time"], x["a_one_call_per_track"]["ms"], x["a_over_tracks"], b["ms"], x["tracks_over_b"])
+
+    t8, b8 = c["taps8"]["tracks_call"], c["taps8"]["b_single_track_of_the_total_length"]
+    d8 = c["taps8_deemph"]["tracks_call"]
+    km, kd = t8["kernel_ms"], d8["kernel_ms"]
+    return ("many cassette tracks in one call (`ntscsim_cass_tracks_device`): %d independent stereo tracks of %g s resident in HBM, all from sample count 0, each with "
+            "its own state and FIR history on the device (`tools/bench_cass_tracks.py`); (a) the same tracks as one `ntscsim_cass_device` call each with `set_state` / "
+            "`get_state` between them, wall clock; (b) one `ntscsim_cass_device` call over a single track of the same total length; all in the same run"
+            % (j["tracks"], j["frames_per_track"] / j["rate"]),
+            "8 taps: **%.1f ms** (%.0f × real time); (a) %.0f ms, so the one call is worth **%.1f ×**; (b) %.1f ms, the tracks call takes %.2f × that.  "
+            "With de-emphasis: %.1f ms (%.0f ×); (a) %.0f ms, %.1f ×; (b) %.1f ms, %.2f ×.  57 taps: %.1f ms (%.0f ×); (a) %.0f ms, %.1f ×; (b) %.1f ms, %.2f ×; "
+            "with de-emphasis %.1f ms (%.0f ×); (a) %.0f ms, %.1f ×; (b) %.1f ms, %.2f ×.  Kernels at 8 taps: draws %.2f, front %.1f, its verify %.2f, FIR %.2f ms, "
+            "back %.2f + %.2f with de-emphasis; host `sin()` fill %.2f ms for %d sines (the union of the tracks' counts: one track's), against %.1f ms for the %d of (b); "
+            "%d + %d segments repaired.  Bytes and end states of every track equal (a)'s"
+            % (cell(c["taps8"]) + cell(c["taps8_deemph"]) + cell(c["taps57"]) + cell(c["taps57_deemph"]) +
+               (km["k_audio_hiss"], km["k_cass_track_front"], km["k_cass_track_front_verify"], km["k_cass_track_conv"], kd["k_cass_track_back"],
+                kd["k_cass_track_back_verify"], km["host_sin_fill"], t8["tilt_frames"], b8["kernel_ms"]["host_sin_fill"], b8["tilt_frames"],
+                d8["repaired_front"], d8["repaired_back"])),
+            "`profiles/cass_tracks.json`, DESIGN.md §7m")
+
+
+for row in (led_row, filmac_row, audio_tracks_row, cass_tracks_row):
     try:
         rows.append(row())
     except Exception:
