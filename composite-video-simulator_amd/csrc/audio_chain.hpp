@@ -6,7 +6,8 @@
 //
 // Also here: the PLAN that cuts a call's frames into segments which start early from a zero state, and
 // run / verify / repair over that plan, so that a host program executes what the device executes -- for one stream and
-// for many independent tracks in one call (the track table and the segment-to-track lookup).
+// for many independent tracks in one call (the track table and the segment-to-track lookup), with one cfg or one per
+// track (the mixed plan).
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -269,6 +270,11 @@ struct AudioTrackEnt {
     uint64_t seg0;                       // its first segment in the call-wide numbering (= the segments of the tracks before it)
     AudioState *state;                   // carried state: read at the start, written at the end; NULL: zeros, count 0, end discarded
     int32_t block0, nblocks;             // its blocks in the call's block array (a block's `first` counts in the plane)
+    // a mixed call only (audio_mixed_layout)
+    uint64_t hiss0;                      // its first channel-sample in the hiss plane: tracks differ in channels, so frames * channels
+                                         // does not find it; tracks that draw nothing take no room there
+    int32_t set;                         // its AudioCfg in the call's set table
+    uint32_t warmup;                     // its own warm-up, in frames
 };
 
 // fills plane and seg0 of tab[0..n) from the frames; returns the segments of the call
@@ -359,6 +365,97 @@ inline void audio_run_tracks_planned(const AudioCfg &c, const AudioTrackIO *trac
             }
         }
         if (e.state) *e.state = truth;
+        stats[t].segments = nt;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ mixed tracks
+// A mixed call (ntscsim_audio_mixed_tracks_device) is a tracks call whose tracks each name an AudioCfg of a set table:
+// frame size, hiss, buzz and warm-up are the track's own.  A track whose cfg is not enabled is a copy: it has no frames
+// in the table (no segments, its state stays) and its blocks set no rand() position.
+
+// does a block of a track with this cfg advance the rand() position (and take room in the hiss plane)?
+AUDIO_HD bool audio_track_draws(const AudioCfg &c) { return c.enabled && c.hiss_level != 0; }
+
+// Fills plane, seg0, hiss0 and warmup of tab[0..n) from frames and set; returns the segments of the call.  plan_warmup:
+// one warm-up for every track (the debug plan), or NULL: each track's audio_default_warmup().  hiss_items, plane_frames
+// (may be NULL): what the hiss plane and the pulse plane must hold.
+inline uint64_t audio_mixed_layout(AudioTrackEnt *tab, int n, const AudioCfg *cfgs, uint32_t L, const uint32_t *plan_warmup, uint64_t *hiss_items,
+                                   uint64_t *plane_frames)
+{
+    uint64_t plane = 0, seg = 0, hiss = 0;
+    for (int t = 0; t < n; t++) {
+        const AudioCfg &c = cfgs[tab[t].set];
+        tab[t].plane = plane;
+        tab[t].seg0 = seg;
+        tab[t].hiss0 = hiss;
+        tab[t].warmup = plan_warmup ? *plan_warmup : audio_default_warmup(c);
+        plane += tab[t].frames;
+        seg += audio_seg_count(tab[t].frames, L);
+        if (audio_track_draws(c)) hiss += tab[t].frames * (uint64_t)c.channels;
+    }
+    if (hiss_items) *hiss_items = hiss;
+    if (plane_frames) *plane_frames = plane;
+    return seg;
+}
+
+struct AudioMixedTrackIO {               // host: one track of audio_run_mixed_tracks_planned()
+    const int16_t *src;
+    int16_t *dst;                        // must not overlap any src
+    uint64_t frames;                     // of channels(cfgs[set]) samples
+    AudioState *state;                   // as AudioTrackEnt's
+    int set;
+};
+
+// Run, verify, repair over tracks with a cfg each: what k_audio_mixed_segments and k_audio_mixed_verify do.  hiss: the
+// hiss plane of the call, laid out by audio_mixed_layout() (NULL: no track draws).  stats[t]: of track t.
+inline void audio_run_mixed_tracks_planned(const AudioCfg *cfgs, const AudioMixedTrackIO *tracks, int n, const int32_t *hiss, uint32_t L,
+                                           const uint32_t *plan_warmup, AudioPlanStats *stats)
+{
+    if (L == 0) L = 1;
+    std::vector<AudioTrackEnt> tab((size_t)n);
+    for (int t = 0; t < n; t++) {
+        stats[t].segments = stats[t].repaired = stats[t].worst_convergence = 0;
+        const AudioCfg &c = cfgs[tracks[t].set];
+        AudioTrackEnt &e = tab[(size_t)t];
+        std::memset(&e, 0, sizeof(e));
+        e.set = tracks[t].set;
+        e.state = tracks[t].state;
+        e.block0 = t;
+        e.nblocks = 1;
+        if (c.enabled) e.frames = tracks[t].frames;
+        else if (tracks[t].frames) std::memmove(tracks[t].dst, tracks[t].src, (size_t)tracks[t].frames * (size_t)c.channels * sizeof(int16_t));
+    }
+    const uint64_t nseg = audio_mixed_layout(tab.data(), n, cfgs, L, plan_warmup, nullptr, nullptr);
+    const auto hiss_of = [&](const AudioTrackEnt &e) { return audio_track_draws(cfgs[e.set]) ? hiss + e.hiss0 : nullptr; };
+    std::vector<AudioState> at_start((size_t)nseg), at_end((size_t)nseg);
+    for (uint64_t j = 0; j < nseg; j++) {                                       // the speculative pass
+        const int t = audio_track_of(tab.data(), n, j);
+        const AudioTrackEnt &e = tab[(size_t)t];
+        const AudioCfg &c = cfgs[e.set];
+        const AudioSeg g = audio_seg(e.frames, L, e.warmup, j - e.seg0);
+        const AudioState carried = audio_track_carried(e);
+        AudioState s = g.run_start == 0 ? carried : audio_spec_state(c, carried, g.run_start);
+        audio_run_span(c, s, tracks[t].src, nullptr, hiss_of(e), g.run_start, g.start - g.run_start);
+        at_start[(size_t)j] = s;
+        audio_run_span(c, s, tracks[t].src, tracks[t].dst, hiss_of(e), g.start, g.len);
+        at_end[(size_t)j] = s;
+    }
+    for (int t = 0; t < n; t++) {                                               // verify, repair: per track
+        const AudioTrackEnt &e = tab[(size_t)t];
+        const AudioCfg &c = cfgs[e.set];
+        const uint64_t nt = audio_seg_count(e.frames, L);
+        AudioState truth = audio_track_carried(e);
+        for (uint64_t j = 0; j < nt; j++) {
+            const AudioSeg g = audio_seg(e.frames, L, e.warmup, j);
+            if (!audio_state_same(at_start[(size_t)(e.seg0 + j)], truth)) {
+                audio_run_span(c, truth, tracks[t].src, tracks[t].dst, hiss_of(e), g.start, g.len);
+                stats[t].repaired++;
+            } else {
+                truth = at_end[(size_t)(e.seg0 + j)];
+            }
+        }
+        if (e.state && nt) *e.state = truth;
         stats[t].segments = nt;
     }
 }

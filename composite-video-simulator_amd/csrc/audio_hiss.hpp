@@ -17,14 +17,14 @@ constexpr int HISS_POLYS = 26;           // x^(HISS_CHUNK * 2^j): 2^33 draws of 
 
 struct AudioHissBlock {                  // rand() window at the block's position; first: its first channel-sample in the call
     uint32_t w[31];
-    uint32_t _pad;
+    int32_t level;                       // the hiss level of the block's stream: the blocks of one launch may differ in it
     uint64_t first, items;
 };
 
 // The window of a block whose first draw is at position p.  seq / seq_pos: a generator the caller keeps across the
 // blocks of a call (seq_pos UINT64_MAX: it stands nowhere) -- small blocks that follow each other (the tool's packets)
 // step it instead of jumping.
-inline void audio_hiss_window(AudioHissBlock &h, RandSeq &seq, uint64_t &seq_pos, uint64_t p, uint64_t first, uint64_t items)
+inline void audio_hiss_window(AudioHissBlock &h, RandSeq &seq, uint64_t &seq_pos, uint64_t p, uint64_t first, uint64_t items, int level)
 {
     if (seq_pos == UINT64_MAX || p < seq_pos || p - seq_pos > 65536) {
         seq = RandSeq(rand_state_at(p));
@@ -32,7 +32,7 @@ inline void audio_hiss_window(AudioHissBlock &h, RandSeq &seq, uint64_t &seq_pos
     }
     for (; seq_pos < p; seq_pos++) (void)seq.next();
     for (int j = 0; j < 31; j++) h.w[j] = seq.r[(seq.i + j) % 31];
-    h._pad = 0;
+    h.level = level;
     h.first = first;
     h.items = items;
 }
@@ -40,6 +40,7 @@ inline void audio_hiss_window(AudioHissBlock &h, RandSeq &seq, uint64_t &seq_pos
 // HISS_POLYS polynomials in device memory (the caller frees them)
 int audio_hiss_polys(const CtxStageView &v, uint32_t **polys);
 // k_audio_hiss over m blocks (device records) whose longest has max_items draws: out[first + i] = numerator of draw i
-void audio_hiss_launch(const AudioHissBlock *blocks, int m, uint64_t max_items, const uint32_t *polys, int level, int32_t *out, hipStream_t st);
+// at the block's level
+void audio_hiss_launch(const AudioHissBlock *blocks, int m, uint64_t max_items, const uint32_t *polys, int32_t *out, hipStream_t st);
 
 } // namespace ntscsim

@@ -8,6 +8,8 @@
 // state keep two values and alternate; the pre-/de-emphasis stages keep one, which IS the reference's cross-channel
 // coupling (:920, :960).  k_audio_verify_repair then makes the result independent of the speculation.
 // ntscsim_audio_tracks_device() runs many such streams side by side through a track table (k_audio_track_*).
+// ntscsim_audio_mixed_tracks_device() does so with parameters per track: a set table in the call's records and a per-lane
+// view of the track's cfg (k_audio_mixed_*).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,11 +45,11 @@ struct AudioSegRec {
 // ---------------------------------------------------------------------------------------- the draws
 // Lane k of block b: the window at the block's position advanced by k chunks (the set bits of k pick the polynomials),
 // then HISS_CHUNK draws kept in registers, 31 to a round.
-__global__ __launch_bounds__(64) void k_audio_hiss(const AudioHissBlock *__restrict__ hb, int nblocks, const uint32_t *__restrict__ polys, int level,
-                                                   int32_t *__restrict__ out)
+__global__ __launch_bounds__(64) void k_audio_hiss(const AudioHissBlock *__restrict__ hb, int nblocks, const uint32_t *__restrict__ polys, int32_t *__restrict__ out)
 {
     for (int b = (int)blockIdx.y; b < nblocks; b += (int)gridDim.y) {
         const uint64_t items = hb[b].items, first = hb[b].first;
+        const int level = hb[b].level;                                          // per block: a mixed call's tracks differ in it
         const uint64_t nchunks = (items + HISS_CHUNK - 1) / HISS_CHUNK;
         for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nchunks; k += (uint64_t)gridDim.x * blockDim.x) {
             uint32_t w[61];
@@ -78,11 +80,11 @@ __global__ __launch_bounds__(64) void k_audio_hiss(const AudioHissBlock *__restr
     }
 }
 
-void audio_hiss_launch(const AudioHissBlock *blocks, int m, uint64_t max_items, const uint32_t *polys, int level, int32_t *out, hipStream_t st)
+void audio_hiss_launch(const AudioHissBlock *blocks, int m, uint64_t max_items, const uint32_t *polys, int32_t *out, hipStream_t st)
 {
     const uint64_t chunks = (max_items + HISS_CHUNK - 1) / HISS_CHUNK;
     const unsigned gx = (unsigned)std::min<uint64_t>((chunks + 63) / 64, 65535), gy = (unsigned)std::min(m, 1024);
-    hipLaunchKernelGGL(k_audio_hiss, dim3(gx, gy), dim3(64), 0, st, blocks, m, polys, level, out);
+    hipLaunchKernelGGL(k_audio_hiss, dim3(gx, gy), dim3(64), 0, st, blocks, m, polys, out);
 }
 
 int audio_hiss_polys(const CtxStageView &v, uint32_t **polys)
@@ -111,15 +113,6 @@ __global__ __launch_bounds__(256) void k_audio_pulses(AudioCfg c, const AudioSta
 enum AudioRole { AR_LOAD, AR_FILTER, AR_PASS, AR_BUZZ_A, AR_BUZZ_B, AR_STORE, AR_IDLE };
 enum AudioRule { AO_PREV, AO_HIGH, AO_EMPH };
 
-struct AudioCall {                       // what every lane of a call reads
-    AudioCfg c;
-    const AudioBlock *blocks;
-    const int32_t *hiss;                 // per channel-sample of the call, NULL without hiss
-    const uint8_t *pulses;               // per frame of the call, NULL without buzz
-    uint64_t total;                      // frames of the call
-    int nblocks;
-};
-
 struct AudioLane {
     int role, rule;
     int slot0, slot1;                    // values of the state this lane owns (-1: none)
@@ -127,7 +120,7 @@ struct AudioLane {
     double alpha, gain;
 };
 
-__device__ __forceinline__ AudioLane audio_lane(const AudioCfg &c, int r)
+__device__ __forceinline__ AudioLane audio_idle_lane()
 {
     AudioLane l;
     l.role = AR_IDLE;
@@ -136,6 +129,12 @@ __device__ __forceinline__ AudioLane audio_lane(const AudioCfg &c, int r)
     l.on = true;
     l.alpha = 0;
     l.gain = 1.0;
+    return l;
+}
+
+__device__ __forceinline__ AudioLane audio_lane(const AudioCfg &c, int r)
+{
+    AudioLane l = audio_idle_lane();
     const bool two = c.channels == 2;
     if (r == 0) l.role = AR_LOAD;
     else if (r <= 6) { l.role = AR_FILTER; l.slot0 = r - 1; l.slot1 = two ? 12 + r - 1 : -1; l.alpha = c.a_lo; }
@@ -149,8 +148,48 @@ __device__ __forceinline__ AudioLane audio_lane(const AudioCfg &c, int r)
     return l;
 }
 
+// What audio_run_lanes reads of a call, in two forms.  AudioCall: one cfg for every lane, a kernel argument, so all of it
+// is wave-uniform.  AudioMixedView (below): the groups of a wavefront serve tracks with different cfgs, so a lane keeps
+// what the steps read of its track's cfg -- and no more -- in registers.
+struct AudioCall {
+    AudioCfg c;
+    const AudioBlock *blocks;
+    const int32_t *hiss;                 // per channel-sample of the call, NULL without hiss
+    const uint8_t *pulses;               // per frame of the call, NULL without buzz
+    uint64_t total;                      // frames of the call
+    int nblocks;
+
+    __device__ __forceinline__ int channels() const { return c.channels; }
+    __device__ __forceinline__ AudioLane lane(int r) const { return audio_lane(c, r); }
+    __device__ __forceinline__ double buzz_step() const { return c.buzz / AUDIO_OVERSAMPLE / 2; }
+    __device__ __forceinline__ bool hiss_on() const { return c.hiss_level != 0; }
+    __device__ __forceinline__ bool buzz_on() const { return pulses != nullptr; }
+    __device__ __forceinline__ int32_t hiss_at(uint64_t f, int ch, int cc) const { return hiss[f * ch + cc]; }
+};
+
+struct AudioMixedView {
+    const AudioBlock *blocks;            // of all tracks, `first` in the plane: wave-uniform, as the two planes are
+    const int32_t *hiss;
+    const uint8_t *pulses;               // per frame of the plane
+    uint64_t hiss_off;                   // channel-sample (plane frame f, channel cc) of the track is hiss[f * ch + cc + hiss_off]: the
+                                         // track's hiss0 minus its plane frames in its own channels, modulo 2^64
+    AudioLane L;                         // of this lane at its place in the group, from the track's cfg; the two buzz lanes own no
+                                         // filter, so their alpha holds the track's buzz step
+    int nblocks;
+    int ch;
+    bool hissing, buzzing;               // of the track
+
+    __device__ __forceinline__ int channels() const { return ch; }
+    __device__ __forceinline__ AudioLane lane(int) const { return L; }
+    __device__ __forceinline__ double buzz_step() const { return L.alpha; }
+    __device__ __forceinline__ bool hiss_on() const { return hissing; }
+    __device__ __forceinline__ bool buzz_on() const { return buzzing; }
+    __device__ __forceinline__ int32_t hiss_at(uint64_t f, int chn, int cc) const { return hiss[f * chn + cc + hiss_off]; }
+};
+
 // the block that holds frame f (f < total); b only moves forward
-__device__ __forceinline__ void audio_seek(const AudioCall &k, int &b, uint64_t f)
+template <class K>
+__device__ __forceinline__ void audio_seek(const K &k, int &b, uint64_t f)
 {
     while (b + 1 < k.nblocks && f >= k.blocks[b].first + k.blocks[b].frames) b++;
 }
@@ -163,17 +202,17 @@ __device__ __forceinline__ void audio_seek(const AudioCall &k, int &b, uint64_t 
 // ring: AUDIO_RING entries of the group for each of the three prefetched inputs -- every lane fetches, one period of 21
 // steps ahead, what channel-sample (period * 21 + r) needs (input, hiss numerator, pulse count), so that no stage waits
 // for memory inside a step.
-__device__ void audio_run_lanes(const AudioCall &k, int r, bool live, uint64_t first, uint64_t warm, uint64_t own, const double *init,
+template <class K>
+__device__ void audio_run_lanes(const K &k, int r, bool live, uint64_t first, uint64_t warm, uint64_t own, const double *init,
                                 AudioState *at_start, AudioState *at_end, int32_t *ring_in, int32_t *ring_hiss, int32_t *ring_pulses, int b0 = 0)
 {
-    const AudioCfg &c = k.c;
-    const int ch = c.channels;
-    const AudioLane L = audio_lane(c, live ? r : 99);
+    const int ch = k.channels();
+    const AudioLane L = k.lane(live ? r : 99);
     const uint64_t N = live ? (warm + own) * (uint64_t)ch : 0;                  // channel-samples of the run
     const uint64_t warm_items = warm * (uint64_t)ch;
     double st0 = L.slot0 >= 0 ? init[L.slot0] : 0.0, st1 = L.slot1 >= 0 ? init[L.slot1] : 0.0;
-    const double q = c.buzz / AUDIO_OVERSAMPLE / 2;
-    const bool hiss_on = c.hiss_level != 0;
+    const double q = k.buzz_step();
+    const bool hiss_on = k.hiss_on();
 
     // prefetch cursor: channel-sample pf of the run, period by period
     uint64_t pf = (uint64_t)r;
@@ -188,8 +227,8 @@ __device__ void audio_run_lanes(const AudioCall &k, int r, bool live, uint64_t f
             const int cc = ch == 2 ? (int)(pf & 1) : 0;
             audio_seek(k, pf_block, f);
             pf_in = k.blocks[pf_block].src[(f - k.blocks[pf_block].first) * ch + cc];
-            if (hiss_on) pf_hiss = k.hiss[f * ch + cc];
-            if (k.pulses) pf_pulses = k.pulses[f];
+            if (hiss_on) pf_hiss = k.hiss_at(f, ch, cc);
+            if (k.buzz_on()) pf_pulses = k.pulses[f];
         }
     };
     int pslot = r;                                                             // ring entry of the period being fetched
@@ -235,7 +274,7 @@ __device__ void audio_run_lanes(const AudioCall &k, int r, bool live, uint64_t f
             }
             case AR_BUZZ_B: {
                 double s = x;
-                if (k.pulses) {
+                if (k.buzz_on()) {
                     const int p = ring_pulses[slot] - 8;
                     for (int i = 0; i < p; i++) s -= q;
                 }
@@ -462,6 +501,140 @@ __global__ __launch_bounds__(64) void k_audio_track_verify(AudioTracksCall k, co
     if (lane == 0) { stats[2 * (uint64_t)blockIdx.x] = nseg; stats[2 * (uint64_t)blockIdx.x + 1] = repaired; }
 }
 
+// ---------------------------------------------------------------------------------------- mixed tracks
+// ntscsim_audio_mixed_tracks_device(): a tracks call whose tracks each name a cfg of a SET TABLE (device records of the
+// call).  A lane reads its track's cfg once, in front of the run, and keeps of it what AudioMixedView holds; the 120-byte
+// AudioCfg is dead before the first step.  The pulse plane is per frame as before; the hiss plane is per channel-sample
+// and tracks differ in channels, so a track finds its part through AudioTrackEnt::hiss0.
+struct AudioMixedCall {
+    const AudioCfg *cfgs;                // the set table
+    const AudioTrackEnt *tracks;
+    const AudioBlock *blocks;            // of all tracks, `first` in the plane
+    const int32_t *hiss;
+    const uint8_t *pulses;
+    uint64_t nseg;                       // segments of the call
+    int ntracks;
+};
+
+// r: the lane's place in its group (>= AUDIO_LANES: it only takes part in the hand-offs)
+__device__ __forceinline__ AudioMixedView audio_mixed_view(const AudioMixedCall &k, const AudioTrackEnt &e, const AudioCfg &c, int r)
+{
+    AudioMixedView v;
+    v.blocks = k.blocks;
+    v.hiss = k.hiss;
+    v.pulses = k.pulses;
+    v.hiss_off = e.hiss0 - e.plane * (uint64_t)c.channels;
+    v.L = audio_lane(c, r < AUDIO_LANES ? r : 99);
+    if (v.L.role == AR_BUZZ_A || v.L.role == AR_BUZZ_B) v.L.alpha = c.buzz / AUDIO_OVERSAMPLE / 2;
+    v.hissing = c.hiss_level != 0;
+    v.buzzing = audio_buzz_on(c);
+    v.nblocks = e.block0 + e.nblocks;                                           // audio_seek stops at the track's last block
+    v.ch = c.channels;
+    return v;
+}
+
+// pulse counts per frame of every track whose buzz is on, each from its own sample count with its own line rates
+__global__ __launch_bounds__(256) void k_audio_mixed_pulses(const AudioCfg *__restrict__ cfgs, const AudioTrackEnt *__restrict__ tracks, int ntracks,
+                                                            uint8_t *__restrict__ out)
+{
+    for (int t = (int)blockIdx.y; t < ntracks; t += (int)gridDim.y) {
+        const AudioTrackEnt e = tracks[t];
+        const AudioCfg c = cfgs[e.set];
+        if (!audio_buzz_on(c)) continue;                                        // nobody reads these frames of the plane
+        const uint64_t base = e.state ? e.state->count : 0;
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e.frames; i += (uint64_t)gridDim.x * blockDim.x)
+            out[e.plane + i] = (uint8_t)audio_pulse_count(c, base + i);
+    }
+}
+
+// k_audio_track_segments with the cfg, the warm-up and the hiss base of the segment's own track
+__global__ __launch_bounds__(64) void k_audio_mixed_segments(AudioMixedCall k, AudioSegRec *__restrict__ recs, uint32_t seg_len)
+{
+    __shared__ int32_t ring[AUDIO_GROUPS + 1][3][AUDIO_RING];
+    __shared__ double init[AUDIO_GROUPS + 1][AUDIO_STATE_VALUES];
+    const int lane = (int)threadIdx.x, g = lane / AUDIO_LANES, r = lane - g * AUDIO_LANES;
+    const uint64_t j = (uint64_t)blockIdx.x * AUDIO_GROUPS + (uint64_t)g;
+    const bool live = g < AUDIO_GROUPS && j < k.nseg;
+    AudioSeg s{0, 0, 0};
+    uint64_t plane = 0;
+    int block0 = 0;
+    AudioMixedView view;
+    view.blocks = k.blocks;
+    view.hiss = k.hiss;
+    view.pulses = k.pulses;
+    view.hiss_off = 0;
+    view.hissing = view.buzzing = false;
+    view.L = audio_idle_lane();
+    view.nblocks = 0;
+    view.ch = 1;
+    if (live) {
+        const AudioTrackEnt e = k.tracks[audio_track_of(k.tracks, k.ntracks, j)];
+        const AudioCfg c = k.cfgs[e.set];
+        s = audio_seg(e.frames, seg_len, e.warmup, j - e.seg0);                  // clamps at frame 0 of this track
+        const bool spec = s.run_start != 0;
+        for (int i = r; i < AUDIO_STATE_VALUES; i += AUDIO_LANES) {
+            const double v = (spec && audio_value_live(c, i)) || !e.state ? 0.0 : e.state->v[i];
+            init[g][i] = v;
+            recs[j].at_start.v[i] = v;
+            recs[j].at_end.v[i] = v;
+        }
+        if (r == 0) {
+            const uint64_t count = e.state ? e.state->count : 0;
+            recs[j].at_start.count = count + s.start;
+            recs[j].at_end.count = count + s.start + s.len;
+        }
+        view = audio_mixed_view(k, e, c, r);
+        plane = e.plane;
+        block0 = e.block0;
+    }
+    __syncthreads();
+    audio_run_lanes(view, r, live, plane + s.run_start, s.start - s.run_start, s.len, init[g], live ? &recs[j].at_start : nullptr,
+                    live ? &recs[j].at_end : nullptr, ring[g][0], ring[g][1], ring[g][2], block0);
+}
+
+
+// One workgroup (one wavefront) per track, as k_audio_track_verify: the track's cfg is the workgroup's.
+__global__ __launch_bounds__(64) void k_audio_mixed_verify(AudioMixedCall k, const AudioSegRec *__restrict__ recs, uint32_t seg_len,
+                                                           uint64_t *__restrict__ stats)
+{
+    __shared__ int32_t ring[3][AUDIO_RING];
+    __shared__ AudioState truth;
+    __shared__ double init[AUDIO_STATE_VALUES];
+    const int lane = (int)threadIdx.x;
+    const AudioTrackEnt e = k.tracks[blockIdx.x];
+    const AudioMixedView view = audio_mixed_view(k, e, k.cfgs[e.set], lane);
+    const uint64_t nseg = audio_seg_count(e.frames, seg_len);
+    recs += e.seg0;
+    if (lane < AUDIO_STATE_VALUES) truth.v[lane] = e.state ? e.state->v[lane] : 0.0;
+    if (lane == AUDIO_STATE_VALUES) truth.count = e.state ? e.state->count : 0;
+    __syncthreads();
+    uint64_t repaired = 0;
+    for (uint64_t j = 0; j < nseg; j++) {
+        bool same = true;
+        if (lane < AUDIO_STATE_VALUES) same = __double_as_longlong(recs[j].at_start.v[lane]) == __double_as_longlong(truth.v[lane]);
+        if (lane == AUDIO_STATE_VALUES) same = recs[j].at_start.count == truth.count;
+        const bool ok = __all(same);
+        __syncthreads();
+        if (ok) {
+            if (lane < AUDIO_STATE_VALUES) truth.v[lane] = recs[j].at_end.v[lane];
+            if (lane == AUDIO_STATE_VALUES) truth.count = recs[j].at_end.count;
+        } else {
+            const AudioSeg s = audio_seg(e.frames, seg_len, e.warmup, j);
+            if (lane < AUDIO_STATE_VALUES) init[lane] = truth.v[lane];
+            __syncthreads();
+            audio_run_lanes(view, lane, lane < AUDIO_LANES, e.plane + s.start, 0, s.len, init, nullptr, &truth, ring[0], ring[1], ring[2], e.block0);
+            if (lane == 0) truth.count += s.len;
+            repaired++;
+        }
+        __syncthreads();
+    }
+    if (e.state && nseg) {                                                      // a track without frames (or a copied one) keeps its state
+        if (lane < AUDIO_STATE_VALUES) e.state->v[lane] = truth.v[lane];
+        if (lane == AUDIO_STATE_VALUES) e.state->count = truth.count;
+    }
+    if (lane == 0) { stats[2 * (uint64_t)blockIdx.x] = nseg; stats[2 * (uint64_t)blockIdx.x + 1] = repaired; }
+}
+
 // ---------------------------------------------------------------------------------------- host side
 struct AudioStageState {
     ntscsim_audio_params prm;
@@ -642,7 +815,7 @@ int audio_blocks(ntscsim_ctx *c, const ntscsim_audio_desc *descs, int n, hipStre
         if (d.samples == 0) continue;
         blocks[o] = AudioBlock{d.src, d.dst, first, d.samples};
         if (hiss) {
-            audio_hiss_window(hb[o], seq, seq_pos, block_pos[(size_t)i], first * cfg.channels, (uint64_t)d.samples * cfg.channels);
+            audio_hiss_window(hb[o], seq, seq_pos, block_pos[(size_t)i], first * cfg.channels, (uint64_t)d.samples * cfg.channels, cfg.hiss_level);
             max_items = std::max(max_items, hb[o].items);
         }
         first += d.samples;
@@ -659,7 +832,7 @@ int audio_blocks(ntscsim_ctx *c, const ntscsim_audio_desc *descs, int n, hipStre
     int lrc = audio_mark(v, k, st);
     if (lrc != NTSCSIM_OK) return lrc;
     if (hiss) {
-        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + blocks_bytes), m, max_items, k->polys, cfg.hiss_level, k->hiss, st);
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + blocks_bytes), m, max_items, k->polys, k->hiss, st);
         lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
         if (lrc != NTSCSIM_OK) return lrc;
     }
@@ -789,7 +962,7 @@ int audio_tracks(ntscsim_ctx *c, const ntscsim_audio_track *tracks, int n, hipSt
         uint64_t seq_pos = UINT64_MAX;                                          // where seq stands; UINT64_MAX: nowhere
         for (int t = 0; t < n; t++)
             for (int b = tab[t].block0; b < tab[t].block0 + tab[t].nblocks; b++) {
-                audio_hiss_window(hb[b], seq, seq_pos, block_pos[(size_t)b], blocks[b].first * cfg.channels, blocks[b].frames * cfg.channels);
+                audio_hiss_window(hb[b], seq, seq_pos, block_pos[(size_t)b], blocks[b].first * cfg.channels, blocks[b].frames * cfg.channels, cfg.hiss_level);
                 max_items = std::max(max_items, hb[b].items);
             }
     }
@@ -813,7 +986,7 @@ int audio_tracks(ntscsim_ctx *c, const ntscsim_audio_track *tracks, int n, hipSt
     int lrc = audio_mark(v, k, st);
     if (lrc != NTSCSIM_OK) return lrc;
     if (hiss) {
-        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + tab_bytes + blocks_bytes), (int)m, max_items, k->polys, cfg.hiss_level, k->hiss, st);
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + tab_bytes + blocks_bytes), (int)m, max_items, k->polys, k->hiss, st);
         lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
         if (lrc != NTSCSIM_OK) return lrc;
     }
@@ -834,6 +1007,214 @@ int audio_tracks(ntscsim_ctx *c, const ntscsim_audio_track *tracks, int n, hipSt
     return lrc == NTSCSIM_OK ? audio_mark(v, k, st) : lrc;
 }
 
+// what ntscsim_audio_bind() accepts
+bool audio_params_ok(const ntscsim_audio_params &p)
+{
+    return !(p.channels < 1 || p.channels > 2 || p.passes != AUDIO_PASSES || p.rate <= 0 || !(p.lowpass_hz > 0) || !(p.highpass_hz > 0) ||
+             p.vsync_lines <= 0 || p.hiss_level < 0 || p.hiss_level > 0x3FFFFFFF);
+}
+
+// What a mixed call checks before it looks at a sample pointer: the shape of the arguments and the sets that tracks
+// name.  cfgs: the set table, one AudioCfg per distinct set in use, in order of first use; cfg_of_track[t]: track t's.
+int audio_mixed_sets(const AudioStageState *k, const ntscsim_audio_params *sets, int n_sets, const ntscsim_audio_mixed_track *tracks, int n,
+                     std::vector<AudioCfg> &cfgs, std::vector<int32_t> &cfg_of_track)
+{
+    if (n_sets < 0 || n < 0 || (n_sets > 0 && !sets) || (n > 0 && !tracks)) return NTSCSIM_E_ARG;
+    for (int t = 0; t < n; t++) {
+        const ntscsim_audio_mixed_track &tr = tracks[t];
+        if (tr.set < -1 || tr.set >= n_sets || tr.n_blocks < 0 || (tr.n_blocks > 0 && !tr.blocks)) return NTSCSIM_E_ARG;
+        if (tr.set >= 0 && sets[tr.set].struct_size != sizeof(ntscsim_audio_params)) return NTSCSIM_E_ARG;
+    }
+    std::vector<int32_t> at((size_t)n_sets + 1, -1);                            // at[set + 1]: its place in the table
+    cfg_of_track.assign((size_t)n, 0);
+    for (int t = 0; t < n; t++) {
+        const int set = tracks[t].set;
+        if (at[(size_t)set + 1] < 0) {
+            if (set >= 0 && !audio_params_ok(sets[set])) return NTSCSIM_E_PARAM;
+            at[(size_t)set + 1] = (int32_t)cfgs.size();
+            cfgs.push_back(set < 0 ? k->cfg : audio_cfg_of(sets[set]));
+        }
+        cfg_of_track[(size_t)t] = at[(size_t)set + 1];
+    }
+    return NTSCSIM_OK;
+}
+
+// ntscsim_audio_mixed_tracks_device(): n independent streams, each with the cfg of its set, in one launch of each kernel
+int audio_mixed(ntscsim_ctx *c, const std::vector<AudioCfg> &cfgs, const std::vector<int32_t> &cfg_of_track, const ntscsim_audio_mixed_track *tracks,
+                int n, hipStream_t st)
+{
+    CtxStageView v = ctx_stage_view(c);
+    AudioStageState *k = *v.audio;
+    // every track and descriptor checked before anything is enqueued or the rand() position moves
+    std::vector<Span> srcs;
+    std::vector<uintptr_t> states;
+    size_t m = 0, mh = 0;                                                       // blocks that run the chain; those of them that draw
+    for (int t = 0; t < n; t++) {
+        const ntscsim_audio_mixed_track &tr = tracks[t];
+        const AudioCfg &cfg = cfgs[(size_t)cfg_of_track[(size_t)t]];
+        const size_t fbytes = (size_t)cfg.channels * sizeof(int16_t);
+        if ((uintptr_t)tr.state & 7) return NTSCSIM_E_ARG;
+        if (tr.state) states.push_back((uintptr_t)tr.state);
+        for (int i = 0; i < tr.n_blocks; i++) {
+            const ntscsim_audio_desc &d = tr.blocks[i];
+            if (d.samples == 0) continue;
+            if (!d.src || !d.dst || (((uintptr_t)d.src | (uintptr_t)d.dst) & 1)) return NTSCSIM_E_ARG;
+            srcs.push_back(Span{(uintptr_t)d.src, (uintptr_t)d.src + (size_t)d.samples * fbytes});
+            if (cfg.enabled) m++;
+            if (audio_track_draws(cfg)) mh++;
+        }
+    }
+    if (m > (size_t)INT32_MAX) return NTSCSIM_E_ARG;
+    std::sort(states.begin(), states.end());
+    for (size_t i = 1; i < states.size(); i++)
+        if (states[i] - states[i - 1] < sizeof(AudioState)) return NTSCSIM_E_ARG;   // two tracks would share a state
+    std::sort(srcs.begin(), srcs.end(), [](const Span &x, const Span &y) { return x.a < y.a; });
+    std::vector<uintptr_t> reach(srcs.size());                                  // the furthest end among srcs[0..i]
+    for (size_t i = 0; i < srcs.size(); i++) reach[i] = std::max(srcs[i].b, i ? reach[i - 1] : 0);
+    for (int t = 0; t < n; t++) {
+        const size_t fbytes = (size_t)cfgs[(size_t)cfg_of_track[(size_t)t]].channels * sizeof(int16_t);
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_audio_desc &d = tracks[t].blocks[i];
+            if (d.samples == 0) continue;
+            const uintptr_t a = (uintptr_t)d.dst, b = a + (size_t)d.samples * fbytes;
+            const size_t at = (size_t)(std::lower_bound(srcs.begin(), srcs.end(), b, [](const Span &x, uintptr_t e) { return x.a < e; }) - srcs.begin());
+            if (at > 0 && reach[at - 1] > a) return NTSCSIM_E_ARG;              // a warm-up reads input again, in any track
+        }
+    }
+    STAGECHK(v, hipSetDevice(v.device));
+    if (2 * (size_t)n > k->track_stats_cap) {
+        int rc = k->slots.wait_all(v);                                          // launches in flight use what is replaced
+        if (rc == NTSCSIM_OK) rc = audio_grow(v, k->track_stats, k->track_stats_cap, 2 * (size_t)n);
+        if (rc != NTSCSIM_OK) return rc;
+    }
+    v.kernels->clear();
+    audio_drop_marks(k);
+    k->last_tracks = n;
+    const size_t stats_bytes = (size_t)n * 2 * sizeof(uint64_t);
+    const uint32_t L = k->plan_len ? k->plan_len : AUDIO_DEFAULT_SEG;
+    // the rand() position moves at call time, whatever becomes of the launch: tracks in order, blocks in order; a copied
+    // track is no call of the chain and leaves the position alone
+    uint64_t pos = ntscsim_get_rng_pos(c);
+    std::vector<uint64_t> block_pos;                                            // of the blocks that draw
+    block_pos.reserve(mh);
+    for (int t = 0; t < n; t++) {
+        const AudioCfg &cfg = cfgs[(size_t)cfg_of_track[(size_t)t]];
+        if (!cfg.enabled) continue;
+        const bool draws = audio_track_draws(cfg);
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_audio_desc &d = tracks[t].blocks[i];
+            if (d.rng_pos != NTSCSIM_RNG_AUTO) pos = d.rng_pos;
+            if (d.samples && draws) block_pos.push_back(pos);
+            if (draws) pos += (uint64_t)d.samples * (uint64_t)cfg.channels;
+        }
+    }
+    ntscsim_set_rng_pos(c, pos);
+    for (int t = 0; t < n; t++) {                                               // -nocomp tracks: the tool does not call the chain
+        const AudioCfg &cfg = cfgs[(size_t)cfg_of_track[(size_t)t]];
+        if (cfg.enabled) continue;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_audio_desc &d = tracks[t].blocks[i];
+            if (d.samples)
+                STAGECHK(v, hipMemcpyAsync(d.dst, d.src, (size_t)d.samples * (size_t)cfg.channels * sizeof(int16_t), hipMemcpyDeviceToDevice, st));
+        }
+    }
+    if (m == 0) {
+        if (n) STAGECHK(v, hipMemsetAsync(k->track_stats, 0, stats_bytes, st));
+        return NTSCSIM_OK;
+    }
+    // records: the set table, the track table, the blocks that run the chain, the rand() windows of those that draw
+    const size_t cfg_bytes = cfgs.size() * sizeof(AudioCfg), tab_bytes = (size_t)n * sizeof(AudioTrackEnt), blocks_bytes = m * sizeof(AudioBlock),
+                 hb_bytes = mh * sizeof(AudioHissBlock);
+    static_assert(sizeof(AudioCfg) % 8 == 0 && sizeof(AudioTrackEnt) % 8 == 0 && sizeof(AudioBlock) % 8 == 0, "the records follow each other");
+    RecordSlot *slot = nullptr;
+    const int rc = k->slots.acquire(v, cfg_bytes + tab_bytes + blocks_bytes + hb_bytes, slot);
+    if (rc != NTSCSIM_OK) return rc;
+    std::memcpy(slot->host, cfgs.data(), cfg_bytes);
+    AudioTrackEnt *tab = reinterpret_cast<AudioTrackEnt *>(slot->host + cfg_bytes);
+    AudioBlock *blocks = reinterpret_cast<AudioBlock *>(slot->host + cfg_bytes + tab_bytes);
+    AudioHissBlock *hb = reinterpret_cast<AudioHissBlock *>(slot->host + cfg_bytes + tab_bytes + blocks_bytes);
+    int o = 0;
+    uint64_t total_before = 0;                                                  // = the plane of the track, as audio_mixed_layout() sets it
+    for (int t = 0; t < n; t++) {
+        AudioTrackEnt &e = tab[t];
+        std::memset(&e, 0, sizeof(e));
+        e.state = reinterpret_cast<AudioState *>(tracks[t].state);
+        e.block0 = o;
+        e.set = cfg_of_track[(size_t)t];
+        if (cfgs[(size_t)e.set].enabled)
+            for (int i = 0; i < tracks[t].n_blocks; i++) {
+                const ntscsim_audio_desc &d = tracks[t].blocks[i];
+                if (d.samples == 0) continue;
+                blocks[o++] = AudioBlock{d.src, d.dst, total_before + e.frames, d.samples};   // first: in the plane
+                e.frames += d.samples;
+            }
+        e.nblocks = o - e.block0;
+        total_before += e.frames;
+    }
+    uint64_t hiss_items = 0, plane_frames = 0;
+    const uint64_t nseg = audio_mixed_layout(tab, n, cfgs.data(), L, k->plan_warmup_set ? &k->plan_warmup : nullptr, &hiss_items, &plane_frames);
+    uint64_t max_items = 0, max_frames = 0;
+    bool buzz = false;
+    {
+        RandSeq seq(rand_state_origin());
+        uint64_t seq_pos = UINT64_MAX;                                          // where seq stands; UINT64_MAX: nowhere
+        size_t h = 0;
+        for (int t = 0; t < n; t++) {
+            const AudioTrackEnt &e = tab[t];
+            const AudioCfg &cfg = cfgs[(size_t)e.set];
+            if (audio_buzz_on(cfg) && e.frames) {
+                buzz = true;
+                max_frames = std::max(max_frames, e.frames);
+            }
+            if (!audio_track_draws(cfg)) continue;
+            for (int b = e.block0; b < e.block0 + e.nblocks; b++, h++) {
+                audio_hiss_window(hb[h], seq, seq_pos, block_pos[h], e.hiss0 + (blocks[b].first - e.plane) * cfg.channels, blocks[b].frames * cfg.channels,
+                                  cfg.hiss_level);
+                max_items = std::max(max_items, hb[h].items);
+            }
+        }
+    }
+    const bool hiss = hiss_items != 0;
+    if ((hiss && hiss_items > k->hiss_cap) || (buzz && plane_frames > k->pulses_cap) || nseg > k->recs_cap) {
+        int grc = k->slots.wait_all(v);                                         // launches in flight use what is replaced
+        if (grc == NTSCSIM_OK && hiss) grc = audio_grow(v, k->hiss, k->hiss_cap, (size_t)hiss_items);
+        if (grc == NTSCSIM_OK && buzz) grc = audio_grow(v, k->pulses, k->pulses_cap, (size_t)plane_frames);
+        if (grc == NTSCSIM_OK) grc = audio_grow(v, k->recs, k->recs_cap, (size_t)nseg);
+        if (grc != NTSCSIM_OK) return grc;
+    }
+    STAGECHK(v, hipMemcpyAsync(slot->dev, slot->host, cfg_bytes + tab_bytes + blocks_bytes + hb_bytes, hipMemcpyHostToDevice, st));
+    AudioMixedCall call;
+    call.cfgs = reinterpret_cast<const AudioCfg *>(slot->dev);
+    call.tracks = reinterpret_cast<const AudioTrackEnt *>(slot->dev + cfg_bytes);
+    call.blocks = reinterpret_cast<const AudioBlock *>(slot->dev + cfg_bytes + tab_bytes);
+    call.hiss = hiss ? k->hiss : nullptr;
+    call.pulses = buzz ? k->pulses : nullptr;
+    call.nseg = nseg;
+    call.ntracks = n;
+    int lrc = audio_mark(v, k, st);
+    if (lrc != NTSCSIM_OK) return lrc;
+    if (hiss) {
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + cfg_bytes + tab_bytes + blocks_bytes), (int)mh, max_items, k->polys, k->hiss, st);
+        lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
+        if (lrc != NTSCSIM_OK) return lrc;
+    }
+    if (buzz) {
+        const dim3 grid((unsigned)std::min<uint64_t>((max_frames + 255) / 256, 65535), (unsigned)std::min(n, 1024));
+        hipLaunchKernelGGL(k_audio_mixed_pulses, grid, dim3(256), 0, st, call.cfgs, call.tracks, n, k->pulses);
+        lrc = stage_launched(v, nullptr, st, "k_audio_mixed_pulses");
+        if (lrc != NTSCSIM_OK) return lrc;
+    }
+    lrc = audio_mark(v, k, st);
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_audio_mixed_segments, dim3((unsigned)((nseg + AUDIO_GROUPS - 1) / AUDIO_GROUPS)), dim3(64), 0, st, call, k->recs, L);
+    lrc = stage_launched(v, nullptr, st, "k_audio_mixed_segments");
+    if (lrc == NTSCSIM_OK) lrc = audio_mark(v, k, st);
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_audio_mixed_verify, dim3((unsigned)n), dim3(64), 0, st, call, k->recs, L, k->track_stats);
+    lrc = stage_launched(v, slot, st, "k_audio_mixed_verify");
+    return lrc == NTSCSIM_OK ? audio_mark(v, k, st) : lrc;
+}
+
 AudioStageState *audio_of(ntscsim_ctx *c) { return c ? *ctx_stage_view(c).audio : nullptr; }
 
 } // namespace
@@ -841,9 +1222,7 @@ AudioStageState *audio_of(ntscsim_ctx *c) { return c ? *ctx_stage_view(c).audio 
 extern "C" int ntscsim_audio_bind(ntscsim_ctx *c, const ntscsim_audio_params *p)
 {
     if (!c || !p || p->struct_size != sizeof(*p)) return NTSCSIM_E_ARG;
-    if (p->channels < 1 || p->channels > 2 || p->passes != AUDIO_PASSES || p->rate <= 0 || !(p->lowpass_hz > 0) || !(p->highpass_hz > 0) ||
-        p->vsync_lines <= 0 || p->hiss_level < 0 || p->hiss_level > 0x3FFFFFFF)
-        return NTSCSIM_E_PARAM;
+    if (!audio_params_ok(*p)) return NTSCSIM_E_PARAM;
     CtxStageView v = ctx_stage_view(c);
     STAGECHK(v, hipSetDevice(v.device));
     AudioStageState *k = *v.audio;
@@ -881,6 +1260,102 @@ extern "C" int ntscsim_audio_tracks_device(ntscsim_ctx *c, const ntscsim_audio_t
     CtxStageView v = ctx_stage_view(c);
     if (!*v.audio) return NTSCSIM_E_ARG;                                        // ntscsim_audio_bind() first
     return audio_tracks(c, tracks, n_tracks, hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream);
+}
+
+extern "C" int ntscsim_audio_mixed_tracks_device(ntscsim_ctx *c, const ntscsim_audio_params *sets, int n_sets, const ntscsim_audio_mixed_track *tracks,
+                                                 int n_tracks, void *hip_stream)
+{
+    AudioStageState *k = audio_of(c);
+    if (!k) return NTSCSIM_E_ARG;                                               // ntscsim_audio_bind() first
+    std::vector<AudioCfg> cfgs;
+    std::vector<int32_t> cfg_of_track;
+    const int rc = audio_mixed_sets(k, sets, n_sets, tracks, n_tracks, cfgs, cfg_of_track);
+    if (rc != NTSCSIM_OK) return rc;
+    return audio_mixed(c, cfgs, cfg_of_track, tracks, n_tracks, hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx_stage_view(c).stream);
+}
+
+// The host form: every block's samples and every state through the ctx's staging -- [sources | states | results] on
+// both sides, so that one copy goes up and one comes down around ONE device call.
+extern "C" int ntscsim_audio_mixed_tracks_host(ntscsim_ctx *c, const ntscsim_audio_params *sets, int n_sets, const ntscsim_audio_mixed_track *tracks,
+                                               int n_tracks)
+{
+    AudioStageState *k = audio_of(c);
+    if (!k) return NTSCSIM_E_ARG;
+    std::vector<AudioCfg> cfgs;
+    std::vector<int32_t> cfg_of_track;
+    int rc = audio_mixed_sets(k, sets, n_sets, tracks, n_tracks, cfgs, cfg_of_track);
+    if (rc != NTSCSIM_OK) return rc;
+    size_t samples_bytes = 0, n_descs = 0, n_states = 0;
+    for (int t = 0; t < n_tracks; t++) {
+        const size_t fbytes = (size_t)cfgs[(size_t)cfg_of_track[(size_t)t]].channels * sizeof(int16_t);
+        n_states += tracks[t].state != nullptr;
+        n_descs += (size_t)tracks[t].n_blocks;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_audio_desc &d = tracks[t].blocks[i];
+            if (d.samples && (!d.src || !d.dst)) return NTSCSIM_E_ARG;
+            samples_bytes += (size_t)d.samples * fbytes;
+        }
+    }
+    std::vector<uintptr_t> states;
+    for (int t = 0; t < n_tracks; t++)
+        if (tracks[t].state) states.push_back((uintptr_t)tracks[t].state);
+    std::sort(states.begin(), states.end());
+    for (size_t i = 1; i < states.size(); i++)
+        if (states[i] - states[i - 1] < sizeof(AudioState)) return NTSCSIM_E_ARG;   // two tracks would share a state
+    CtxStageView v = ctx_stage_view(c);
+    STAGECHK(v, hipSetDevice(v.device));
+    const size_t src_bytes = (samples_bytes + 255) & ~(size_t)255, states_bytes = (n_states * sizeof(AudioState) + 255) & ~(size_t)255;
+    const size_t whole = 2 * src_bytes + states_bytes;
+    if (whole > k->frames.arena_cap || whole > k->frames.staging_cap) {
+        rc = k->slots.wait_all(v);                                              // launches in flight may use the arena
+        if (rc == NTSCSIM_OK) rc = k->frames.reserve(v, whole, whole);
+        if (rc != NTSCSIM_OK) return rc;
+    }
+    unsigned char *stage = k->frames.staging, *arena = k->frames.arena;
+    std::vector<ntscsim_audio_desc> descs(n_descs);
+    std::vector<ntscsim_audio_mixed_track> dev((size_t)n_tracks);
+    size_t at = 0, s_at = 0, d_at = 0;
+    for (int t = 0; t < n_tracks; t++) {
+        const size_t fbytes = (size_t)cfgs[(size_t)cfg_of_track[(size_t)t]].channels * sizeof(int16_t);
+        dev[(size_t)t] = tracks[t];
+        dev[(size_t)t].blocks = descs.data() + d_at;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            ntscsim_audio_desc &d = descs[d_at++];
+            d = tracks[t].blocks[i];
+            const size_t bytes = (size_t)d.samples * fbytes;
+            if (!bytes) continue;
+            std::memcpy(stage + at, tracks[t].blocks[i].src, bytes);
+            d.src = reinterpret_cast<const int16_t *>(arena + at);
+            d.dst = reinterpret_cast<int16_t *>(arena + src_bytes + states_bytes + at);
+            at += bytes;
+        }
+        if (tracks[t].state) {
+            std::memcpy(stage + src_bytes + s_at, tracks[t].state, sizeof(AudioState));
+            dev[(size_t)t].state = reinterpret_cast<ntscsim_audio_state *>(arena + src_bytes + s_at);
+            s_at += sizeof(AudioState);
+        }
+    }
+    if (src_bytes + states_bytes) STAGECHK(v, hipMemcpyAsync(arena, stage, src_bytes + states_bytes, hipMemcpyHostToDevice, v.stream));
+    rc = audio_mixed(c, cfgs, cfg_of_track, dev.data(), n_tracks, v.stream);
+    if (rc != NTSCSIM_OK) return rc;
+    if (src_bytes + states_bytes)
+        STAGECHK(v, hipMemcpyAsync(stage + src_bytes, arena + src_bytes, states_bytes + src_bytes, hipMemcpyDeviceToHost, v.stream));
+    STAGECHK(v, hipStreamSynchronize(v.stream));
+    at = s_at = 0;
+    for (int t = 0; t < n_tracks; t++) {
+        const size_t fbytes = (size_t)cfgs[(size_t)cfg_of_track[(size_t)t]].channels * sizeof(int16_t);
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const size_t bytes = (size_t)tracks[t].blocks[i].samples * fbytes;
+            if (!bytes) continue;
+            std::memcpy(tracks[t].blocks[i].dst, stage + src_bytes + states_bytes + at, bytes);
+            at += bytes;
+        }
+        if (tracks[t].state) {
+            std::memcpy(tracks[t].state, stage + src_bytes + s_at, sizeof(AudioState));
+            s_at += sizeof(AudioState);
+        }
+    }
+    return NTSCSIM_OK;
 }
 
 extern "C" int ntscsim_audio_host(ntscsim_ctx *c, int16_t *audio, uint32_t samples)

@@ -799,7 +799,7 @@ int cass_blocks(ntscsim_ctx *c, const ntscsim_cass_desc *descs, int n, hipStream
         if (d.samples == 0) continue;
         blocks[o] = CassBlock{d.src, d.dst, first, d.samples};
         if (hiss) {
-            audio_hiss_window(hb[o], seq, seq_pos, block_pos[(size_t)i], first * 2, (uint64_t)d.samples * 2);
+            audio_hiss_window(hb[o], seq, seq_pos, block_pos[(size_t)i], first * 2, (uint64_t)d.samples * 2, cfg.hiss_level);
             max_items = std::max(max_items, hb[o].items);
         }
         first += d.samples;
@@ -816,7 +816,7 @@ int cass_blocks(ntscsim_ctx *c, const ntscsim_cass_desc *descs, int n, hipStream
     int lrc = cass_mark(v, k, st);                                              // 0
     if (lrc != NTSCSIM_OK) return lrc;
     if (hiss) {
-        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + blocks_bytes), m, max_items, k->polys, cfg.hiss_level, k->hiss, st);
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + blocks_bytes), m, max_items, k->polys, k->hiss, st);
         lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
         if (lrc != NTSCSIM_OK) return lrc;
     }
@@ -959,7 +959,7 @@ int cass_tracks(ntscsim_ctx *c, const ntscsim_cass_track *tracks, int n, hipStre
         RandSeq seq(rand_state_origin());
         uint64_t seq_pos = UINT64_MAX;                                          // where seq stands; UINT64_MAX: nowhere
         for (size_t b = 0; b < m; b++) {
-            audio_hiss_window(hb[b], seq, seq_pos, block_pos[b], blocks[b].first * 2, blocks[b].frames * 2);
+            audio_hiss_window(hb[b], seq, seq_pos, block_pos[b], blocks[b].first * 2, blocks[b].frames * 2, cfg.hiss_level);
             max_items = std::max(max_items, hb[b].items);
         }
     }
@@ -986,7 +986,7 @@ int cass_tracks(ntscsim_ctx *c, const ntscsim_cass_track *tracks, int n, hipStre
     int lrc = cass_mark(v, k, st);                                              // 0
     if (lrc != NTSCSIM_OK) return lrc;
     if (hiss) {
-        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + tab_bytes + blocks_bytes), (int)m, max_items, k->polys, cfg.hiss_level, k->hiss, st);
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + tab_bytes + blocks_bytes), (int)m, max_items, k->polys, k->hiss, st);
         lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
         if (lrc != NTSCSIM_OK) return lrc;
     }

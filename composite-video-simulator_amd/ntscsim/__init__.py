@@ -1041,8 +1041,73 @@ class AudioChain:
             stream = self.sim._torch_stream()
         self._call("tracks_device", tracks, n, C.c_void_p(stream))
 
+    def _mixed_tracks(self, sets, set_of, chunks, state_ptrs, blocks):
+        """The argument arrays of a mixed call.  chunks[t]: (src pointer, dst pointer, int16 values) of track t."""
+        n = len(chunks)
+        assert len(set_of) == n and (blocks is None or len(blocks) == n)
+        arr = (_capi.AudioParams * max(1, len(sets)))(*sets)
+        tracks = (_capi.AudioMixedTrack * max(1, n))()
+        keep = [arr]                                                            # the arrays, alive until the call returns
+        for t, (src, dst, numel) in enumerate(chunks):
+            ch = int(sets[set_of[t]].channels) if set_of[t] >= 0 else self.channels
+            total = numel // ch
+            assert total * ch == numel
+            cut = blocks[t] if blocks is not None and blocks[t] is not None else [(total, None)]
+            assert sum(b[0] for b in cut) == total
+            descs = (_capi.AudioDesc * max(1, len(cut)))()
+            at = 0
+            for d, (frames, pos) in zip(descs, cut):
+                d.src = src + at * ch * 2
+                d.dst = dst + at * ch * 2
+                d.samples = int(frames)
+                d.rng_pos = RNG_AUTO if pos is None else int(pos)
+                at += int(frames)
+            keep.append(descs)
+            tracks[t].blocks = descs
+            tracks[t].n_blocks = len(cut)
+            tracks[t].set = int(set_of[t])
+            tracks[t].state = state_ptrs[t]
+        return arr, tracks, keep
+
+    def process_mixed_tracks(self, sets, set_of, srcs, dsts, states=None, blocks=None, stream=None):
+        """ntscsim_audio_mixed_tracks_device: process_tracks() with parameters per track.  sets: a list of
+        ntscsim_audio_params; set_of[t]: the index in it of track t's parameters, or -1 for the chain's own.  A track's
+        tensors hold frames of ITS set's channels.  states, blocks: as process_tracks().  Enqueues; does not
+        synchronise."""
+        n = len(srcs)
+        assert len(dsts) == n
+        base = 0
+        if states is not None:
+            assert states.is_cuda and states.is_contiguous() and states.numel() * states.element_size() == n * self.STATE_BYTES
+            base = states.data_ptr()
+        for src, dst in zip(srcs, dsts):
+            assert src.is_contiguous() and dst.is_contiguous() and dst.numel() == src.numel()
+        chunks = [(s.data_ptr(), d.data_ptr(), s.numel()) for s, d in zip(srcs, dsts)]
+        ptrs = [base + t * self.STATE_BYTES if states is not None else None for t in range(n)]
+        arr, tracks, _keep = self._mixed_tracks(sets, set_of, chunks, ptrs, blocks)
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("mixed_tracks_device", arr, len(sets), tracks, n, C.c_void_p(stream))
+
+    def host_mixed_tracks(self, sets, set_of, arrays, states=None, blocks=None):
+        """ntscsim_audio_mixed_tracks_host: the mixed call in place on numpy int16 arrays whose samples are contiguous
+        (any alignment), one per track.  states: None or a writeable numpy uint8 array of len(arrays) * STATE_BYTES
+        bytes, updated in place.  Synchronous."""
+        n = len(arrays)
+        for a in arrays:
+            assert a.dtype.str in ("<i2", "=i2") and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"]
+        base = 0
+        if states is not None:
+            assert states.dtype.itemsize == 1 and states.flags["C_CONTIGUOUS"] and states.flags["WRITEABLE"] and states.size == n * self.STATE_BYTES
+            base = states.ctypes.data
+        chunks = [(a.ctypes.data, a.ctypes.data, a.size) for a in arrays]
+        ptrs = [base + t * self.STATE_BYTES if states is not None else None for t in range(n)]
+        arr, tracks, _keep = self._mixed_tracks(sets, set_of, chunks, ptrs, blocks)
+        self._call("mixed_tracks_host", arr, len(sets), tracks, n)
+
     def track_stats(self, n):
-        """[(segments, repaired segments)] of tracks 0 .. n-1 of the last process_tracks().  Synchronises."""
+        """[(segments, repaired segments)] of tracks 0 .. n-1 of the last process_tracks() or process_mixed_tracks().
+        Synchronises."""
         s = (_capi.AudioStats * max(1, int(n)))()
         self._call("debug_track_stats", s, int(n))
         return [(int(s[t].segments), int(s[t].repaired)) for t in range(int(n))]

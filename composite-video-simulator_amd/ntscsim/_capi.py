@@ -73,6 +73,7 @@ EXPORTS = (
     "ntscsim_audio_get_state", "ntscsim_audio_set_state", "ntscsim_audio_debug_set_plan", "ntscsim_audio_debug_stats",
     "ntscsim_audio_debug_pulses", "ntscsim_audio_debug_time_kernels", "ntscsim_audio_debug_kernel_ms",
     "ntscsim_audio_tracks_device", "ntscsim_audio_debug_track_stats",
+    "ntscsim_audio_mixed_tracks_device", "ntscsim_audio_mixed_tracks_host",
     "ntscsim_cass_params_init", "ntscsim_cass_parse_argv", "ntscsim_cass_params_derive", "ntscsim_cass_bind", "ntscsim_cass_device",
     "ntscsim_cass_host", "ntscsim_cass_reset", "ntscsim_cass_get_state", "ntscsim_cass_set_state", "ntscsim_cass_debug_set_plan",
     "ntscsim_cass_debug_stats", "ntscsim_cass_debug_time_kernels", "ntscsim_cass_debug_kernel_ms",
@@ -454,6 +455,11 @@ class AudioStats(C.Structure):
 class AudioTrack(C.Structure):
     """struct ntscsim_audio_track"""
     _fields_ = [("blocks", C.POINTER(AudioDesc)), ("n_blocks", C.c_int32), ("_pad", C.c_int32), ("state", C.c_void_p)]
+
+
+class AudioMixedTrack(C.Structure):
+    """struct ntscsim_audio_mixed_track"""
+    _fields_ = [("blocks", C.POINTER(AudioDesc)), ("n_blocks", C.c_int32), ("set", C.c_int32), ("state", C.c_void_p)]
 
 
 CASS_MAX_TAPS = 512
@@ -852,6 +858,10 @@ def lib():
     L.ntscsim_audio_debug_kernel_ms.restype = C.c_int
     L.ntscsim_audio_tracks_device.argtypes = [C.c_void_p, C.POINTER(AudioTrack), C.c_int, C.c_void_p]
     L.ntscsim_audio_tracks_device.restype = C.c_int
+    L.ntscsim_audio_mixed_tracks_device.argtypes = [C.c_void_p, C.POINTER(AudioParams), C.c_int, C.POINTER(AudioMixedTrack), C.c_int, C.c_void_p]
+    L.ntscsim_audio_mixed_tracks_device.restype = C.c_int
+    L.ntscsim_audio_mixed_tracks_host.argtypes = [C.c_void_p, C.POINTER(AudioParams), C.c_int, C.POINTER(AudioMixedTrack), C.c_int]
+    L.ntscsim_audio_mixed_tracks_host.restype = C.c_int
     L.ntscsim_audio_debug_track_stats.argtypes = [C.c_void_p, C.POINTER(AudioStats), C.c_int]
     L.ntscsim_audio_debug_track_stats.restype = C.c_int
     L.ntscsim_cass_params_init.argtypes = [C.POINTER(CassParams)]

@@ -1712,6 +1712,54 @@ typedef struct ntscsim_audio_track {
                                            NULL: start from zeros / count 0, end state discarded                     */
 } ntscsim_audio_track;
 int  ntscsim_audio_tracks_device(ntscsim_ctx *ctx, const ntscsim_audio_track *tracks, int n_tracks, void *hip_stream);
+/*
+ * Many independent streams in one call, EACH WITH ITS OWN PARAMETERS: a tracks call whose tracks name a set of `sets`
+ * (Hi-Fi stereo next to linear mono, SP next to LP and EP, NTSC buzz next to PAL buzz, different hiss levels).  The
+ * call equals, in output bytes, every track's end state and count and the ctx's rand() position, this sequence for
+ * t = 0 .. n_tracks-1 in order: ntscsim_audio_bind(set of track t), ntscsim_audio_set_state(*tracks[t].state),
+ * ntscsim_audio_device(blocks of t), ntscsim_audio_get_state(tracks[t].state) -- but the tracks run side by side in one
+ * launch of each kernel however many sets there are, nothing waits for the device, and the ctx's own carried state and
+ * bound parameters are neither read (except through set == -1) nor written.
+ * Frame size: a block of track t holds samples * channels(set of t) int16; the frame size is the track's, so mono and
+ * stereo tracks stand in one call.
+ * rand() positions: tracks go in order, and blocks in order within a track; NTSCSIM_RNG_AUTO continues from the ctx's
+ * position; a block advances the position by samples * channels only when ITS track's hiss_level != 0; the position
+ * moves at call time.
+ * Buzz: each track's sync buzz runs from its own state's count with its own hsync_hz, vsync_lines and pulse ends; a PAL
+ * track and an NTSC track can share a wavefront.
+ * Disabled tracks: a track whose set has enabled == 0 is copied; it draws nothing (its blocks' rng_pos are not looked
+ * at, as ntscsim_audio_device() does not look at them), keeps its state and reports zero segments.  Its neighbours run
+ * the chain.
+ * Warm-up: with the default plan each track's warm-up is its own set's (72 time constants of ITS high-pass: 25,280
+ * frames at 20 Hz, 5,056 at 100 Hz), so each track is planned exactly as a lone call of its frames would be.
+ * ntscsim_audio_debug_set_plan overrides it for all tracks as it does for the other calls; the segment length is
+ * call-wide.
+ * ntscsim_audio_debug_track_stats and ntscsim_audio_debug_kernel_ms work after a mixed call as they do after a tracks
+ * call; ntscsim_debug_last_kernels names the kernels that ran: k_audio_hiss (when a track draws; the level is per
+ * block), k_audio_mixed_pulses (when a track's buzz is on; tracks without buzz are skipped), k_audio_mixed_segments (a
+ * group of 21 lanes takes the cfg of its segment's track from the call's set table), k_audio_mixed_verify.
+ * A previous ntscsim_audio_bind() is required: it owns the stage's scratch and polynomials.  n_sets == 0 with every
+ * set == -1 is allowed.  `sets`, `tracks` and the block arrays are host memory, consumed by the call.
+ * Refused before anything is enqueued or the rand() position moves -- NTSCSIM_E_ARG: everything
+ * ntscsim_audio_tracks_device refuses, the overlap checks in each track's own frame size; a `set` outside
+ * -1 .. n_sets-1; n_sets < 0; a NULL `sets` that should hold something; a set some track names with a wrong
+ * struct_size.  NTSCSIM_E_PARAM: a set some track names that ntscsim_audio_bind() would refuse.  Sets that no track
+ * names are not looked at.
+ */
+typedef struct ntscsim_audio_mixed_track {
+    const ntscsim_audio_desc *blocks;   /* host memory: ONE continuous stream, as in ntscsim_audio_track               */
+    int32_t                   n_blocks;
+    int32_t                   set;      /* index into `sets`; -1: the parameters of the last ntscsim_audio_bind()      */
+    ntscsim_audio_state      *state;    /* DEVICE pointer, 8-byte aligned; NULL: zeros / count 0, end discarded        */
+} ntscsim_audio_mixed_track;
+int  ntscsim_audio_mixed_tracks_device(ntscsim_ctx *ctx, const ntscsim_audio_params *sets, int n_sets,
+                                       const ntscsim_audio_mixed_track *tracks, int n_tracks, void *hip_stream);
+/* The same call on HOST memory: the block pointers (any alignment) and the states are host memory, dst may equal src
+ * (results are written after every source has been read; other overlaps are the caller's business).  Synchronous.  It
+ * goes through pinned staging of the ctx in ONE device call, not one per track, and returns the same bytes, states and
+ * position as the device call.  Two tracks on one state: NTSCSIM_E_ARG. */
+int  ntscsim_audio_mixed_tracks_host(ntscsim_ctx *ctx, const ntscsim_audio_params *sets, int n_sets,
+                                     const ntscsim_audio_mixed_track *tracks, int n_tracks);
 /* Drop-in for composite_audio_process(audio, samples): HOST memory, in place, through pinned staging of the ctx.
  * Synchronous.  The rand() position is the ctx's. */
 int  ntscsim_audio_host(ntscsim_ctx *ctx, int16_t *audio, uint32_t samples);
@@ -1725,13 +1773,14 @@ int  ntscsim_audio_set_state(ntscsim_ctx *ctx, const ntscsim_audio_state *in);
  * seg_len of 0 is the default length.  seg_len >= the call's frames is the serial form.  pulses: the device's pulse counts of frames count0 .. count0+n-1 (host `out`). */
 int  ntscsim_audio_debug_set_plan(ntscsim_ctx *ctx, uint32_t seg_len, uint32_t warmup);
 int  ntscsim_audio_debug_stats(ntscsim_ctx *ctx, ntscsim_audio_stats *out);
-/* stats of tracks 0 .. n_tracks-1 of the last ntscsim_audio_tracks_device() call (n_tracks beyond that call's:
+/* stats of tracks 0 .. n_tracks-1 of the last ntscsim_audio_tracks_device() or mixed tracks call (n_tracks beyond that call's:
  * NTSCSIM_E_ARG).  Waits for the device. */
 int  ntscsim_audio_debug_track_stats(ntscsim_ctx *ctx, ntscsim_audio_stats *out, int n_tracks);
 int  ntscsim_audio_debug_pulses(ntscsim_ctx *ctx, uint64_t count0, uint32_t n, uint8_t *out);
 int  ntscsim_audio_debug_time_kernels(ntscsim_ctx *ctx, int on);
 /* (k_audio_hiss + k_audio_pulses, k_audio_segments, k_audio_verify_repair) milliseconds of the last call; after a
- * tracks call (k_audio_hiss + k_audio_track_pulses, k_audio_track_segments, k_audio_track_verify) */
+ * tracks call (k_audio_hiss + k_audio_track_pulses, k_audio_track_segments, k_audio_track_verify), after a mixed
+ * tracks call their k_audio_mixed_* counterparts */
 int  ntscsim_audio_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[3]);
 
 /* ------------------------------------------------------------------------------------------

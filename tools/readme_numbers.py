@@ -146,6 +146,24 @@ def audio_tracks_row(path="profiles/audio_tracks.json"):
             "`profiles/audio_tracks.json`, DESIGN.md §7l")
 
 
+def audio_mixed_row(path="profiles/audio_mixed_tracks.json"):
+    """The row of audio tracks with parameters per track, from tools/bench_audio_mixed.py's file."""
+    j = json.load(open(path))
+    m, a_, b = j["mixed_call"], j["a_one_bind_and_tracks_call_per_set"], j["b_all_tracks_on_one_set"]
+    km = m["kernel_ms"]
+    return ("audio tracks with parameters per track in one call (`ntscsim_audio_mixed_tracks_device`): %d independent tracks of %g s resident in HBM over %d sets "
+            "(stereo Hi-Fi, stereo linear, mono SP, mono LP), each with its own state on the device (`tools/bench_audio_mixed.py`); (a) the same tracks as one "
+            "`ntscsim_audio_bind` + `ntscsim_audio_tracks_device` per set, wall clock; (b) %d tracks all on one set (stereo Hi-Fi) through the mixed call and "
+            "through `ntscsim_audio_tracks_device`; all in the same run" % (j["tracks"], j["frames_per_track"] / j["rate"], len(j["sets"]), j["tracks"]),
+            "**%.1f ms** (%.0f × real time); kernels: draws and pulses %.2f, segments %.1f, verify %.2f ms; %d of %d segments repaired; (a) %.1f ms, %.2f × the "
+            "mixed call; (b) mixed call %.1f ms (segments %.1f ms), tracks call %.1f ms (segments %.1f ms): %.3f ×, %d and %d repaired.  Bytes and end states of every "
+            "track equal (a)'s, and in (b) each other's" % (
+                m["ms"], j["times_real_time"], km["draws_and_pulses"], km["k_audio_mixed_segments"], km["k_audio_mixed_verify"], m["repaired"], m["segments"],
+                a_["ms"], j["a_over_mixed"], b["mixed_call"]["ms"], b["mixed_call"]["kernel_ms"]["k_audio_mixed_segments"], b["tracks_call"]["ms"],
+                b["tracks_call"]["kernel_ms"]["k_audio_track_segments"], b["mixed_over_tracks"], b["mixed_call"]["repaired"], b["tracks_call"]["repaired"]),
+            "`profiles/audio_mixed_tracks.json`, DESIGN.md §7l")
+
+
 def cass_tracks_row(path="profiles/cass_tracks.json"):
     """The row of many cassette tracks in one call, from tools/bench_cass_tracks.py's file."""
     j = json.load(open(path))
@@ -174,7 +192,7 @@ def cass_tracks_row(path="profiles/cass_tracks.json"):
             "`profiles/cass_tracks.json`, DESIGN.md §7m")
 
 
-for row in (led_row, filmac_row, audio_tracks_row, cass_tracks_row):
+for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row):
     try:
         rows.append(row())
     except Exception:
