@@ -60,7 +60,7 @@ inline double cass_sin_arg(const CassCfg &c, uint64_t count)
     const double t = (double)count / c.rate;
     return t * 3.14159265358979323846 * 2 * 1.5;
 }
-inline double cass_tilt_of_sin(const CassCfg &c, double s) { return (c.waver * s) + c.tilt; }
+AUDIO_HD double cass_tilt_of_sin(const CassCfg &c, double s) { return (c.waver * s) + c.tilt; }
 inline void cass_fill_tilt(const CassCfg &c, uint64_t count0, uint64_t n, double *tf)
 {
     for (uint64_t i = 0; i < n; i++) tf[i] = cass_tilt_of_sin(c, std::sin(cass_sin_arg(c, count0 + i)));
@@ -560,6 +560,278 @@ inline bool cass_run_tracks_planned(const CassCfg &c, const CassTrackIO *tracks,
         const CassTrackEnt &e = tab[(size_t)t];
         if (!e.frames || !e.state) continue;
         for (uint64_t k = 0; k < h; k++)
+            for (int ch = 0; ch < CASS_CHANNELS; ch++) e.state->hist[k][ch] = xs[(size_t)(e.xs + e.frames + k) * 2 + ch];
+        e.state->front.count = e.count + e.frames;
+        e.state->taps = (uint32_t)c.taps;
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ parameters per track
+// A mixed tracks call (ntscsim_cass_mixed_tracks_device) is a tracks call whose tracks each name a CassCfg of a SET
+// TABLE: one cfg per distinct set that some track names, in order of first use.  What was the call's and is now the
+// track's: the taps (so the size of its section of the x plane, the halo of its tiles and the length of its history),
+// the front's warm-up, pre-emphasis, de-emphasis (tracks without it are packed and closed by the FIR; the back skips
+// them), mono, the hiss level, tilt and waver.  The segment length and the back's warm-up stay the call's.
+// The table that the FIR reads holds the SINES s = sin(cass_sin_arg(count, rate)), not head_tilt_final: s depends on the
+// count and the rate alone, so tracks on different tilt and waver share it, and cass_tilt_of_sin() of the track's cfg --
+// one product and one sum, rounded one by one -- makes head_tilt_final of it where it is used.
+
+struct CassMixedEnt {
+    uint64_t frames, plane, seg0, tile0, xs, tilt, count;   // as CassTrackEnt's; xs counts taps_t - 1 history frames per
+                                         // track, tilt is an offset in the table of sines
+    CassState *state;
+    int32_t block0, nblocks;
+    int32_t set;                         // the track's cfg in the set table
+    uint32_t warm;                       // the front's warm-up of this track
+};
+
+// set_of[t] in -1 .. n_sets - 1 (checked by the caller).  order: the sets of the table, in order of first use;
+// cfg_of[t]: track t's place in it.
+inline void cass_mixed_set_table(const int32_t *set_of, int n, int n_sets, std::vector<int32_t> &order, std::vector<int32_t> &cfg_of)
+{
+    std::vector<int32_t> at((size_t)n_sets + 1, -1);                            // at[set + 1]: its place in the table
+    order.clear();
+    cfg_of.assign((size_t)n, 0);
+    for (int t = 0; t < n; t++) {
+        int32_t &a = at[(size_t)(set_of[t] + 1)];
+        if (a < 0) {
+            a = (int32_t)order.size();
+            order.push_back(set_of[t]);
+        }
+        cfg_of[(size_t)t] = a;
+    }
+}
+
+// fills plane, seg0, tile0, xs and warm of tab[0..n) from frames and set.  warm_all (may be NULL): a debug plan's
+// warm-up for every track; otherwise each track has its own cfg's default, as a lone call of its frames would.
+inline CassTracksTotals cass_mixed_layout(CassMixedEnt *tab, int n, const CassCfg *cfgs, uint32_t L, const uint32_t *warm_all)
+{
+    CassTracksTotals z{0, 0, 0, 0};
+    for (int t = 0; t < n; t++) {
+        const CassCfg &c = cfgs[tab[t].set];
+        tab[t].plane = z.frames;
+        tab[t].seg0 = z.segments;
+        tab[t].tile0 = z.tiles;
+        tab[t].xs = z.xs_frames;
+        tab[t].warm = warm_all ? *warm_all : cass_default_front_warmup(c);
+        z.frames += tab[t].frames;
+        z.segments += audio_seg_count(tab[t].frames, L);
+        z.tiles += audio_seg_count(tab[t].frames, CASS_TILE_FRAMES);
+        z.xs_frames += (uint64_t)(c.taps - 1) + tab[t].frames;
+    }
+    return z;
+}
+
+AUDIO_HD int cass_track_of_seg(const CassMixedEnt *tab, int n, uint64_t j)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (tab[mid].seg0 <= j) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+AUDIO_HD int cass_track_of_tile(const CassMixedEnt *tab, int n, uint64_t i)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (tab[mid].tile0 <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The table of sines: per distinct rate (in order of first use by a track that has frames) the union of the ranges
+// [count, count + frames) of the tracks on that rate, as cass_tilt_layout() makes it; the unions back to back.
+struct CassSineRun {
+    uint64_t count0, n, at;              // counts [count0, count0 + n) stand at table entries [at, at + n)
+    double rate;
+};
+
+// Fills tab[t].tilt (0 for a track without frames) and the runs; *total: entries of the table = sines to evaluate.
+// false: count + frames of a track overflows 64 bits.
+inline bool cass_sine_layout(CassMixedEnt *tab, int n, const CassCfg *cfgs, std::vector<CassSineRun> &runs, uint64_t *total)
+{
+    runs.clear();
+    *total = 0;
+    std::vector<double> rates;
+    for (int t = 0; t < n; t++) {
+        if (tab[t].count + tab[t].frames < tab[t].count) return false;
+        const double r = cfgs[tab[t].set].rate;
+        if (tab[t].frames && std::find(rates.begin(), rates.end(), r) == rates.end()) rates.push_back(r);
+    }
+    for (const double rate : rates) {
+        std::vector<std::pair<uint64_t, int>> order;
+        for (int t = 0; t < n; t++)
+            if (tab[t].frames && cfgs[tab[t].set].rate == rate) order.push_back({tab[t].count, t});
+        std::sort(order.begin(), order.end());
+        const size_t first_run = runs.size();
+        for (const std::pair<uint64_t, int> &o : order) {
+            const int t = o.second;
+            const uint64_t a = tab[t].count, b = a + tab[t].frames;
+            if (runs.size() == first_run || a > runs.back().count0 + runs.back().n) runs.push_back(CassSineRun{a, b - a, *total, rate});
+            else if (b > runs.back().count0 + runs.back().n) runs.back().n = b - runs.back().count0;
+            *total = runs.back().at + runs.back().n;
+            tab[t].tilt = runs.back().at + (a - runs.back().count0);
+        }
+    }
+    for (int t = 0; t < n; t++)
+        if (!tab[t].frames) tab[t].tilt = 0;
+    return true;
+}
+
+// entries [at, at + n) of the table of sines: what one thread of the fill evaluates
+inline void cass_fill_sines_part(const CassSineRun *runs, size_t nruns, uint64_t at, uint64_t n, double *s)
+{
+    CassCfg c;
+    std::memset(&c, 0, sizeof(c));
+    for (size_t r = 0; r < nruns && n; r++) {
+        if (runs[r].at + runs[r].n <= at) continue;
+        const uint64_t skip = at - runs[r].at, m = runs[r].n - skip < n ? runs[r].n - skip : n;
+        c.rate = runs[r].rate;
+        for (uint64_t i = 0; i < m; i++) s[at + i] = std::sin(cass_sin_arg(c, runs[r].count0 + skip + i));
+        at += m;
+        n -= m;
+    }
+}
+
+struct CassMixedIO {                     // host: one track of cass_run_mixed_tracks_planned()
+    CassTrackIO io;
+    int32_t set;                         // in the set table
+};
+
+// Run, verify, repair over tracks that each have a cfg of the set table: what k_cass_mixed_front,
+// k_cass_mixed_front_verify, k_cass_mixed_conv, k_cass_mixed_back and k_cass_mixed_back_verify do, in their order.
+// warm_all: as cass_mixed_layout()'s.  stats[t]: of track t.  tilt_frames (may be NULL): the sines evaluated.
+// false: a count overflows; nothing ran.
+inline bool cass_run_mixed_tracks_planned(const CassCfg *cfgs, const CassMixedIO *tracks, int n, uint32_t L, const uint32_t *warm_all, uint32_t Wb,
+                                          CassPlanStats *stats, uint64_t *tilt_frames = nullptr)
+{
+    for (int t = 0; t < n; t++) stats[t].segments = stats[t].repaired_front = stats[t].repaired_back = 0;
+    if (L == 0) L = 1;
+    std::vector<CassMixedEnt> tab((size_t)n);
+    for (int t = 0; t < n; t++) {
+        CassMixedEnt &e = tab[(size_t)t];
+        std::memset(&e, 0, sizeof(e));
+        e.frames = tracks[t].io.frames;
+        e.count = tracks[t].io.count;
+        e.state = tracks[t].io.state;
+        e.block0 = t;
+        e.nblocks = 1;
+        e.set = tracks[t].set;
+    }
+    std::vector<CassSineRun> runs;
+    uint64_t sines_total = 0;
+    if (!cass_sine_layout(tab.data(), n, cfgs, runs, &sines_total)) return false;
+    if (tilt_frames) *tilt_frames = sines_total;
+    const CassTracksTotals z = cass_mixed_layout(tab.data(), n, cfgs, L, warm_all);
+    std::vector<double> sines((size_t)sines_total + 1), xs((size_t)z.xs_frames * 2 + 2, 0.0), rs((size_t)z.frames * 2 + 2);
+    cass_fill_sines_part(runs.data(), runs.size(), 0, sines_total, sines.data());
+    const auto carried_of = [](const CassMixedEnt &e) {
+        CassTrackEnt u;
+        std::memset(&u, 0, sizeof(u));
+        u.count = e.count;
+        u.state = e.state;
+        return cass_track_carried(u);
+    };
+    {
+        std::vector<CassFront> at_start((size_t)z.segments), at_end((size_t)z.segments);
+        for (uint64_t j = 0; j < z.segments; j++) {                             // the speculative front
+            const int t = cass_track_of_seg(tab.data(), n, j);
+            const CassMixedEnt &e = tab[(size_t)t];
+            const CassCfg &c = cfgs[e.set];
+            const CassTrackIO &io = tracks[t].io;
+            const AudioSeg g = audio_seg(e.frames, L, e.warm, j - e.seg0);
+            const CassFront carried = carried_of(e).front;
+            CassFront s = g.run_start == 0 ? carried : cass_front_spec(c, carried, g.run_start);
+            cass_front_span(c, s, io.src, nullptr, io.hiss, g.run_start, g.start - g.run_start);
+            at_start[(size_t)j] = s;
+            cass_front_span(c, s, io.src, xs.data() + e.xs * 2, io.hiss, g.start, g.len);
+            at_end[(size_t)j] = s;
+        }
+        for (int t = 0; t < n; t++) {                                           // verify, repair: per track
+            const CassMixedEnt &e = tab[(size_t)t];
+            if (!e.frames) continue;
+            const CassCfg &c = cfgs[e.set];
+            const CassTrackIO &io = tracks[t].io;
+            const CassState carried = carried_of(e);
+            for (uint64_t k = 0; k < (uint64_t)(c.taps - 1); k++)
+                for (int ch = 0; ch < CASS_CHANNELS; ch++) xs[(size_t)(e.xs + k) * 2 + ch] = carried.hist[k][ch];
+            const uint64_t nt = audio_seg_count(e.frames, L);
+            CassFront truth = carried.front;
+            for (uint64_t j = 0; j < nt; j++) {
+                const AudioSeg g = audio_seg(e.frames, L, e.warm, j);
+                if (!cass_front_same(at_start[(size_t)(e.seg0 + j)], truth)) {
+                    cass_front_span(c, truth, io.src, xs.data() + e.xs * 2, io.hiss, g.start, g.len);
+                    stats[t].repaired_front++;
+                } else {
+                    truth = at_end[(size_t)(e.seg0 + j)];
+                }
+            }
+            if (e.state) e.state->front = truth;
+            stats[t].segments = nt;
+        }
+    }
+    bool any_post = false;
+    for (uint64_t i = 0; i < z.tiles; i++) {                                    // the FIR by tile; tracks without de-emphasis end here
+        const int t = cass_track_of_tile(tab.data(), n, i);
+        const CassMixedEnt &e = tab[(size_t)t];
+        const CassCfg &c = cfgs[e.set];
+        const uint64_t first = (i - e.tile0) * CASS_TILE_FRAMES, own = e.frames - first < CASS_TILE_FRAMES ? e.frames - first : CASS_TILE_FRAMES;
+        const double *x = xs.data() + e.xs * 2;
+        double *r = rs.data() + e.plane * 2;
+        for (uint64_t f = first; f < first + own; f++) {
+            const double tf = cass_tilt_of_sin(c, sines[(size_t)(e.tilt + f)]);
+            for (int ch = 0; ch < CASS_CHANNELS; ch++) r[f * 2 + ch] = cass_conv<true>(c.taps, tf, ch, x + f * 2 + ch, 2);
+        }
+        if (c.post) {
+            any_post = true;
+        } else {
+            CassBack none = carried_of(e).back;
+            cass_back_span(c, none, r, tracks[t].io.dst, first, own);
+        }
+    }
+    if (any_post) {
+        std::vector<CassBack> at_start((size_t)z.segments), at_end((size_t)z.segments);
+        for (uint64_t j = 0; j < z.segments; j++) {                             // the speculative back
+            const int t = cass_track_of_seg(tab.data(), n, j);
+            const CassMixedEnt &e = tab[(size_t)t];
+            const CassCfg &c = cfgs[e.set];
+            if (!c.post) continue;
+            const AudioSeg g = audio_seg(e.frames, L, Wb, j - e.seg0);
+            CassBack s = carried_of(e).back;
+            if (g.run_start != 0) s.post[0] = s.post[1] = 0;
+            cass_back_span(c, s, rs.data() + e.plane * 2, nullptr, g.run_start, g.start - g.run_start);
+            at_start[(size_t)j] = s;
+            cass_back_span(c, s, rs.data() + e.plane * 2, tracks[t].io.dst, g.start, g.len);
+            at_end[(size_t)j] = s;
+        }
+        for (int t = 0; t < n; t++) {
+            const CassMixedEnt &e = tab[(size_t)t];
+            const CassCfg &c = cfgs[e.set];
+            if (!e.frames || !c.post) continue;
+            const uint64_t nt = audio_seg_count(e.frames, L);
+            CassBack truth = carried_of(e).back;
+            for (uint64_t j = 0; j < nt; j++) {
+                const AudioSeg g = audio_seg(e.frames, L, Wb, j);
+                if (!cass_back_same(at_start[(size_t)(e.seg0 + j)], truth)) {
+                    cass_back_span(c, truth, rs.data() + e.plane * 2, tracks[t].io.dst, g.start, g.len);
+                    stats[t].repaired_back++;
+                } else {
+                    truth = at_end[(size_t)(e.seg0 + j)];
+                }
+            }
+            if (e.state) e.state->back = truth;
+        }
+    }
+    for (int t = 0; t < n; t++) {                                               // the history of the track's own length, the count, the taps
+        const CassMixedEnt &e = tab[(size_t)t];
+        if (!e.frames || !e.state) continue;
+        const CassCfg &c = cfgs[e.set];
+        for (uint64_t k = 0; k < (uint64_t)(c.taps - 1); k++)
             for (int ch = 0; ch < CASS_CHANNELS; ch++) e.state->hist[k][ch] = xs[(size_t)(e.xs + e.frames + k) * 2 + ch];
         e.state->front.count = e.count + e.frames;
         e.state->taps = (uint32_t)c.taps;

@@ -8,7 +8,9 @@
 // sits on the beat of the lane pipeline.  BACK (the two shared de-emphasis poles, pack, downmix) is a recurrence of two
 // values: one lane per segment, a short warm-up, k_cass_back_verify behind it.  head_tilt_final of every frame comes
 // from the host (libm sin), never from the device.
-// ntscsim_cass_tracks_device() runs many such streams side by side through a track table (k_cass_track_*).
+// ntscsim_cass_tracks_device() runs many such streams side by side through a track table (k_cass_track_*);
+// ntscsim_cass_mixed_tracks_device() does so with parameters per track: a set table in the call's records, sections of
+// the x plane of every track's own taps, and a table of sines in place of head_tilt_final (k_cass_mixed_*).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -568,6 +570,224 @@ __global__ __launch_bounds__(64) void k_cass_track_back_verify(CassTracksCall k,
     cass_track_close(k.c, e, seg_len, stats, t);
 }
 
+// ---------------------------------------------------------------------------------------- parameters per track
+// ntscsim_cass_mixed_tracks_device(): a tracks call whose tracks each name a cfg of a SET TABLE (device records of the
+// call, cass_chain.hpp).  The kernels above stay the uniform calls'; these hand the same cass_run_lanes / cass_back_run
+// a view whose cfg is the TRACK's.  A lane of the front loads its track's cfg once, in front of the run, and keeps of
+// it what its stage reads -- its alpha, whether its stage filters, the hiss flag, the offset of frame 0 in its track's
+// section -- so the three groups of a wavefront may serve three tracks on three sets and no step loads from the table.
+// The FIR's table holds sines, not head_tilt_final: cass_tilt_of_sin() of the track's cfg makes the tilt per frame.
+struct CassMixedCall {
+    const CassCfg *cfgs;                 // the set table
+    const CassMixedEnt *tracks;
+    const CassBlock *blocks;             // of all tracks, `first` in the plane
+    const int32_t *hiss;                 // per channel-sample of the plane (written for the tracks that draw), NULL if none does
+    double *xs;                          // the tracks' sections: taps_t - 1 history frames, then the frames of track t
+    uint64_t nseg;                       // segments of the call
+    int ntracks;
+};
+
+__device__ __forceinline__ CassCall cass_mixed_view(const CassMixedCall &k, const CassMixedEnt &e, const CassCfg &c)
+{
+    CassCall v;
+    v.c = c;
+    v.blocks = k.blocks + e.block0;
+    v.hiss = k.hiss;
+    v.xs = k.xs + ((int64_t)e.xs - (int64_t)e.plane) * 2;                       // plane frame plane_t + f: entry taps_t - 1 + f of the section
+    v.total = e.plane + e.frames;
+    v.nblocks = e.nblocks;
+    return v;
+}
+
+__device__ __forceinline__ CassMixedEnt cass_mixed_none()
+{
+    CassMixedEnt e;
+    e.frames = e.plane = e.seg0 = e.tile0 = e.xs = e.tilt = e.count = 0;
+    e.state = nullptr;
+    e.block0 = e.nblocks = e.set = 0;
+    e.warm = 0;
+    return e;
+}
+
+// k_cass_track_front with the cfg and the warm-up of the segment's track
+__global__ __launch_bounds__(64) void k_cass_mixed_front(CassMixedCall k, CassFrontRec *__restrict__ recs, uint32_t seg_len)
+{
+    __shared__ int32_t ring[CASS_GROUPS + 1][2][CASS_RING];
+    __shared__ double init[CASS_GROUPS + 1][CASS_FRONT_VALUES];
+    const int lane = (int)threadIdx.x, g = lane / CASS_LANES, r = lane - g * CASS_LANES;
+    const uint64_t j = (uint64_t)blockIdx.x * CASS_GROUPS + (uint64_t)g;
+    const bool live = g < CASS_GROUPS && j < k.nseg;
+    CassMixedEnt e = cass_mixed_none();
+    AudioSeg s{0, 0, 0};
+    if (live) {
+        e = k.tracks[cass_track_of_seg(k.tracks, k.ntracks, j)];
+        s = audio_seg(e.frames, seg_len, e.warm, j - e.seg0);                    // clamps at frame 0 of this track
+    }
+    const CassCfg c = k.cfgs[e.set];                                            // entry 0 exists whenever a track has frames
+    if (live) {
+        const bool spec = s.run_start != 0;
+        for (int i = r; i < CASS_FRONT_VALUES; i += CASS_LANES) {
+            const double v = (spec && cass_front_live(c, i)) || !e.state ? 0.0 : e.state->front.v[i];
+            init[g][i] = v;
+            recs[j].at_start.v[i] = v;
+            recs[j].at_end.v[i] = v;
+        }
+        if (r == 0) {
+            recs[j].at_start.count = e.count + s.start;
+            recs[j].at_end.count = e.count + s.start + s.len;
+        }
+    }
+    __syncthreads();
+    const CassCall view = cass_mixed_view(k, e, c);
+    cass_run_lanes(view, r, live, e.plane + s.run_start, s.start - s.run_start, s.len, init[g], live ? &recs[j].at_start : nullptr,
+                   live ? &recs[j].at_end : nullptr, ring[g][0], ring[g][1]);
+}
+
+// One workgroup (one wavefront) per track, as k_cass_track_front_verify: the cfg is the workgroup's.
+__global__ __launch_bounds__(64) void k_cass_mixed_front_verify(CassMixedCall k, const CassFrontRec *__restrict__ recs, uint32_t seg_len,
+                                                                uint64_t *__restrict__ stats)
+{
+    __shared__ int32_t ring[2][CASS_RING];
+    __shared__ CassFront truth;
+    __shared__ double init[CASS_FRONT_VALUES];
+    const int lane = (int)threadIdx.x;
+    const CassMixedEnt e = k.tracks[blockIdx.x];
+    if (e.frames == 0) return;
+    const CassCfg c = k.cfgs[e.set];
+    const CassCall view = cass_mixed_view(k, e, c);
+    const uint64_t nseg = audio_seg_count(e.frames, seg_len);
+    recs += e.seg0;
+    double *const sec = k.xs + e.xs * 2;
+    for (int i = lane; i < (c.taps - 1) * 2; i += 64) sec[i] = e.state ? e.state->hist[i >> 1][i & 1] : 0.0;
+    if (lane < CASS_FRONT_VALUES) truth.v[lane] = e.state ? e.state->front.v[lane] : 0.0;
+    if (lane == CASS_FRONT_VALUES) truth.count = e.count;
+    __syncthreads();
+    uint64_t repaired = 0;
+    for (uint64_t j = 0; j < nseg; j++) {
+        bool same = true;
+        if (lane < CASS_FRONT_VALUES) same = __double_as_longlong(recs[j].at_start.v[lane]) == __double_as_longlong(truth.v[lane]);
+        if (lane == CASS_FRONT_VALUES) same = recs[j].at_start.count == truth.count;
+        const bool ok = __all(same);
+        __syncthreads();
+        if (ok) {
+            if (lane < CASS_FRONT_VALUES) truth.v[lane] = recs[j].at_end.v[lane];
+            if (lane == CASS_FRONT_VALUES) truth.count = recs[j].at_end.count;
+        } else {
+            const AudioSeg s = audio_seg(e.frames, seg_len, e.warm, j);
+            if (lane < CASS_FRONT_VALUES) init[lane] = truth.v[lane];
+            __syncthreads();
+            cass_run_lanes(view, lane, lane < CASS_LANES, e.plane + s.start, 0, s.len, init, nullptr, &truth, ring[0], ring[1]);
+            if (lane == 0) truth.count += s.len;
+            repaired++;
+        }
+        __syncthreads();
+    }
+    if (e.state && lane < CASS_FRONT_VALUES) e.state->front.v[lane] = truth.v[lane];
+    if (lane == 0) stats[CASS_STAT_VALUES * (uint64_t)blockIdx.x + 1] = repaired;
+}
+
+__device__ __forceinline__ void cass_mixed_close(int taps, const CassMixedEnt &e, uint32_t seg_len, uint64_t *__restrict__ stats, uint64_t t)
+{
+    if (e.state) {
+        e.state->front.count = e.count + e.frames;
+        e.state->taps = (uint32_t)taps;
+    }
+    stats[CASS_STAT_VALUES * t] = audio_seg_count(e.frames, seg_len);
+}
+
+// One workgroup per call-wide tile.  The halo in front of a tile is its TRACK's taps - 1 frames (the LDS tile has room
+// for CASS_HIST); head_tilt_final is made from the sine of the frame's count and the track's tilt and waver.  A track
+// with de-emphasis leaves r in the plane for the back; one without is packed, downmixed, stored and closed here.
+__global__ __launch_bounds__(CASS_TILE) void k_cass_mixed_conv(CassMixedCall k, const double *__restrict__ sines, double *__restrict__ rs, uint32_t seg_len,
+                                                               uint64_t *__restrict__ stats)
+{
+    __shared__ double tile[2][CASS_TILE + CASS_HIST];
+    const int t = (int)threadIdx.x;
+    const int tr = cass_track_of_tile(k.tracks, k.ntracks, (uint64_t)blockIdx.x);
+    const CassMixedEnt e = k.tracks[tr];
+    const CassCfg c = k.cfgs[e.set];
+    const int taps = c.taps;
+    const uint64_t tile0 = ((uint64_t)blockIdx.x - e.tile0) * CASS_TILE;        // in the track
+    const int own = (int)(e.frames - tile0 < CASS_TILE ? e.frames - tile0 : CASS_TILE);
+    const double *sec = k.xs + e.xs * 2;
+    const double *src = sec + tile0 * 2;                                        // section entry tile0 is frame tile0 - (taps - 1)
+    for (int i = t; i < (own + taps - 1) * 2; i += CASS_TILE) tile[i & 1][i >> 1] = src[i];
+    __syncthreads();
+    if (t < own) {
+        const uint64_t f = tile0 + (uint64_t)t;
+        const double h = cass_tilt_of_sin(c, sines[e.tilt + f]);
+        const double r0 = cass_conv<true>(taps, h, 0, &tile[0][t], 1);
+        const double r1 = cass_conv<true>(taps, h, 1, &tile[1][t], 1);
+        if (c.post) {
+            rs[(e.plane + f) * 2] = r0;
+            rs[(e.plane + f) * 2 + 1] = r1;
+        } else {
+            int16_t o0 = audio_pack(r0), o1 = audio_pack(r1);
+            cass_downmix(c, o0, o1);
+            const CassCall view = cass_mixed_view(k, e, c);
+            const CassBlock &b = view.blocks[cass_find(view, e.plane + f)];
+            int16_t *d = b.dst + (e.plane + f - b.first) * 2;
+            d[0] = o0;
+            d[1] = o1;
+        }
+    }
+    if (tile0 == 0) {
+        if (e.state)
+            for (int i = t; i < (taps - 1) * 2; i += CASS_TILE) e.state->hist[i >> 1][i & 1] = sec[e.frames * 2 + (uint64_t)i];
+        if (!c.post && t == 0) cass_mixed_close(taps, e, seg_len, stats, (uint64_t)tr);
+    }
+}
+
+// one lane per call-wide segment; the segments of tracks without de-emphasis are skipped
+__global__ __launch_bounds__(64) void k_cass_mixed_back(CassMixedCall k, const double *__restrict__ rs, CassBackRec *__restrict__ recs, uint32_t seg_len,
+                                                        uint32_t warmup)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k.nseg) return;
+    const CassMixedEnt e = k.tracks[cass_track_of_seg(k.tracks, k.ntracks, j)];
+    const CassCfg c = k.cfgs[e.set];
+    if (!c.post) return;
+    const CassCall view = cass_mixed_view(k, e, c);
+    const AudioSeg s = audio_seg(e.frames, seg_len, warmup, j - e.seg0);
+    CassBack b{{0.0, 0.0}};
+    if (e.state && s.run_start == 0) b = e.state->back;
+    cass_back_run(view, b, rs, e.plane + s.run_start, s.start - s.run_start, false);
+    recs[j].at_start = b;
+    cass_back_run(view, b, rs, e.plane + s.start, s.len, true);
+    recs[j].at_end = b;
+}
+
+// one lane per track that has de-emphasis: the ordered walk over its records; it closes the track
+__global__ __launch_bounds__(64) void k_cass_mixed_back_verify(CassMixedCall k, const double *__restrict__ rs, const CassBackRec *__restrict__ recs,
+                                                               uint32_t seg_len, uint32_t warmup, uint64_t *__restrict__ stats)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)k.ntracks) return;
+    const CassMixedEnt e = k.tracks[t];
+    if (e.frames == 0) return;
+    const CassCfg c = k.cfgs[e.set];
+    if (!c.post) return;
+    const CassCall view = cass_mixed_view(k, e, c);
+    const uint64_t nseg = audio_seg_count(e.frames, seg_len);
+    recs += e.seg0;
+    CassBack truth{{0.0, 0.0}};
+    if (e.state) truth = e.state->back;
+    uint64_t repaired = 0;
+    for (uint64_t j = 0; j < nseg; j++) {
+        const CassBackRec rec = recs[j];
+        if (cass_back_same(rec.at_start, truth)) {
+            truth = rec.at_end;
+        } else {
+            const AudioSeg s = audio_seg(e.frames, seg_len, warmup, j);
+            cass_back_run(view, truth, rs, e.plane + s.start, s.len, true);
+            repaired++;
+        }
+    }
+    if (e.state) e.state->back = truth;
+    stats[CASS_STAT_VALUES * t + 2] = repaired;
+    cass_mixed_close(c.taps, e, seg_len, stats, t);
+}
+
 // ---------------------------------------------------------------------------------------- host side
 constexpr int CASS_MARKS = 9;
 constexpr int CASS_FILL_THREADS = 4;     // of the sin() fill of a long call; fixed, whatever the host has
@@ -683,9 +903,10 @@ int cass_mark(const CtxStageView &v, CassStageState *k, hipStream_t st)
     return NTSCSIM_OK;
 }
 
-// head_tilt_final of the `total` table entries that the runs describe into the pinned staging (entries are independent: a
-// long table is split over a fixed number of threads), then up on the call's stream
-int cass_upload_tilt_runs(const CtxStageView &v, CassStageState *k, const CassTiltRun *runs, size_t nruns, uint64_t total, hipStream_t st)
+// The `total` entries of the FIR's table into the pinned staging -- part(at, n, table) fills entries [at, at + n); they
+// are independent: a long table is split over a fixed number of threads -- then up on the call's stream
+template <class Part>
+int cass_upload_table(const CtxStageView &v, CassStageState *k, uint64_t total, hipStream_t st, Part part)
 {
     if (k->tf_used) STAGECHK(v, hipEventSynchronize(k->tf_done));                // the last upload still reads the staging
     if (total > k->tf_host_cap) {
@@ -697,15 +918,15 @@ int cass_upload_tilt_runs(const CtxStageView &v, CassStageState *k, const CassTi
     if (!k->tf_done) STAGECHK(v, hipEventCreateWithFlags(&k->tf_done, hipEventDisableTiming));
     const auto t0 = std::chrono::steady_clock::now();
     if (total < CASS_FILL_SPLIT) {
-        cass_fill_tilt_part(k->cfg, runs, nruns, 0, total, k->tf_host);
+        part(0, total, k->tf_host);
     } else {
         std::thread helpers[CASS_FILL_THREADS - 1];
-        const uint64_t part = (total + CASS_FILL_THREADS - 1) / CASS_FILL_THREADS;
+        const uint64_t each = (total + CASS_FILL_THREADS - 1) / CASS_FILL_THREADS;
         for (int i = 1; i < CASS_FILL_THREADS; i++) {
-            const uint64_t at = std::min<uint64_t>(part * (uint64_t)i, total), n = std::min<uint64_t>(part, total - at);
-            helpers[i - 1] = std::thread([k, runs, nruns, at, n]() { cass_fill_tilt_part(k->cfg, runs, nruns, at, n, k->tf_host); });
+            const uint64_t at = std::min<uint64_t>(each * (uint64_t)i, total), n = std::min<uint64_t>(each, total - at);
+            helpers[i - 1] = std::thread([k, part, at, n]() { part(at, n, k->tf_host); });
         }
-        cass_fill_tilt_part(k->cfg, runs, nruns, 0, std::min<uint64_t>(part, total), k->tf_host);
+        part(0, std::min<uint64_t>(each, total), k->tf_host);
         for (std::thread &h : helpers) h.join();
     }
     k->tilt_frames = total;
@@ -716,6 +937,19 @@ int cass_upload_tilt_runs(const CtxStageView &v, CassStageState *k, const CassTi
     STAGECHK(v, hipEventRecord(k->tf_done, st));
     k->tf_used = true;
     return cass_mark(v, k, st);
+}
+
+// head_tilt_final of the bound cfg at the table entries that the runs describe
+int cass_upload_tilt_runs(const CtxStageView &v, CassStageState *k, const CassTiltRun *runs, size_t nruns, uint64_t total, hipStream_t st)
+{
+    const CassCfg cfg = k->cfg;
+    return cass_upload_table(v, k, total, st, [cfg, runs, nruns](uint64_t at, uint64_t n, double *tf) { cass_fill_tilt_part(cfg, runs, nruns, at, n, tf); });
+}
+
+// a mixed call's table: the sines themselves
+int cass_upload_sines(const CtxStageView &v, CassStageState *k, const CassSineRun *runs, size_t nruns, uint64_t total, hipStream_t st)
+{
+    return cass_upload_table(v, k, total, st, [runs, nruns](uint64_t at, uint64_t n, double *s) { cass_fill_sines_part(runs, nruns, at, n, s); });
 }
 
 // the single stream's table: one run from the host's copy of the count
@@ -1023,6 +1257,220 @@ int cass_tracks(ntscsim_ctx *c, const ntscsim_cass_track *tracks, int n, hipStre
     return lrc;
 }
 
+// what ntscsim_cass_bind() accepts
+bool cass_params_ok(const ntscsim_cass_params &p)
+{
+    return !(p.channels != CASS_CHANNELS || p.passes != AUDIO_PASSES || p.rate <= 0 || !(p.lowpass_hz > 0) || !(p.highpass_hz > 0) || p.hiss_level < 0 ||
+             p.hiss_level > 0x3FFFFFFF || p.taps < 1 || p.taps > CASS_MAX_TAPS || !(std::fabs(p.head_tilt) <= CASS_MAX_TAPS) ||
+             p.taps != cass_taps(p.head_tilt));
+}
+
+// What a mixed call checks before it looks at a sample pointer: the shape of the arguments and the sets that tracks
+// name.  cfgs: the set table (cass_mixed_set_table); cfg_of_track[t]: track t's place in it.
+int cass_mixed_sets(const CassStageState *k, const ntscsim_cass_params *sets, int n_sets, const ntscsim_cass_mixed_track *tracks, int n,
+                    std::vector<CassCfg> &cfgs, std::vector<int32_t> &cfg_of_track)
+{
+    if (n_sets < 0 || n < 0 || (n_sets > 0 && !sets) || (n > 0 && !tracks)) return NTSCSIM_E_ARG;
+    std::vector<int32_t> set_of((size_t)n);
+    for (int t = 0; t < n; t++) {
+        const ntscsim_cass_mixed_track &tr = tracks[t];
+        if (tr.set < -1 || tr.set >= n_sets || tr.n_blocks < 0 || (tr.n_blocks > 0 && !tr.blocks)) return NTSCSIM_E_ARG;
+        if (tr.set >= 0 && sets[tr.set].struct_size != sizeof(ntscsim_cass_params)) return NTSCSIM_E_ARG;
+        set_of[(size_t)t] = tr.set;
+    }
+    std::vector<int32_t> order;
+    cass_mixed_set_table(set_of.data(), n, n_sets, order, cfg_of_track);
+    cfgs.clear();
+    for (const int32_t set : order) {
+        if (set >= 0 && !cass_params_ok(sets[set])) return NTSCSIM_E_PARAM;
+        cfgs.push_back(set < 0 ? k->cfg : cass_cfg_of(sets[set]));
+    }
+    return NTSCSIM_OK;
+}
+
+// ntscsim_cass_mixed_tracks_device(): n independent streams, each with the cfg of its set, in one launch of each kernel
+int cass_mixed(ntscsim_ctx *c, const std::vector<CassCfg> &cfgs, const std::vector<int32_t> &cfg_of_track, const ntscsim_cass_mixed_track *tracks, int n,
+               hipStream_t st)
+{
+    CtxStageView v = ctx_stage_view(c);
+    CassStageState *k = *v.cass;
+    const size_t fbytes = 2 * sizeof(int16_t);
+    // every track and descriptor checked before anything is enqueued or the rand() position moves
+    std::vector<Span> srcs;
+    std::vector<uintptr_t> states;
+    uint64_t total = 0;
+    size_t m = 0, mh = 0;                                                       // blocks that have frames; those of them that draw
+    bool post = false;                                                          // some track that has frames has de-emphasis
+    for (int t = 0; t < n; t++) {
+        const ntscsim_cass_mixed_track &tr = tracks[t];
+        const CassCfg &cfg = cfgs[(size_t)cfg_of_track[(size_t)t]];
+        if ((uintptr_t)tr.state & 7) return NTSCSIM_E_ARG;
+        if (tr.state) states.push_back((uintptr_t)tr.state);
+        uint64_t frames = 0;
+        for (int i = 0; i < tr.n_blocks; i++) {
+            const ntscsim_cass_desc &d = tr.blocks[i];
+            if (d.samples == 0) continue;
+            if (!d.src || !d.dst || (((uintptr_t)d.src | (uintptr_t)d.dst) & 1)) return NTSCSIM_E_ARG;
+            srcs.push_back(Span{(uintptr_t)d.src, (uintptr_t)d.src + (size_t)d.samples * fbytes});
+            frames += d.samples;
+            m++;
+            if (cfg.hiss_level != 0) mh++;
+        }
+        if (tr.count + frames < tr.count) return NTSCSIM_E_ARG;                 // the count would wrap inside the track
+        if (frames && cfg.post) post = true;
+        total += frames;
+    }
+    if (m > (size_t)INT32_MAX) return NTSCSIM_E_ARG;
+    std::sort(states.begin(), states.end());
+    for (size_t i = 1; i < states.size(); i++)
+        if (states[i] - states[i - 1] < sizeof(CassState)) return NTSCSIM_E_ARG;    // two tracks would share a state
+    std::sort(srcs.begin(), srcs.end(), [](const Span &x, const Span &y) { return x.a < y.a; });
+    std::vector<uintptr_t> reach(srcs.size());                                  // the furthest end among srcs[0..i]
+    for (size_t i = 0; i < srcs.size(); i++) reach[i] = std::max(srcs[i].b, i ? reach[i - 1] : 0);
+    for (int t = 0; t < n; t++)
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_cass_desc &d = tracks[t].blocks[i];
+            if (d.samples == 0) continue;
+            const uintptr_t a = (uintptr_t)d.dst, b = a + (size_t)d.samples * fbytes;
+            const size_t at = (size_t)(std::lower_bound(srcs.begin(), srcs.end(), b, [](const Span &x, uintptr_t e) { return x.a < e; }) - srcs.begin());
+            if (at > 0 && reach[at - 1] > a) return NTSCSIM_E_ARG;              // a warm-up reads input again, in any track
+        }
+    STAGECHK(v, hipSetDevice(v.device));
+    if ((size_t)CASS_STAT_VALUES * (size_t)n > k->track_stats_cap) {
+        int rc = k->slots.wait_all(v);                                          // launches in flight use what is replaced
+        if (rc == NTSCSIM_OK) rc = cass_grow(v, k->track_stats, k->track_stats_cap, (size_t)CASS_STAT_VALUES * (size_t)n);
+        if (rc != NTSCSIM_OK) return rc;
+    }
+    v.kernels->clear();
+    cass_drop_marks(k);
+    k->last_tracks = n;
+    k->tilt_frames = 0;
+    const bool hiss = mh != 0;
+    const uint32_t L = k->plan_len ? k->plan_len : AUDIO_DEFAULT_SEG;
+    const uint32_t Wb = k->plan_set ? k->plan_back : CASS_DEFAULT_BACK_WARMUP;
+    // the rand() position moves at call time: tracks in order, blocks in order, by the blocks of the tracks that draw
+    uint64_t pos = ntscsim_get_rng_pos(c);
+    std::vector<uint64_t> block_pos;
+    block_pos.reserve(m);
+    for (int t = 0; t < n; t++) {
+        const bool draws = cfgs[(size_t)cfg_of_track[(size_t)t]].hiss_level != 0;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_cass_desc &d = tracks[t].blocks[i];
+            if (d.rng_pos != NTSCSIM_RNG_AUTO) pos = d.rng_pos;
+            if (d.samples) block_pos.push_back(pos);
+            if (draws) pos += (uint64_t)d.samples * 2;
+        }
+    }
+    ntscsim_set_rng_pos(c, pos);
+    if (n) STAGECHK(v, hipMemsetAsync(k->track_stats, 0, (size_t)n * CASS_STAT_VALUES * sizeof(uint64_t), st));
+    if (total == 0) return NTSCSIM_OK;
+    // records: the set table, the track table, the blocks that have frames, the rand() windows of those that draw
+    const size_t cfg_bytes = (cfgs.size() * sizeof(CassCfg) + 15) & ~(size_t)15, tab_bytes = (size_t)n * sizeof(CassMixedEnt),
+                 blocks_bytes = m * sizeof(CassBlock), hb_bytes = mh * sizeof(AudioHissBlock);
+    RecordSlot *slot = nullptr;
+    const int rc = k->slots.acquire(v, cfg_bytes + tab_bytes + blocks_bytes + hb_bytes, slot);
+    if (rc != NTSCSIM_OK) return rc;
+    CassCfg *set_table = reinterpret_cast<CassCfg *>(slot->host);
+    CassMixedEnt *tab = reinterpret_cast<CassMixedEnt *>(slot->host + cfg_bytes);
+    CassBlock *blocks = reinterpret_cast<CassBlock *>(slot->host + cfg_bytes + tab_bytes);
+    AudioHissBlock *hb = reinterpret_cast<AudioHissBlock *>(slot->host + cfg_bytes + tab_bytes + blocks_bytes);
+    std::memset(slot->host, 0, cfg_bytes);
+    std::memcpy(set_table, cfgs.data(), cfgs.size() * sizeof(CassCfg));
+    int o = 0;
+    uint64_t total_before = 0;                                                  // = the plane of the track, as cass_mixed_layout() sets it
+    for (int t = 0; t < n; t++) {
+        CassMixedEnt &e = tab[t];
+        std::memset(&e, 0, sizeof(e));
+        e.count = tracks[t].count;
+        e.state = reinterpret_cast<CassState *>(tracks[t].state);
+        e.set = cfg_of_track[(size_t)t];
+        e.block0 = o;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_cass_desc &d = tracks[t].blocks[i];
+            if (d.samples == 0) continue;
+            blocks[o++] = CassBlock{d.src, d.dst, total_before + e.frames, d.samples};   // first: in the plane
+            e.frames += d.samples;
+        }
+        e.nblocks = o - e.block0;
+        total_before += e.frames;
+    }
+    const CassTracksTotals z = cass_mixed_layout(tab, n, cfgs.data(), L, k->plan_set ? &k->plan_front : nullptr);
+    std::vector<CassSineRun> runs;
+    uint64_t sines_total = 0;
+    if (!cass_sine_layout(tab, n, cfgs.data(), runs, &sines_total)) return NTSCSIM_E_ARG;   // checked above: not reached
+    uint64_t max_items = 0;
+    if (hiss) {
+        RandSeq seq(rand_state_origin());
+        uint64_t seq_pos = UINT64_MAX;                                          // where seq stands; UINT64_MAX: nowhere
+        size_t h = 0;
+        for (int t = 0; t < n; t++) {
+            const int level = cfgs[(size_t)tab[t].set].hiss_level;
+            if (level == 0) continue;
+            for (int b = tab[t].block0; b < tab[t].block0 + tab[t].nblocks; b++, h++) {
+                audio_hiss_window(hb[h], seq, seq_pos, block_pos[(size_t)b], blocks[b].first * 2, blocks[b].frames * 2, level);
+                max_items = std::max(max_items, hb[h].items);
+            }
+        }
+    }
+    if ((hiss && z.frames * 2 > k->hiss_cap) || z.xs_frames * 2 > k->xs_cap || (post && z.frames * 2 > k->rs_cap) || sines_total > k->tf_cap ||
+        z.segments > k->frecs_cap || (post && z.segments > k->brecs_cap)) {
+        int grc = k->slots.wait_all(v);                                         // launches in flight use what is replaced
+        if (grc == NTSCSIM_OK && hiss) grc = cass_grow(v, k->hiss, k->hiss_cap, (size_t)z.frames * 2);
+        if (grc == NTSCSIM_OK) grc = cass_grow(v, k->xs, k->xs_cap, (size_t)z.xs_frames * 2);
+        if (grc == NTSCSIM_OK && post) grc = cass_grow(v, k->rs, k->rs_cap, (size_t)z.frames * 2);
+        if (grc == NTSCSIM_OK) grc = cass_grow(v, k->tf, k->tf_cap, (size_t)sines_total);
+        if (grc == NTSCSIM_OK) grc = cass_grow(v, k->frecs, k->frecs_cap, (size_t)z.segments);
+        if (grc == NTSCSIM_OK && post) grc = cass_grow(v, k->brecs, k->brecs_cap, (size_t)z.segments);
+        if (grc != NTSCSIM_OK) return grc;
+    }
+    STAGECHK(v, hipMemcpyAsync(slot->dev, slot->host, cfg_bytes + tab_bytes + blocks_bytes + hb_bytes, hipMemcpyHostToDevice, st));
+    CassMixedCall call;
+    call.cfgs = reinterpret_cast<const CassCfg *>(slot->dev);
+    call.tracks = reinterpret_cast<const CassMixedEnt *>(slot->dev + cfg_bytes);
+    call.blocks = reinterpret_cast<const CassBlock *>(slot->dev + cfg_bytes + tab_bytes);
+    call.hiss = hiss ? k->hiss : nullptr;
+    call.xs = k->xs;
+    call.nseg = z.segments;
+    call.ntracks = n;
+    int lrc = cass_mark(v, k, st);                                              // 0
+    if (lrc != NTSCSIM_OK) return lrc;
+    if (hiss) {
+        audio_hiss_launch(reinterpret_cast<const AudioHissBlock *>(slot->dev + cfg_bytes + tab_bytes + blocks_bytes), (int)mh, max_items, k->polys, k->hiss, st);
+        lrc = stage_launched(v, nullptr, st, "k_audio_hiss");
+        if (lrc != NTSCSIM_OK) return lrc;
+    }
+    lrc = cass_mark(v, k, st);                                                  // 1
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_cass_mixed_front, dim3((unsigned)((z.segments + CASS_GROUPS - 1) / CASS_GROUPS)), dim3(64), 0, st, call, k->frecs, L);
+    lrc = stage_launched(v, nullptr, st, "k_cass_mixed_front");
+    if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                           // 2
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_cass_mixed_front_verify, dim3((unsigned)n), dim3(64), 0, st, call, k->frecs, L, k->track_stats);
+    lrc = stage_launched(v, nullptr, st, "k_cass_mixed_front_verify");
+    if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                           // 3
+    if (lrc != NTSCSIM_OK) return lrc;
+    // only the FIR reads the sines: the host's fill runs while the front is at work on the device
+    lrc = cass_upload_sines(v, k, runs.data(), runs.size(), sines_total, st);   // 4, 5
+    if (lrc != NTSCSIM_OK) return lrc;
+    hipLaunchKernelGGL(k_cass_mixed_conv, dim3((unsigned)z.tiles), dim3(CASS_TILE), 0, st, call, k->tf, post ? k->rs : (double *)nullptr, L, k->track_stats);
+    lrc = stage_launched(v, post ? nullptr : slot, st, "k_cass_mixed_conv");
+    if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                           // 6
+    if (lrc != NTSCSIM_OK) return lrc;
+    if (post) {
+        hipLaunchKernelGGL(k_cass_mixed_back, dim3((unsigned)((z.segments + 63) / 64)), dim3(64), 0, st, call, k->rs, k->brecs, L, Wb);
+        lrc = stage_launched(v, nullptr, st, "k_cass_mixed_back");
+        if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                       // 7
+        if (lrc != NTSCSIM_OK) return lrc;
+        hipLaunchKernelGGL(k_cass_mixed_back_verify, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, call, k->rs, k->brecs, L, Wb, k->track_stats);
+        lrc = stage_launched(v, slot, st, "k_cass_mixed_back_verify");
+        if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);                       // 8
+    } else {
+        lrc = cass_mark(v, k, st);
+        if (lrc == NTSCSIM_OK) lrc = cass_mark(v, k, st);
+    }
+    return lrc;
+}
+
 CassStageState *cass_of(ntscsim_ctx *c) { return c ? *ctx_stage_view(c).cass : nullptr; }
 
 int cass_put_state(const CtxStageView &v, CassStageState *k, const CassState &s)
@@ -1039,9 +1487,7 @@ int cass_put_state(const CtxStageView &v, CassStageState *k, const CassState &s)
 extern "C" int ntscsim_cass_bind(ntscsim_ctx *c, const ntscsim_cass_params *p)
 {
     if (!c || !p || p->struct_size != sizeof(*p)) return NTSCSIM_E_ARG;
-    if (p->channels != CASS_CHANNELS || p->passes != AUDIO_PASSES || p->rate <= 0 || !(p->lowpass_hz > 0) || !(p->highpass_hz > 0) || p->hiss_level < 0 ||
-        p->hiss_level > 0x3FFFFFFF || p->taps < 1 || p->taps > CASS_MAX_TAPS || !(std::fabs(p->head_tilt) <= CASS_MAX_TAPS) || p->taps != cass_taps(p->head_tilt))
-        return NTSCSIM_E_PARAM;
+    if (!cass_params_ok(*p)) return NTSCSIM_E_PARAM;
     CtxStageView v = ctx_stage_view(c);
     STAGECHK(v, hipSetDevice(v.device));
     CassStageState *k = *v.cass;
@@ -1081,6 +1527,106 @@ extern "C" int ntscsim_cass_tracks_device(ntscsim_ctx *c, const ntscsim_cass_tra
     CtxStageView v = ctx_stage_view(c);
     if (!*v.cass) return NTSCSIM_E_ARG;                                         // ntscsim_cass_bind() first
     return cass_tracks(c, tracks, n_tracks, hip_stream ? static_cast<hipStream_t>(hip_stream) : v.stream);
+}
+
+static_assert(sizeof(ntscsim_cass_mixed_track) == 32 && offsetof(ntscsim_cass_mixed_track, set) == 12 && offsetof(ntscsim_cass_mixed_track, count) == 16 &&
+                  offsetof(ntscsim_cass_mixed_track, state) == 24,
+              "ntscsim_cass_mixed_track is what ntscsim/_capi.py mirrors");
+
+extern "C" int ntscsim_cass_mixed_tracks_device(ntscsim_ctx *c, const ntscsim_cass_params *sets, int n_sets, const ntscsim_cass_mixed_track *tracks,
+                                                int n_tracks, void *hip_stream)
+{
+    CassStageState *k = cass_of(c);
+    if (!k) return NTSCSIM_E_ARG;                                               // ntscsim_cass_bind() first
+    std::vector<CassCfg> cfgs;
+    std::vector<int32_t> cfg_of_track;
+    const int rc = cass_mixed_sets(k, sets, n_sets, tracks, n_tracks, cfgs, cfg_of_track);
+    if (rc != NTSCSIM_OK) return rc;
+    return cass_mixed(c, cfgs, cfg_of_track, tracks, n_tracks, hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx_stage_view(c).stream);
+}
+
+// The host form: every block's samples and every state through the ctx's staging -- [sources | states | results] on
+// both sides, so that one copy goes up and one comes down around ONE device call.
+extern "C" int ntscsim_cass_mixed_tracks_host(ntscsim_ctx *c, const ntscsim_cass_params *sets, int n_sets, const ntscsim_cass_mixed_track *tracks,
+                                              int n_tracks)
+{
+    CassStageState *k = cass_of(c);
+    if (!k) return NTSCSIM_E_ARG;
+    std::vector<CassCfg> cfgs;
+    std::vector<int32_t> cfg_of_track;
+    int rc = cass_mixed_sets(k, sets, n_sets, tracks, n_tracks, cfgs, cfg_of_track);
+    if (rc != NTSCSIM_OK) return rc;
+    const size_t fbytes = 2 * sizeof(int16_t);
+    size_t samples_bytes = 0, n_descs = 0, n_states = 0;
+    std::vector<uintptr_t> states;
+    for (int t = 0; t < n_tracks; t++) {
+        if (tracks[t].state) states.push_back((uintptr_t)tracks[t].state);
+        n_descs += (size_t)tracks[t].n_blocks;
+        uint64_t frames = 0;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const ntscsim_cass_desc &d = tracks[t].blocks[i];
+            if (d.samples && (!d.src || !d.dst)) return NTSCSIM_E_ARG;
+            samples_bytes += (size_t)d.samples * fbytes;
+            frames += d.samples;
+        }
+        if (tracks[t].count + frames < tracks[t].count) return NTSCSIM_E_ARG;   // refused before the staging is touched
+    }
+    n_states = states.size();
+    std::sort(states.begin(), states.end());
+    for (size_t i = 1; i < states.size(); i++)
+        if (states[i] - states[i - 1] < sizeof(CassState)) return NTSCSIM_E_ARG;    // two tracks would share a state
+    CtxStageView v = ctx_stage_view(c);
+    STAGECHK(v, hipSetDevice(v.device));
+    const size_t src_bytes = (samples_bytes + 255) & ~(size_t)255, states_bytes = (n_states * sizeof(CassState) + 255) & ~(size_t)255;
+    const size_t whole = 2 * src_bytes + states_bytes;
+    if (whole > k->frames.arena_cap || whole > k->frames.staging_cap) {
+        rc = k->slots.wait_all(v);                                              // launches in flight may use the arena
+        if (rc == NTSCSIM_OK) rc = k->frames.reserve(v, whole, whole);
+        if (rc != NTSCSIM_OK) return rc;
+    }
+    unsigned char *stage = k->frames.staging, *arena = k->frames.arena;
+    std::vector<ntscsim_cass_desc> descs(n_descs);
+    std::vector<ntscsim_cass_mixed_track> dev((size_t)n_tracks);
+    size_t at = 0, s_at = 0, d_at = 0;
+    for (int t = 0; t < n_tracks; t++) {
+        dev[(size_t)t] = tracks[t];
+        dev[(size_t)t].blocks = descs.data() + d_at;
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            ntscsim_cass_desc &d = descs[d_at++];
+            d = tracks[t].blocks[i];
+            const size_t bytes = (size_t)d.samples * fbytes;
+            if (!bytes) continue;
+            std::memcpy(stage + at, tracks[t].blocks[i].src, bytes);
+            d.src = reinterpret_cast<const int16_t *>(arena + at);
+            d.dst = reinterpret_cast<int16_t *>(arena + src_bytes + states_bytes + at);
+            at += bytes;
+        }
+        if (tracks[t].state) {
+            std::memcpy(stage + src_bytes + s_at, tracks[t].state, sizeof(CassState));
+            dev[(size_t)t].state = reinterpret_cast<ntscsim_cass_state *>(arena + src_bytes + s_at);
+            s_at += sizeof(CassState);
+        }
+    }
+    if (src_bytes + states_bytes) STAGECHK(v, hipMemcpyAsync(arena, stage, src_bytes + states_bytes, hipMemcpyHostToDevice, v.stream));
+    rc = cass_mixed(c, cfgs, cfg_of_track, dev.data(), n_tracks, v.stream);
+    if (rc != NTSCSIM_OK) return rc;
+    if (src_bytes + states_bytes)
+        STAGECHK(v, hipMemcpyAsync(stage + src_bytes, arena + src_bytes, states_bytes + src_bytes, hipMemcpyDeviceToHost, v.stream));
+    STAGECHK(v, hipStreamSynchronize(v.stream));
+    at = s_at = 0;
+    for (int t = 0; t < n_tracks; t++) {
+        for (int i = 0; i < tracks[t].n_blocks; i++) {
+            const size_t bytes = (size_t)tracks[t].blocks[i].samples * fbytes;
+            if (!bytes) continue;
+            std::memcpy(tracks[t].blocks[i].dst, stage + src_bytes + states_bytes + at, bytes);
+            at += bytes;
+        }
+        if (tracks[t].state) {
+            std::memcpy(tracks[t].state, stage + src_bytes + s_at, sizeof(CassState));
+            s_at += sizeof(CassState);
+        }
+    }
+    return NTSCSIM_OK;
 }
 
 extern "C" int ntscsim_cass_host(ntscsim_ctx *c, int16_t *audio, uint32_t samples)

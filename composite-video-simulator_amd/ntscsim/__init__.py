@@ -1296,9 +1296,73 @@ class Cassette:
             stream = self.sim._torch_stream()
         self._call("tracks_device", tracks, n, C.c_void_p(stream))
 
+    def _mixed_tracks(self, sets, set_of, chunks, counts, state_ptrs, blocks):
+        """The argument arrays of a mixed call.  chunks[t]: (src pointer, dst pointer, int16 values) of track t."""
+        n = len(chunks)
+        assert len(set_of) == n and len(counts) == n and (blocks is None or len(blocks) == n)
+        arr = (_capi.CassParams * max(1, len(sets)))(*sets)
+        tracks = (_capi.CassMixedTrack * max(1, n))()
+        keep = [arr]                                                            # the arrays, alive until the call returns
+        for t, (src, dst, numel) in enumerate(chunks):
+            total = numel // 2
+            assert total * 2 == numel
+            cut = blocks[t] if blocks is not None and blocks[t] is not None else [(total, None)]
+            assert sum(b[0] for b in cut) == total
+            descs = (_capi.CassDesc * max(1, len(cut)))()
+            at = 0
+            for d, (frames, pos) in zip(descs, cut):
+                d.src = src + at * 4
+                d.dst = dst + at * 4
+                d.samples = int(frames)
+                d.rng_pos = RNG_AUTO if pos is None else int(pos)
+                at += int(frames)
+            keep.append(descs)
+            tracks[t].blocks = descs
+            tracks[t].n_blocks = len(cut)
+            tracks[t].set = int(set_of[t])
+            tracks[t].count = int(counts[t])
+            tracks[t].state = state_ptrs[t]
+        return arr, tracks, keep
+
+    def process_mixed_tracks(self, sets, set_of, srcs, dsts, counts, states=None, blocks=None, stream=None):
+        """ntscsim_cass_mixed_tracks_device: process_tracks() with parameters per track.  sets: a list of
+        ntscsim_cass_params; set_of[t]: the index in it of track t's parameters, or -1 for the chain's own.  counts,
+        states, blocks: as process_tracks(); the history of a track's state has the length of ITS set's taps - 1.
+        Enqueues; does not synchronise."""
+        n = len(srcs)
+        assert len(dsts) == n
+        base = 0
+        if states is not None:
+            assert states.is_cuda and states.is_contiguous() and states.numel() * states.element_size() == n * self.STATE_BYTES
+            base = states.data_ptr()
+        for src, dst in zip(srcs, dsts):
+            assert src.is_contiguous() and dst.is_contiguous() and dst.numel() == src.numel()
+        chunks = [(s.data_ptr(), d.data_ptr(), s.numel()) for s, d in zip(srcs, dsts)]
+        ptrs = [base + t * self.STATE_BYTES if states is not None else None for t in range(n)]
+        arr, tracks, _keep = self._mixed_tracks(sets, set_of, chunks, counts, ptrs, blocks)
+        if stream is None:
+            stream = self.sim._torch_stream()
+        self._call("mixed_tracks_device", arr, len(sets), tracks, n, C.c_void_p(stream))
+
+    def host_mixed_tracks(self, sets, set_of, arrays, counts, states=None, blocks=None):
+        """ntscsim_cass_mixed_tracks_host: the mixed call in place on numpy int16 arrays whose samples are contiguous
+        (any alignment), one per track.  states: None or a writeable numpy uint8 array of len(arrays) * STATE_BYTES
+        bytes, updated in place.  Synchronous."""
+        n = len(arrays)
+        for a in arrays:
+            assert a.dtype.str in ("<i2", "=i2") and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"]
+        base = 0
+        if states is not None:
+            assert states.dtype.itemsize == 1 and states.flags["C_CONTIGUOUS"] and states.flags["WRITEABLE"] and states.size == n * self.STATE_BYTES
+            base = states.ctypes.data
+        chunks = [(a.ctypes.data, a.ctypes.data, a.size) for a in arrays]
+        ptrs = [base + t * self.STATE_BYTES if states is not None else None for t in range(n)]
+        arr, tracks, _keep = self._mixed_tracks(sets, set_of, chunks, counts, ptrs, blocks)
+        self._call("mixed_tracks_host", arr, len(sets), tracks, n)
+
     def track_stats(self, n):
         """[(segments, segments the front repaired, segments the back repaired)] of tracks 0 .. n-1 of the last
-        process_tracks().  Synchronises."""
+        process_tracks() or process_mixed_tracks().  Synchronises."""
         s = (_capi.CassStats * max(1, int(n)))()
         self._call("debug_track_stats", s, int(n))
         return [(int(s[t].segments), int(s[t].repaired_front), int(s[t].repaired_back)) for t in range(int(n))]

@@ -78,6 +78,7 @@ EXPORTS = (
     "ntscsim_cass_host", "ntscsim_cass_reset", "ntscsim_cass_get_state", "ntscsim_cass_set_state", "ntscsim_cass_debug_set_plan",
     "ntscsim_cass_debug_stats", "ntscsim_cass_debug_time_kernels", "ntscsim_cass_debug_kernel_ms",
     "ntscsim_cass_tracks_device", "ntscsim_cass_debug_track_stats", "ntscsim_cass_debug_tilt_frames",
+    "ntscsim_cass_mixed_tracks_device", "ntscsim_cass_mixed_tracks_host",
 )
 
 
@@ -500,6 +501,12 @@ class CassTrack(C.Structure):
                 ("state", C.c_void_p)]
 
 
+class CassMixedTrack(C.Structure):
+    """struct ntscsim_cass_mixed_track"""
+    _fields_ = [("blocks", C.POINTER(CassDesc)), ("n_blocks", C.c_int32), ("set", C.c_int32), ("count", C.c_uint64),
+                ("state", C.c_void_p)]
+
+
 _u8p = C.POINTER(C.c_uint8)
 _lib = None
 
@@ -892,6 +899,10 @@ def lib():
     L.ntscsim_cass_debug_kernel_ms.restype = C.c_int
     L.ntscsim_cass_tracks_device.argtypes = [C.c_void_p, C.POINTER(CassTrack), C.c_int, C.c_void_p]
     L.ntscsim_cass_tracks_device.restype = C.c_int
+    L.ntscsim_cass_mixed_tracks_device.argtypes = [C.c_void_p, C.POINTER(CassParams), C.c_int, C.POINTER(CassMixedTrack), C.c_int, C.c_void_p]
+    L.ntscsim_cass_mixed_tracks_device.restype = C.c_int
+    L.ntscsim_cass_mixed_tracks_host.argtypes = [C.c_void_p, C.POINTER(CassParams), C.c_int, C.POINTER(CassMixedTrack), C.c_int]
+    L.ntscsim_cass_mixed_tracks_host.restype = C.c_int
     L.ntscsim_cass_debug_track_stats.argtypes = [C.c_void_p, C.POINTER(CassStats), C.c_int]
     L.ntscsim_cass_debug_track_stats.restype = C.c_int
     L.ntscsim_cass_debug_tilt_frames.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]

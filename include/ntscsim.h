@@ -1906,6 +1906,57 @@ typedef struct ntscsim_cass_track {
                                           NULL: start from zeros, end state discarded                                 */
 } ntscsim_cass_track;
 int  ntscsim_cass_tracks_device(ntscsim_ctx *ctx, const ntscsim_cass_track *tracks, int n_tracks, void *hip_stream);
+/*
+ * The tracks call with parameters PER TRACK: a library of tapes, a worn deck (-preset 3, 57 taps) next to a good one (8
+ * taps), mono next to stereo, de-emphasis on some, a hiss level and a band limit each.  Track t names one of `sets`
+ * (set == -1: the parameters of the last ntscsim_cass_bind()).  The call equals, in output bytes, in every end state
+ * (the 28 filter values, the FIR history of THAT track's taps - 1 frames, count, taps) and in the ctx's rand() position,
+ * this sequence for t = 0 .. n_tracks-1 in order: ntscsim_cass_bind(set of t), ntscsim_cass_set_state(*state_t with
+ * count = tracks[t].count and taps = that set's), ntscsim_cass_device(blocks of t), ntscsim_cass_get_state(state_t) --
+ * but each kernel is launched once however many sets there are, nothing waits for the device, and the ctx's bound
+ * parameters, carried state and host-side count are neither read (except through set == -1) nor written.
+ * State on entry and exit: as ntscsim_cass_tracks_device(), with "the bound taps" read as "the taps of the track's
+ * set": count and taps are ignored on entry and written on exit; a track shorter than its own taps - 1 keeps the rest
+ * of its history; tracks without frames are left alone.
+ * rand() positions: tracks in order, blocks in order within a track; a block advances the position by 2 * samples only
+ * when ITS track's hiss_level != 0; the position moves at call time.
+ * Warm-up: with the default plan the front's warm-up of a track is its own set's (72 time constants of ITS high-pass:
+ * 25,280 frames at 20 Hz, 5,056 at 100 Hz), so each track is planned exactly as a lone call of its frames would be;
+ * ntscsim_cass_debug_set_plan overrides it for all tracks.  Segment length and the back's warm-up are call-wide.
+ * Sines: the table the FIR reads holds sin() of each sample count -- it depends on the count and the rate alone -- over
+ * the union of [count, count + frames) of the tracks whose sets share a rate, one union per distinct rate; the device
+ * makes head_tilt_final = (waver * s) + tilt from it per frame with the track's tilt and waver, the same two rounded
+ * operations the tool performs.  Tracks on different decks that cover the same counts share their sines
+ * (ntscsim_cass_debug_tilt_frames).  The host calls sin(); the device never does.
+ * Kernels (ntscsim_debug_last_kernels): k_audio_hiss (when some track draws; blocks of tracks that draw nothing are not
+ * in its launch), k_cass_mixed_front (a lane takes what its stage reads of its track's cfg from the call's set table
+ * in front of the run), k_cass_mixed_front_verify, k_cass_mixed_conv (the halo of a tile is its track's taps - 1; a
+ * track without de-emphasis is packed, stored and closed here), and -- only if some track that has frames has
+ * de-emphasis -- k_cass_mixed_back and k_cass_mixed_back_verify, which skip the tracks that have none.
+ * ntscsim_cass_debug_track_stats, _tilt_frames, _kernel_ms (the same eight slots) and _set_plan work as after a tracks
+ * call; repaired_back of a track without de-emphasis is 0.
+ * A previous ntscsim_cass_bind() is required: it owns the stage's scratch and polynomials.  n_sets == 0 with every
+ * set == -1 is allowed.  `sets`, `tracks` and the block arrays are host memory, consumed by the call.
+ * Refused before anything is enqueued or the rand() position moves -- NTSCSIM_E_ARG: everything
+ * ntscsim_cass_tracks_device refuses; a `set` outside -1 .. n_sets-1; n_sets < 0; a NULL `sets` that should hold
+ * something; a set some track names with a wrong struct_size.  NTSCSIM_E_PARAM: a set some track names that
+ * ntscsim_cass_bind() would refuse.  Sets that no track names are not looked at.
+ */
+typedef struct ntscsim_cass_mixed_track {
+    const ntscsim_cass_desc *blocks;   /* host memory: ONE continuous stream, as in ntscsim_cass_track                */
+    int32_t                  n_blocks;
+    int32_t                  set;      /* index into `sets`; -1: the parameters of the last ntscsim_cass_bind()       */
+    uint64_t                 count;    /* the HOST's audio_proc_count of the first frame, as in ntscsim_cass_track    */
+    ntscsim_cass_state      *state;    /* DEVICE pointer, 8-byte aligned; NULL: zeros, end discarded                  */
+} ntscsim_cass_mixed_track;
+int  ntscsim_cass_mixed_tracks_device(ntscsim_ctx *ctx, const ntscsim_cass_params *sets, int n_sets,
+                                      const ntscsim_cass_mixed_track *tracks, int n_tracks, void *hip_stream);
+/* The same call on HOST memory: the block pointers (any alignment) and the states are host memory, dst may equal src
+ * (results are written after every source has been read; other overlaps are the caller's business).  Synchronous.  It
+ * goes through pinned staging of the ctx [sources | states | results]: one copy up, ONE device call, one copy down,
+ * and returns the same bytes, states and position as the device call.  Two tracks on one state: NTSCSIM_E_ARG. */
+int  ntscsim_cass_mixed_tracks_host(ntscsim_ctx *ctx, const ntscsim_cass_params *sets, int n_sets,
+                                    const ntscsim_cass_mixed_track *tracks, int n_tracks);
 /* Drop-in for composite_audio_process(audio, samples): HOST memory, in place, any alignment.  Synchronous. */
 int  ntscsim_cass_host(ntscsim_ctx *ctx, int16_t *audio, uint32_t samples);
 /* reset: the tool's start.  get / set: a track processed in pieces, or started at any sample count.  set refuses a
@@ -1917,15 +1968,16 @@ int  ntscsim_cass_set_state(ntscsim_ctx *ctx, const ntscsim_cass_state *in);
  * 72 time constants of the high-pass for the front, 64 frames for the back); any other triple is taken as given. */
 int  ntscsim_cass_debug_set_plan(ntscsim_ctx *ctx, uint32_t seg_len, uint32_t warmup_front, uint32_t warmup_back);
 int  ntscsim_cass_debug_stats(ntscsim_ctx *ctx, ntscsim_cass_stats *out);
-/* stats of tracks 0 .. n_tracks-1 of the last ntscsim_cass_tracks_device() call (n_tracks beyond that call's:
+/* stats of tracks 0 .. n_tracks-1 of the last ntscsim_cass_tracks_device() or mixed tracks call (n_tracks beyond that call's:
  * NTSCSIM_E_ARG).  Waits for the device.  set_plan applies to a tracks call as it does to the single call. */
 int  ntscsim_cass_debug_track_stats(ntscsim_ctx *ctx, ntscsim_cass_stats *out, int n_tracks);
-/* sines the last call's host fill evaluated: a single call's frames; a tracks call's union of [count, count + frames) */
+/* sines the last call's host fill evaluated: a single call's frames; a tracks call's union of [count, count + frames);
+ * a mixed tracks call's unions, one per distinct rate */
 int  ntscsim_cass_debug_tilt_frames(ntscsim_ctx *ctx, uint64_t *evaluated);
 int  ntscsim_cass_debug_time_kernels(ntscsim_ctx *ctx, int on);
 /* milliseconds of the last call: [0] the host's sin fill (CPU clock), [1] its upload, [2] k_audio_hiss, [3] k_cass_front,
  * [4] k_cass_front_verify, [5] k_cass_conv, [6] k_cass_back, [7] k_cass_back_verify; after a tracks call the same
- * eight slots hold the k_cass_track_* kernel of the same name */
+ * eight slots hold the k_cass_track_* kernel of the same name, after a mixed tracks call the k_cass_mixed_* one */
 int  ntscsim_cass_debug_kernel_ms(ntscsim_ctx *ctx, float out_ms[8]);
 
 #ifdef __cplusplus

@@ -192,7 +192,27 @@ def cass_tracks_row(path="profiles/cass_tracks.json"):
             "`profiles/cass_tracks.json`, DESIGN.md §7m")
 
 
-for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row):
+def cass_mixed_row(path="profiles/cass_mixed_tracks.json"):
+    """The row of cassette tracks with parameters per track, from tools/bench_cass_mixed.py's file."""
+    j = json.load(open(path))
+    m, a_, b = j["mixed_call"], j["a_one_bind_and_tracks_call_per_set"], j["b_all_tracks_on_one_set"]
+    km = m["kernel_ms"]
+    return ("cassette tracks with parameters per track in one call (`ntscsim_cass_mixed_tracks_device`): %d independent stereo tracks of %g s resident in HBM over "
+            "%d sets (default, `-preset 3`, both emphasis filters, mono at `-high 100`; %s taps), all from sample count 0, each with its own state on the device "
+            "(`tools/bench_cass_mixed.py`); (a) the same tracks as one `ntscsim_cass_bind` + `ntscsim_cass_tracks_device` per set, wall clock; (b) %d tracks all "
+            "on one set (default) through the mixed call and through `ntscsim_cass_tracks_device`; all in the same run"
+            % (j["tracks"], j["frames_per_track"] / j["rate"], len(j["sets"]), " / ".join(str(t) for t in j["taps"]), b["tracks"]),
+            "**%.1f ms** (%.0f × real time); kernels: draws %.2f, front %.1f, its verify %.2f, FIR %.2f, back %.2f + %.2f ms; host `sin()` fill %.2f ms for %d sines "
+            "(one tape's, shared by the four decks); %d + %d of %d segments repaired; (a) %.1f ms, %.2f × the mixed call; (b) mixed call %.1f ms (front %.1f ms), "
+            "tracks call %.1f ms (front %.1f ms): %.3f ×.  Bytes and end states of every track equal (a)'s, and in (b) each other's" % (
+                m["ms"], j["times_real_time"], km["k_audio_hiss"], km["k_cass_mixed_front"], km["k_cass_mixed_front_verify"], km["k_cass_mixed_conv"],
+                km["k_cass_mixed_back"], km["k_cass_mixed_back_verify"], km["host_sin_fill"], m["tilt_frames"], m["repaired_front"], m["repaired_back"],
+                m["segments"], a_["ms"], j["a_over_mixed"], b["mixed_call"]["ms"], b["mixed_call"]["kernel_ms"]["k_cass_mixed_front"], b["tracks_call"]["ms"],
+                b["tracks_call"]["kernel_ms"]["k_cass_track_front"], b["mixed_over_tracks"]),
+            "`profiles/cass_mixed_tracks.json`, DESIGN.md §7m")
+
+
+for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row, cass_mixed_row):
     try:
         rows.append(row())
     except Exception:
