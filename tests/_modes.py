@@ -1,6 +1,7 @@
 """ctypes bindings of oracle/ntsc_modes_oracle.h (the mode model: exact64 / fast32 / real64 / real32), the inputs and the
-case list shared by tests/test_modes_oracle.py (CPU), tests/test_float_model_gpu.py, tests/test_fast32_model_gpu.py and
-tools/float_model_err.py.  Test infrastructure only; no GPU import."""
+case list shared by tests/test_modes_oracle.py (CPU), tests/test_float_model_gpu.py, tests/test_fast32_model_gpu.py, the
+FAST32 form table (tests/_fast32_forms.py and its two test files) and tools/float_model_err.py.  Test infrastructure only;
+no GPU import."""
 import ctypes as C
 
 import numpy as np
@@ -106,12 +107,29 @@ def saturating(w, h):
     return fr
 
 
+def decay(w, h):
+    """rows whose first W/8 pixels are saturated blue with a little red and whose last W/8 are green, black between: the
+    chroma states fall towards zero over the black run (hundreds of samples at W = 720) before colour returns -- long
+    decays, where a kernel that flushed small states to zero would part from the model.  (Whether the float states reach
+    the subnormal range at W = 720 has not been measured.)  Every third row is all 0, every fifth all 255 (a row that is
+    both is 255)."""
+    e = max(1, w // 8)
+    fr = np.zeros((h, w, 4), np.uint8)
+    fr[:, :e, 0], fr[:, :e, 2] = 255, 24          # memory order B, G, R
+    fr[:, w - e:, 1] = 255
+    fr[0::3, :, :3] = 0
+    fr[0::5, :, :3] = 255
+    return fr
+
+
 def sources(kind, w, h):
     """the source frames of a case: field k reads frame k % len"""
     if kind == "mixed":
         return [L.noise_frame(w, h, 0x51 + w + h), L.bars(w, h, 3), ramp(w, h)]
     if kind == "saturating":
         return [saturating(w, h)]
+    if kind == "decay":
+        return [decay(w, h)]
     if kind == "noise":
         return [L.noise_frame(w, h, 0x51 + w + h), L.noise_frame(w, h, 0x52 + w + h)]
     raise ValueError(kind)
