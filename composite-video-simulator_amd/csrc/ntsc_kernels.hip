@@ -17,6 +17,8 @@
 //   k_row_states  : 1 lane / (row, noise stream)  rand() state + noise accumulator at row start
 //   k_encode      : 1 lane / row     BGRA -> YIQ -> chroma LP -> QAM -> pre-emphasis -> luma noise
 //   k_decode      : 1 lane / row     head switch -> Y/C split -> noise -> VHS -> TV LP -> BGRA
+// Each kernel is a caller of a body (field_part_body, row_states_body, encode_body, decode_body, bob_body) that takes its
+// parameters, tables, records, scratch and block index from outside: ntsc_mixed.hip runs the same bodies per parameter set.
 //
 // fp contract: this file MUST be compiled with -ffp-contract=off (an FMA changes the results).
 #include <hip/hip_runtime.h>
@@ -506,16 +508,15 @@ DEV void enc_step(const DevParams &P, EncState<RT> &S, unsigned xi, int W, uint3
     if (valid) cdst[(size_t)x * P.Rpad] = Y;
 }
 
-template <unsigned F, class RT>
-__global__ __launch_bounds__(64) void k_encode(DevParams P, const FieldDev *__restrict__ fields,
-                                               const uint32_t *__restrict__ rs_luma,
-                                               const int *__restrict__ n0_luma,
-                                               int *__restrict__ comp)
+// The body of k_encode for block `block` of the rows P describes (k_mixed_encode, ntsc_mixed.hip, calls it with the
+// parameters, records and scratch of one group of a mixed call: P, and with it every branch below, is wave-uniform).
+template <class O, class RT>
+DEV void encode_body(const DevParams &P, int block, const FieldDev *__restrict__ fields,
+                     const uint32_t *__restrict__ rs_luma, const int *__restrict__ n0_luma,
+                     int *__restrict__ comp, uint32_t *ring)
 {
-    using O = Opt<F>;
-    __shared__ uint32_t ring[31 * 64];
     const int lane = threadIdx.x;
-    const int rho = blockIdx.x * 64 + lane;
+    const int rho = block * 64 + lane;
     const int rc = rho < P.R ? rho : P.R - 1;
     const int f = rc / P.Lslot, k = rc - f * P.Lslot;
     const FieldDev &fd = fields[f];
@@ -575,6 +576,16 @@ __global__ __launch_bounds__(64) void k_encode(DevParams P, const FieldDev *__re
 #pragma unroll
         for (int j = 0; j < 16; j++) cur[j] = nxt[j];
     }
+}
+
+template <unsigned F, class RT>
+__global__ __launch_bounds__(64) void k_encode(DevParams P, const FieldDev *__restrict__ fields,
+                                               const uint32_t *__restrict__ rs_luma,
+                                               const int *__restrict__ n0_luma,
+                                               int *__restrict__ comp)
+{
+    __shared__ uint32_t ring[31 * 64];
+    encode_body<Opt<F>, RT>(P, (int)blockIdx.x, fields, rs_luma, n0_luma, comp, ring);
 }
 
 // =============================================================================== k_decode
@@ -965,29 +976,20 @@ DEV int dec_steady(const DevParams &P, DecState<RT> &S, const DecConst &C, const
 #ifndef NTSC_DEC_WAVES_VHS
 #define NTSC_DEC_WAVES_VHS 2
 #endif
-template <bool VHS, bool COMPOUT, unsigned F, class RT>
-__global__ __launch_bounds__(64, (VHS && COMPOUT) ? NTSC_DEC_WAVES_VHS : NTSC_DEC_WAVES) void k_decode(DevParams P, GeomDev G,
-                                               const FieldDev *__restrict__ fields,
-                                               const int *__restrict__ comp,
-                                               const uint32_t *__restrict__ rs_chroma,
-                                               const int *__restrict__ n0_u,
-                                               const int *__restrict__ n0_v,
-                                               const int *__restrict__ hs_shift,
-                                               const int *__restrict__ pn_noise,
-                                               const int *__restrict__ dropout,
-                                               int *__restrict__ tails)
+// The body of k_decode for block `block` of the rows P describes (k_mixed_decode, ntsc_mixed.hip, calls it per group, as
+// encode_body).  `tblock` / `tblocks`: the block's index in the launch and the launch's blocks -- the tails scratch is
+// the launch's, not the group's.
+template <bool VHS, bool COMPOUT, class O, class RT>
+DEV void decode_body(const DevParams &P, const GeomDev &G, int block, const FieldDev *__restrict__ fields,
+                     const int *__restrict__ comp, const uint32_t *__restrict__ rs_chroma,
+                     const int *__restrict__ n0_u, const int *__restrict__ n0_v,
+                     const int *__restrict__ hs_shift, const int *__restrict__ pn_noise,
+                     const int *__restrict__ dropout, int *__restrict__ tails,
+                     unsigned tblock, unsigned tblocks, uint32_t *ring, uint32_t *ostage)
 {
-    __shared__ uint32_t ring[31 * 64];
-    // output staging: 16 pixels per lane, row stride 20 dwords (16-byte aligned, b128 accesses)
-#ifdef NTSC_DIRECT_STORE
-    uint32_t *ostage = nullptr;
-#else
-    __shared__ __attribute__((aligned(16))) uint32_t ostage[64 * 20];
-#endif
-
     const int lane = threadIdx.x;
     // 63 output rows per wave; lane 0 recomputes the row above (halo for the vertical blend)
-    const int gidx = blockIdx.x * 63 + lane - 1;
+    const int gidx = block * 63 + lane - 1;
     const int rc = gidx < 0 ? 0 : (gidx < P.R ? gidx : P.R - 1);
     const int f = rc / P.Lslot, k = rc - f * P.Lslot;
     const FieldDev &fd = fields[f];
@@ -1001,8 +1003,8 @@ __global__ __launch_bounds__(64, (VHS && COMPOUT) ? NTSC_DEC_WAVES_VHS : NTSC_DE
     uint32_t *drow = reinterpret_cast<uint32_t *>(fd.dst + (size_t)fd.dst_ls * y);
     const int *cbase = comp + rc;
     // every lane of a wave owns a distinct column of the tails scratch (halo lanes included)
-    const size_t tcol = (size_t)blockIdx.x * 64 + lane;
-    const size_t tstride = (size_t)gridDim.x * 64;
+    const size_t tcol = (size_t)tblock * 64 + lane;
+    const size_t tstride = (size_t)tblocks * 64;
 
     DecConst C;
     C.xi = scan_phase(P, y, fd.fieldno);
@@ -1011,7 +1013,6 @@ __global__ __launch_bounds__(64, (VHS && COMPOUT) ? NTSC_DEC_WAVES_VHS : NTSC_DE
     C.k = k;
     C.lane = lane;
     C.d = VHS ? P.cdelay : 0;            // VHS chroma delay (9/12/14)
-    using O = Opt<F>;
     C.dI = O::outlp(P) == 2 ? 2 : (O::outlp(P) == 1 ? 1 : 0);
     C.dQ = O::outlp(P) == 2 ? 4 : (O::outlp(P) == 1 ? 1 : 0);
     C.SKO = C.dQ;                        // output low-pass look-ahead
@@ -1105,6 +1106,29 @@ __global__ __launch_bounds__(64, (VHS && COMPOUT) ? NTSC_DEC_WAVES_VHS : NTSC_DE
     }
 }
 
+template <bool VHS, bool COMPOUT, unsigned F, class RT>
+__global__ __launch_bounds__(64, (VHS && COMPOUT) ? NTSC_DEC_WAVES_VHS : NTSC_DEC_WAVES) void k_decode(DevParams P, GeomDev G,
+                                               const FieldDev *__restrict__ fields,
+                                               const int *__restrict__ comp,
+                                               const uint32_t *__restrict__ rs_chroma,
+                                               const int *__restrict__ n0_u,
+                                               const int *__restrict__ n0_v,
+                                               const int *__restrict__ hs_shift,
+                                               const int *__restrict__ pn_noise,
+                                               const int *__restrict__ dropout,
+                                               int *__restrict__ tails)
+{
+    __shared__ uint32_t ring[31 * 64];
+    // output staging: 16 pixels per lane, row stride 20 dwords (16-byte aligned, b128 accesses)
+#ifdef NTSC_DIRECT_STORE
+    uint32_t *ostage = nullptr;
+#else
+    __shared__ __attribute__((aligned(16))) uint32_t ostage[64 * 20];
+#endif
+    decode_body<VHS, COMPOUT, Opt<F>, RT>(P, G, (int)blockIdx.x, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise,
+                                         dropout, tails, blockIdx.x, gridDim.x, ring, ostage);
+}
+
 // =============================================================================== k_ghost
 // EXTENSION (not in the reference, default off): multipath ghosting of the composite signal,
 // out[x] = in[x] + (sum_k gain_k * in[x - delay_k]) / 256, as a pass of its own -- the form for a delay of 64 samples
@@ -1139,13 +1163,12 @@ __global__ __launch_bounds__(256) void k_ghost(DevParams P, const int *__restric
 // Line doubling done by the field loop after composite_layer (ffmpeg_ntsc.cpp:2233-2257):
 // field 1: row y (odd) is copied onto row y-1; field 0: row y+1 is copied onto odd row y while
 // y+1 < H.  One workgroup per (field slot, destination row); 16-byte coalesced copies.
-__global__ void k_bob(DevParams P, const FieldDev *__restrict__ fields)
+DEV void bob_body(const DevParams &P, const FieldDev *__restrict__ fields, int f, int pair)
 {
-    const int f = blockIdx.y;
     const FieldDev &fd = fields[f];
     if (!(fd.flags & 0x100u)) return;
     const unsigned field = fd.field & 1u;
-    const int yo = 2 * blockIdx.x + 1;            // odd row index
+    const int yo = 2 * pair + 1;                  // odd row index
     int ysrc, ydst;
     if (field) { ysrc = yo; ydst = yo - 1; if (ysrc >= P.H) return; }
     else       { ysrc = yo + 1; ydst = yo; if (ysrc >= P.H) return; }
@@ -1158,6 +1181,11 @@ __global__ void k_bob(DevParams P, const FieldDev *__restrict__ fields)
     } else {
         for (int i = threadIdx.x; i < P.W; i += blockDim.x) o[i] = s[i];
     }
+}
+
+__global__ void k_bob(DevParams P, const FieldDev *__restrict__ fields)
+{
+    bob_body(P, fields, (int)blockIdx.y, (int)blockIdx.x);
 }
 
 // =============================================================================== k_bgra_to_yuv

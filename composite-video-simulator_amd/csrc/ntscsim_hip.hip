@@ -15,10 +15,12 @@
 
 #include "ntscsim.h"
 #include "ntsc_device.hpp"
+#include "mixed_plan.hpp"      // ntscsim_mixed_fields_device(): groups, rows, block tables and rand() positions of a call (no HIP in it)
 #include "engine_host.hpp"     // what the host-frame engines decide without the GPU: row maps, copy lists, copy threads, pinned ranges
 
 // single translation unit: the kernels are compiled together with their launcher
 #include "ntsc_kernels.hip"
+#include "ntsc_mixed.hip"      // the generic chain over fields of different parameter sets (ntscsim_mixed_fields_device)
 #include "ntsc_decode_fast.hip"
 #include "ntsc_encode_fast.hip"
 #include "ntsc_pipe.hip"
@@ -90,6 +92,19 @@ struct Geometry {
     uint64_t calls[2] = {0, 0};
 };
 
+// ntscsim_mixed_fields_device(): the same tables per DRAW LAYOUT (which of the four stages draw: geometry_tables), and a
+// cos/sin table per phase-noise level -- a call holds sets that differ in both
+struct MixedGeom {
+    int W = 0, H = 0;
+    unsigned layout = 0;
+    DevBuf<uint32_t> lskip, pskip, jrow;
+    uint64_t calls[2] = {0, 0};
+};
+struct MixedPtab {
+    int K = 0;
+    DevBuf<double> t;
+};
+
 } // namespace
 
 struct SubmitEngine;      // ntscsim_submit.hip (included at the end of this file)
@@ -118,6 +133,18 @@ struct ntscsim_ctx {
     Geometry *geom_cur = nullptr;
     DevBuf<double> ptab;
     bool ptab_ready = false;
+
+    // ntscsim_mixed_fields_device(): tables keyed by what they depend on (IMMUTABLE once uploaded, like `geoms`), the
+    // call's records (fields | groups | block tables, one upload) and their pinned staging, double-buffered
+    std::vector<MixedGeom *> mixed_geoms;
+    std::vector<MixedPtab *> mixed_ptabs;
+    uint64_t mixed_table_flushes = 0;    // times the two caches started over (ntscsim_debug_mixed_tables)
+    DevBuf<uint8_t> mixed_recs;
+    unsigned char *mixed_stage[2] = {nullptr, nullptr};
+    size_t mixed_stage_cap[2] = {0, 0};
+    hipEvent_t mixed_stage_ev[2] = {nullptr, nullptr};
+    bool mixed_stage_used[2] = {false, false};
+    int mixed_stage_idx = 0;
 
     // per-batch scratch
     DevBuf<FieldDev> fields;
@@ -350,6 +377,51 @@ static uint64_t chroma_stream_offset(const ntscsim_params &p, int W, int L)
     return o;
 }
 
+// The jump tables of one geometry for the draw layout of `prm` (which stages draw: video_noise, head-switch phase noise,
+// video_chroma_noise, video_chroma_phase_noise), and the draws of one field by parity.
+static void geometry_tables(const ntscsim_params &prm, int W, int H, int variant, std::vector<uint32_t> &lskip,
+                            std::vector<uint32_t> &pskip, std::vector<uint32_t> &jrow, uint64_t calls[2])
+{
+    // chroma-noise draws per row: 2 per pixel (BGRA path) / 2 per chroma sample (YUV422P path)
+    const uint64_t cdraws = variant ? 2ull * (uint64_t)(W / 2) : 2ull * (uint64_t)W;
+    const int Lslot = (H + 1) / 2;
+    const int Lp[2] = {(H + 1) / 2, H / 2};
+    lskip.assign(2 * 31, 0u); pskip.assign(4 * 31, 0u); jrow.assign((size_t)4 * Lslot * 31, 0u);
+    const RandPoly xW = rand_poly_pow((uint64_t)W), x2W = rand_poly_pow(cdraws);
+    for (int par = 0; par < 2; par++) {
+        // draws before the 4 head-switch draws, and before the per-row phase-noise draws
+        const uint64_t off_hs = prm.video_noise != 0 ? (uint64_t)W * Lp[par] : 0;
+        const uint64_t off_pn = chroma_stream_offset(prm, W, Lp[par]) +
+                                (prm.video_chroma_noise != 0 ? cdraws * Lp[par] : 0);
+        const RandPoly a = rand_poly_pow(off_hs);
+        const RandPoly b = rand_poly_pow(off_pn);
+        std::memcpy(&lskip[par * 31], a.c, sizeof(a.c));
+        std::memcpy(&pskip[par * 31], b.c, sizeof(b.c));
+        // ... and before the per-row dropout draws, which follow the phase-noise ones (k_field_row_setup walks the two in parallel)
+        const RandPoly bd = rand_poly_pow(off_pn + (prm.video_chroma_phase_noise != 0 ? (uint64_t)Lp[par] : 0));
+        std::memcpy(&pskip[(2 + par) * 31], bd.c, sizeof(bd.c));
+        calls[par] = variant ? ntscsim_rng_calls_per_field_422(&prm, W, H, (unsigned)par)
+                             : ntscsim_rng_calls_per_field(&prm, W, H, (unsigned)par);
+        for (int s = 0; s < 2; s++) {
+            const uint64_t off = s == 0 ? 0 : chroma_stream_offset(prm, W, Lp[par]);
+            const RandPoly so = rand_poly_pow(off);
+            const uint64_t per_row = s == 0 ? (uint64_t)W : cdraws;
+            const RandPoly &step = s == 0 ? xW : x2W;
+            RandPoly cur = so;
+            uint64_t cur_e = off;
+            for (int k = 0; k < Lslot; k++) {
+                const uint64_t e = off + per_row * (uint64_t)k;      // the row's first draw
+                if (e != cur_e) {
+                    cur = (e - cur_e == per_row) ? rand_poly_mul(cur, step) : rand_poly_pow(e);
+                    cur_e = e;
+                }
+                const size_t idx = (size_t)(s * 2 + par) * Lslot + k;
+                std::memcpy(&jrow[idx * 31], cur.c, sizeof(cur.c));
+            }
+        }
+    }
+}
+
 static int build_geometry(ntscsim_ctx *c, int W, int H, const DevParams &D)
 {
     for (Geometry *e : c->geoms)
@@ -369,44 +441,8 @@ static int build_geometry(ntscsim_ctx *c, int W, int H, const DevParams &D)
     c->geom_cur = gp;
     Geometry &g = *gp;
     g.valid = false;
-    // chroma-noise draws per row: 2 per pixel (BGRA path) / 2 per chroma sample (YUV422P path)
-    const uint64_t cdraws = D.variant ? 2ull * (uint64_t)(W / 2) : 2ull * (uint64_t)W;
-    const int Lslot = (H + 1) / 2;
-    const int Lp[2] = {(H + 1) / 2, H / 2};
-    std::vector<uint32_t> lskip(2 * 31), pskip(4 * 31), jrow((size_t)4 * Lslot * 31);
-    const RandPoly xW = rand_poly_pow((uint64_t)W), x2W = rand_poly_pow(cdraws);
-    for (int par = 0; par < 2; par++) {
-        // draws before the 4 head-switch draws, and before the per-row phase-noise draws
-        const uint64_t off_hs = c->prm.video_noise != 0 ? (uint64_t)W * Lp[par] : 0;
-        const uint64_t off_pn = chroma_stream_offset(c->prm, W, Lp[par]) +
-                                (c->prm.video_chroma_noise != 0 ? cdraws * Lp[par] : 0);
-        const RandPoly a = rand_poly_pow(off_hs);
-        const RandPoly b = rand_poly_pow(off_pn);
-        std::memcpy(&lskip[par * 31], a.c, sizeof(a.c));
-        std::memcpy(&pskip[par * 31], b.c, sizeof(b.c));
-        // ... and before the per-row dropout draws, which follow the phase-noise ones (k_field_row_setup walks the two in parallel)
-        const RandPoly bd = rand_poly_pow(off_pn + (c->prm.video_chroma_phase_noise != 0 ? (uint64_t)Lp[par] : 0));
-        std::memcpy(&pskip[(2 + par) * 31], bd.c, sizeof(bd.c));
-        g.calls[par] = D.variant ? ntscsim_rng_calls_per_field_422(&c->prm, W, H, (unsigned)par)
-                                 : ntscsim_rng_calls_per_field(&c->prm, W, H, (unsigned)par);
-        for (int s = 0; s < 2; s++) {
-            const uint64_t off = s == 0 ? 0 : chroma_stream_offset(c->prm, W, Lp[par]);
-            const RandPoly so = rand_poly_pow(off);
-            const uint64_t per_row = s == 0 ? (uint64_t)W : cdraws;
-            const RandPoly &step = s == 0 ? xW : x2W;
-            RandPoly cur = so;
-            uint64_t cur_e = off;
-            for (int k = 0; k < Lslot; k++) {
-                const uint64_t e = off + per_row * (uint64_t)k;      // the row's first draw
-                if (e != cur_e) {
-                    cur = (e - cur_e == per_row) ? rand_poly_mul(cur, step) : rand_poly_pow(e);
-                    cur_e = e;
-                }
-                const size_t idx = (size_t)(s * 2 + par) * Lslot + k;
-                std::memcpy(&jrow[idx * 31], cur.c, sizeof(cur.c));
-            }
-        }
-    }
+    std::vector<uint32_t> lskip, pskip, jrow;
+    geometry_tables(c->prm, W, H, D.variant, lskip, pskip, jrow, g.calls);
     HIPCHK(c, g.lskip.ensure(lskip.size()));
     HIPCHK(c, g.pskip.ensure(pskip.size()));
     HIPCHK(c, g.jrow.ensure(jrow.size()));
@@ -486,6 +522,14 @@ extern "C" void ntscsim_destroy(ntscsim_ctx *c)
         delete e;
     }
     c->geoms.clear();
+    for (MixedGeom *e : c->mixed_geoms) { e->lskip.release(); e->pskip.release(); e->jrow.release(); delete e; }
+    for (MixedPtab *e : c->mixed_ptabs) { e->t.release(); delete e; }
+    c->mixed_geoms.clear(); c->mixed_ptabs.clear();
+    c->mixed_recs.release();
+    for (int i = 0; i < 2; i++) {
+        if (c->mixed_stage[i]) (void)hipHostFree(c->mixed_stage[i]);
+        if (c->mixed_stage_ev[i]) (void)hipEventDestroy(c->mixed_stage_ev[i]);
+    }
     c->ptab.release(); c->fields.release(); c->hs_shift.release(); c->pn_noise.release();
     c->dropout.release(); c->n0_luma.release(); c->n0_u.release(); c->n0_v.release();
     c->comp.release(); c->comp_ghost.release(); c->comp_vcr.release(); c->tails.release(); c->fields422.release(); c->recs422.release(); c->out422.release(); c->yuv.release(); c->scale.release(); c->scratch422.release(); c->halo422.release(); c->rs_luma.release(); c->rs_chroma.release();
@@ -733,6 +777,50 @@ static void speculate_setup(ntscsim_ctx *c, hipStream_t st)
     sp.launched++;
 }
 
+// What every fields call asks of one descriptor.
+static int check_field_desc(const ntscsim_field_desc &d, int W)
+{
+    if (!d.src_dev || !d.dst_dev) return NTSCSIM_E_ARG;
+    if (d.src_linesize < 4 * W || d.dst_linesize < 4 * W) return NTSCSIM_E_SIZE;  // :1580-1581
+    if ((d.src_linesize & 3) || (d.dst_linesize & 3)) return NTSCSIM_E_SIZE;
+    if (((uintptr_t)d.src_dev & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_ARG;
+    if (d.field > 1) return NTSCSIM_E_ARG;
+    return NTSCSIM_OK;
+}
+
+// The device record of a descriptor whose first draw is at rand() position `pos`.
+static void fill_field_record(ntscsim_ctx *c, const ntscsim_field_desc &d, uint64_t pos, FieldDev &o)
+{
+    o.src = (const uint8_t *)d.src_dev;
+    o.dst = (uint8_t *)d.dst_dev;
+    o.src_ls = d.src_linesize; o.dst_ls = d.dst_linesize;
+    o.field = d.field; o.flags = d.flags; o.fieldno = d.fieldno; o._pad = 0;
+    const RandState s = ctx_state_at(c, pos);
+    std::memcpy(o.rng, s.w, sizeof(s.w));
+    for (int j = 31; j < 61; j++) o.rng[j] = o.rng[j - 31] + o.rng[j - 3];
+}
+
+// Descriptors of one batch run concurrently: two of them may share a destination frame only
+// as its two fields (different parity, no bob) -- anything else is a write-write race.
+template <class DescAt>
+static int check_shared_destinations(ntscsim_ctx *c, int n, DescAt desc_at)
+{
+    if (n <= 1) return NTSCSIM_OK;
+    std::vector<std::pair<uintptr_t, unsigned>> keys((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const ntscsim_field_desc &d = desc_at(i);
+        keys[(size_t)i] = {(uintptr_t)d.dst_dev, (d.flags & NTSCSIM_DESC_BOB) ? 2u : (d.field & 1u)};
+    }
+    std::sort(keys.begin(), keys.end());
+    for (int i = 1; i < n; i++)
+        if (keys[(size_t)i].first == keys[(size_t)i - 1].first &&
+            (keys[(size_t)i].second == keys[(size_t)i - 1].second || keys[(size_t)i].second == 2u)) {
+            c->err = "descriptors of one batch share a destination frame (same field parity, or bob)";
+            return NTSCSIM_E_ARG;
+        }
+    return NTSCSIM_OK;
+}
+
 // ---- step 1: descriptors -> device records.  The rand() window of every field is computed on
 // the host (one 31x31 multiply-accumulate per consecutive field).
 static int prepare_records(ntscsim_ctx *c, const ntscsim_field_desc *descs, int n, int W, int H,
@@ -760,41 +848,18 @@ static int prepare_records(ntscsim_ctx *c, const ntscsim_field_desc *descs, int 
     uint64_t pos = c->rng_pos;
     for (int i = 0; i < n; i++) {
         const ntscsim_field_desc &d = descs[i];
-        if (!d.src_dev || !d.dst_dev) return NTSCSIM_E_ARG;
-        if (d.src_linesize < 4 * W || d.dst_linesize < 4 * W) return NTSCSIM_E_SIZE;  // :1580-1581
-        if ((d.src_linesize & 3) || (d.dst_linesize & 3)) return NTSCSIM_E_SIZE;
-        if (((uintptr_t)d.src_dev & 3) || ((uintptr_t)d.dst_dev & 3)) return NTSCSIM_E_ARG;
-        if (d.field > 1) return NTSCSIM_E_ARG;
+        rc = check_field_desc(d, W);
+        if (rc != NTSCSIM_OK) return rc;
         if (d.rng_pos != NTSCSIM_RNG_AUTO) pos = d.rng_pos;
-        FieldDev &o = fh[i];
-        o.src = (const uint8_t *)d.src_dev;
-        o.dst = (uint8_t *)d.dst_dev;
-        o.src_ls = d.src_linesize; o.dst_ls = d.dst_linesize;
-        o.field = d.field; o.flags = d.flags; o.fieldno = d.fieldno; o._pad = 0;
-        const RandState s = ctx_state_at(c, pos);
-        std::memcpy(o.rng, s.w, sizeof(s.w));
-        for (int j = 31; j < 61; j++) o.rng[j] = o.rng[j - 31] + o.rng[j - 3];
+        fill_field_record(c, d, pos, fh[i]);
         pos += c->geom_cur->calls[d.field & 1];
         al_src = al_src && !(((uintptr_t)d.src_dev | (uintptr_t)d.src_linesize) & 15);
         al_dst = al_dst && !(((uintptr_t)d.dst_dev | (uintptr_t)d.dst_linesize) & 15);
         any_bob = any_bob || (d.flags & NTSCSIM_DESC_BOB);
     }
     if (any_bob && n > 65535) return NTSCSIM_E_SIZE;      // k_bob: one grid row per field
-    // Descriptors of one batch run concurrently: two of them may share a destination frame only
-    // as its two fields (different parity, no bob) -- anything else is a write-write race.
-    if (n > 1) {
-        std::vector<std::pair<uintptr_t, unsigned>> keys((size_t)n);
-        for (int i = 0; i < n; i++)
-            keys[(size_t)i] = {(uintptr_t)descs[i].dst_dev,
-                               (descs[i].flags & NTSCSIM_DESC_BOB) ? 2u : (descs[i].field & 1u)};
-        std::sort(keys.begin(), keys.end());
-        for (int i = 1; i < n; i++)
-            if (keys[(size_t)i].first == keys[(size_t)i - 1].first &&
-                (keys[(size_t)i].second == keys[(size_t)i - 1].second || keys[(size_t)i].second == 2u)) {
-                c->err = "descriptors of one batch share a destination frame (same field parity, or bob)";
-                return NTSCSIM_E_ARG;
-            }
-    }
+    rc = check_shared_destinations(c, n, [&](int i) -> const ntscsim_field_desc & { return descs[i]; });
+    if (rc != NTSCSIM_OK) return rc;
     rng_end = pos;          // committed by the caller once the launch has succeeded
     D.src_al16 = al_src; D.dst_al16 = al_dst;
     return NTSCSIM_OK;
@@ -1255,6 +1320,310 @@ extern "C" int ntscsim_fields_device(ntscsim_ctx *c, const ntscsim_field_desc *d
     if (prof) c->ev_live.push_back(evs);
     c->rng_pos = rng_end;
     return NTSCSIM_OK;
+}
+
+// ---- fields that name different parameter sets, one launch of each kernel (csrc/mixed_plan.hpp, csrc/ntsc_mixed.hip)
+static unsigned mixed_draw_layout(const ntscsim_params &p)
+{
+    return (p.video_noise != 0 ? 1u : 0u) | ((p.vhs_head_switching && p.vhs_head_switching_phase_noise != 0) ? 2u : 0u) |
+           (p.video_chroma_noise != 0 ? 4u : 0u) | (p.video_chroma_phase_noise != 0 ? 8u : 0u);
+}
+
+static MixedGeom *mixed_geometry_cached(const ntscsim_ctx *c, unsigned layout, int W, int H)
+{
+    for (MixedGeom *e : c->mixed_geoms)
+        if (e->W == W && e->H == H && e->layout == layout) return e;
+    return nullptr;
+}
+
+static const MixedPtab *mixed_ptab_cached(const ntscsim_ctx *c, int K)
+{
+    for (const MixedPtab *e : c->mixed_ptabs)
+        if (e->K == K) return e;
+    return nullptr;
+}
+
+static int mixed_geometry(ntscsim_ctx *c, const ntscsim_params &prm, int W, int H, MixedGeom *&out)
+{
+    const unsigned layout = mixed_draw_layout(prm);
+    if ((out = mixed_geometry_cached(c, layout, W, H)) != nullptr) return NTSCSIM_OK;
+    std::vector<uint32_t> lskip, pskip, jrow;
+    MixedGeom *g = new (std::nothrow) MixedGeom();
+    if (!g) return NTSCSIM_E_NOMEM;
+    geometry_tables(prm, W, H, 0, lskip, pskip, jrow, g->calls);
+    if (g->lskip.ensure(lskip.size()) != hipSuccess || g->pskip.ensure(pskip.size()) != hipSuccess ||
+        g->jrow.ensure(jrow.size()) != hipSuccess ||
+        upload_table(g->lskip.p, lskip.data(), lskip.size() * 4) != hipSuccess ||
+        upload_table(g->pskip.p, pskip.data(), pskip.size() * 4) != hipSuccess ||
+        upload_table(g->jrow.p, jrow.data(), jrow.size() * 4) != hipSuccess) {
+        g->lskip.release(); g->pskip.release(); g->jrow.release();
+        delete g;
+        c->err = "ntscsim_mixed_fields_device: jump tables: device allocation / upload failed";
+        return NTSCSIM_E_HIP;
+    }
+    g->W = W; g->H = H; g->layout = layout;
+    c->mixed_geoms.push_back(g);
+    out = g;
+    return NTSCSIM_OK;
+}
+
+static int mixed_ptab(ntscsim_ctx *c, int K, const double *&out)
+{
+    if (const MixedPtab *hit = mixed_ptab_cached(c, K)) { out = hit->t.p; return NTSCSIM_OK; }
+    std::vector<double> t((size_t)(2 * K + 1) * 2);
+    for (int n = -K; n <= K; n++) {
+        const double pi = ((double)n * M_PI) / 100;        // ffmpeg_ntsc.cpp:1746, as build_ptab
+        t[(size_t)(n + K) * 2] = std::cos(pi);
+        t[(size_t)(n + K) * 2 + 1] = std::sin(pi);
+    }
+    MixedPtab *e = new (std::nothrow) MixedPtab();
+    if (!e) return NTSCSIM_E_NOMEM;
+    if (e->t.ensure(t.size()) != hipSuccess || upload_table(e->t.p, t.data(), t.size() * sizeof(double)) != hipSuccess) {
+        e->t.release();
+        delete e;
+        c->err = "ntscsim_mixed_fields_device: phase-noise table: device allocation / upload failed";
+        return NTSCSIM_E_HIP;
+    }
+    e->K = K;
+    c->mixed_ptabs.push_back(e);
+    out = e->t.p;
+    return NTSCSIM_OK;
+}
+
+#ifndef NTSC_MIXED_TABLES_MAX
+#define NTSC_MIXED_TABLES_MAX 256     /* cached table sets of either kind before the cache starts over */
+#endif
+
+static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n_sets,
+                               const ntscsim_mixed_field_desc *descs, int n, int W, int H, void *hip_stream)
+{
+    if (!c || n < 0 || n_sets < 0) return NTSCSIM_E_ARG;
+    if (n == 0) return NTSCSIM_OK;
+    if (!descs) return NTSCSIM_E_ARG;
+    if (W < 16 || H < 2 || W > 16384 || H > 16384) return NTSCSIM_E_SIZE;      // as prepare_records
+    const int Lslot = (H + 1) / 2;
+    if (c->pipe_fault && *c->pipe_fault) {      // raised by an earlier launch of this ctx, as in ntscsim_fields_device
+        c->err = "k_field_pipe: hand-off timed out in workgroup " + std::to_string(*c->pipe_fault - 1u);
+        *c->pipe_fault = 0u;
+        return NTSCSIM_E_HIP;
+    }
+
+    // ---- the descriptors, and which sets they name.  The plan sees the NAMED sets only, numbered 0 .. in ascending order
+    // (`used`): nothing here is sized by n_sets.
+    std::vector<int32_t> used((size_t)n);
+    bool al_src = true, al_dst = true, any_bob = false;
+    for (int i = 0; i < n; i++) {
+        const ntscsim_field_desc &d = descs[i].d;
+        const int32_t set = descs[i].set;
+        if (set < -1 || set >= n_sets || (set >= 0 && !sets)) return NTSCSIM_E_ARG;
+        const int drc = check_field_desc(d, W);
+        if (drc != NTSCSIM_OK) return drc;
+        used[(size_t)i] = set;
+        al_src = al_src && !(((uintptr_t)d.src_dev | (uintptr_t)d.src_linesize) & 15);
+        al_dst = al_dst && !(((uintptr_t)d.dst_dev | (uintptr_t)d.dst_linesize) & 15);
+        any_bob = any_bob || (d.flags & NTSCSIM_DESC_BOB);
+    }
+    std::sort(used.begin(), used.end());
+    used.erase(std::unique(used.begin(), used.end()), used.end());
+    const int n_used = (int)used.size();
+    std::vector<mixed::Field> pf((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int32_t id = (int32_t)(std::lower_bound(used.begin(), used.end(), descs[i].set) - used.begin());
+        pf[(size_t)i] = mixed::Field{id, descs[i].d.field, descs[i].d.rng_pos};
+    }
+    auto params_of = [&](int32_t id) -> const ntscsim_params & { return used[(size_t)id] < 0 ? c->prm : sets[used[(size_t)id]]; };
+    // ---- the named sets: refused as ntscsim_create() refuses them; sets nobody names are not looked at
+    std::vector<mixed::SetInfo> info((size_t)n_used + 1);
+    for (int s = 0; s < n_used; s++) {
+        const ntscsim_params &prm = params_of(s);
+        if (prm.struct_size != sizeof(ntscsim_params)) return NTSCSIM_E_ARG;
+        const int vrc = ntscsim_params_validate(&prm);
+        if (vrc != NTSCSIM_OK) return vrc;
+        if (prm.ghost_taps > 0) {
+            c->err = "ntscsim_mixed_fields_device: a named set has ghost_taps > 0 (the ghosting extension stays with the single-set calls)";
+            return NTSCSIM_E_PARAM;
+        }
+        mixed::SetInfo &si = info[(size_t)(s + 1)];
+        for (unsigned par = 0; par < 2; par++) si.calls[par] = ntscsim_rng_calls_per_field(&prm, W, H, par);
+        si.cls = !prm.emulating_vhs ? mixed::CLS_TV : (prm.vhs_svideo_out ? mixed::CLS_VCR_SVIDEO : mixed::CLS_VCR_COMP);
+    }
+    // (across the whole call, whatever sets the descriptors name)
+    int rc = check_shared_destinations(c, n, [&](int i) -> const ntscsim_field_desc & { return descs[i].d; });
+    if (rc != NTSCSIM_OK) return rc;
+    mixed::Plan plan;
+    rc = mixed::make_plan(pf.data(), n, n_used, info.data(), Lslot, W, any_bob, c->rng_pos, plan);
+    if (rc != mixed::PLAN_OK) return rc == mixed::PLAN_E_SIZE ? NTSCSIM_E_SIZE : NTSCSIM_E_ARG;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const size_t ng = plan.groups.size();
+    // ---- tables: one set per draw layout, one cos/sin table per phase-noise level.  A call whose tables are all cached
+    // touches neither cache nor device; one that would take a cache past its bound with the entries it MISSES drains the
+    // device and starts both over before it takes any (entries are immutable while anything queued may read them).
+    {
+        unsigned new_layouts = 0;                    // bit per draw layout (16 of them) this geometry lacks
+        std::vector<int> new_levels;
+        for (size_t g = 0; g < ng; g++) {
+            const ntscsim_params &prm = params_of(plan.groups[g].set);
+            const unsigned layout = mixed_draw_layout(prm);
+            if (!mixed_geometry_cached(c, layout, W, H)) new_layouts |= 1u << layout;
+            const int K = prm.video_chroma_phase_noise;
+            if (K != 0 && !mixed_ptab_cached(c, K)) new_levels.push_back(K);
+        }
+        std::sort(new_levels.begin(), new_levels.end());
+        new_levels.erase(std::unique(new_levels.begin(), new_levels.end()), new_levels.end());
+        const size_t add_geoms = (size_t)__builtin_popcount(new_layouts), add_ptabs = new_levels.size();
+        if ((add_geoms && c->mixed_geoms.size() + add_geoms > NTSC_MIXED_TABLES_MAX) ||
+            (add_ptabs && c->mixed_ptabs.size() + add_ptabs > NTSC_MIXED_TABLES_MAX)) {
+            HIPCHK(c, hipDeviceSynchronize());
+            for (MixedGeom *e : c->mixed_geoms) { e->lskip.release(); e->pskip.release(); e->jrow.release(); delete e; }
+            for (MixedPtab *e : c->mixed_ptabs) { e->t.release(); delete e; }
+            c->mixed_geoms.clear(); c->mixed_ptabs.clear();
+            c->mixed_table_flushes++;
+        }
+    }
+    // ---- records: [n FieldDev, sorted by group][ng MixedGroup][n group of a field][encoder blocks][decoder blocks x 3]
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t off_groups = up16((size_t)n * sizeof(FieldDev));
+    const size_t off_gof = up16(off_groups + ng * sizeof(MixedGroup));
+    const size_t off_enc = up16(off_gof + (size_t)n * sizeof(int32_t));
+    size_t off_dec[mixed::N_CLS + 1];
+    off_dec[0] = up16(off_enc + plan.enc_tab.size() * sizeof(MixedBlock));
+    for (int k = 0; k < mixed::N_CLS; k++) off_dec[k + 1] = up16(off_dec[k] + plan.dec_tab[k].size() * sizeof(MixedBlock));
+    const size_t bytes = off_dec[mixed::N_CLS];
+    static_assert(sizeof(MixedBlock) == sizeof(mixed::BlockRef), "block table layout");
+
+    const int si = c->mixed_stage_idx;
+    c->mixed_stage_idx ^= 1;
+    if (!c->mixed_stage_ev[si]) HIPCHK(c, hipEventCreateWithFlags(&c->mixed_stage_ev[si], hipEventDisableTiming));
+    if (c->mixed_stage_used[si]) HIPCHK(c, hipEventSynchronize(c->mixed_stage_ev[si]));
+    if (c->mixed_stage_cap[si] < bytes) {
+        if (c->mixed_stage[si]) (void)hipHostFree(c->mixed_stage[si]);
+        c->mixed_stage[si] = nullptr; c->mixed_stage_cap[si] = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        HIPCHK(c, hipHostMalloc((void **)&c->mixed_stage[si], want, hipHostMallocDefault));
+        c->mixed_stage_cap[si] = want;
+    }
+    unsigned char *host = c->mixed_stage[si];
+    std::memset(host, 0, bytes);
+    FieldDev *fh = reinterpret_cast<FieldDev *>(host);
+    for (int i = 0; i < n; i++)
+        fill_field_record(c, descs[i].d, plan.rng_start[(size_t)i], fh[plan.slot[(size_t)i]]);
+    MixedGroup *gh = reinterpret_cast<MixedGroup *>(host + off_groups);
+    bool any_cls[mixed::N_CLS] = {false, false, false};
+    for (size_t g = 0; g < ng; g++) {
+        const mixed::Group &pg = plan.groups[g];
+        const ntscsim_params &prm = params_of(pg.set);
+        MixedGroup &o = gh[g];
+        fill_dev_params(prm, o.P);
+        if (c->warm_override[0] > 0) o.P.warm_luma = c->warm_override[0];
+        if (c->warm_override[1] > 0) o.P.warm_chroma = c->warm_override[1];
+        o.P.W = W; o.P.H = H; o.P.Lslot = Lslot;
+        o.P.nfields = pg.nf; o.P.R = pg.R; o.P.Rpad = plan.Rpad;
+        o.P.src_al16 = al_src; o.P.dst_al16 = al_dst;
+        MixedGeom *mg = nullptr;
+        rc = mixed_geometry(c, prm, W, H, mg);
+        if (rc != NTSCSIM_OK) return rc;
+        o.G.lskip = mg->lskip.p; o.G.pskip = mg->pskip.p; o.G.jrow = mg->jrow.p;
+        o.G.ptab = nullptr;
+        if (o.P.pnoise_k) { rc = mixed_ptab(c, o.P.pnoise_k, o.G.ptab); if (rc != NTSCSIM_OK) return rc; }
+        o.base = pg.base; o.field0 = pg.field0;
+        any_cls[pg.cls] = true;
+    }
+    std::memcpy(host + off_gof, plan.group_of.data(), (size_t)n * sizeof(int32_t));
+    std::memcpy(host + off_enc, plan.enc_tab.data(), plan.enc_tab.size() * sizeof(MixedBlock));
+    size_t dec_max = 0;
+    for (int k = 0; k < mixed::N_CLS; k++) {
+        if (!plan.dec_tab[k].empty())
+            std::memcpy(host + off_dec[k], plan.dec_tab[k].data(), plan.dec_tab[k].size() * sizeof(MixedBlock));
+        dec_max = std::max(dec_max, plan.dec_tab[k].size());
+    }
+    // ---- scratch for the padded scanline space (all of it: which tables a call reads is per group)
+    const size_t R = (size_t)plan.R, Rpad = (size_t)plan.Rpad;
+    HIPCHK(c, c->mixed_recs.ensure(bytes));
+    HIPCHK(c, c->comp.ensure(Rpad * W));
+    HIPCHK(c, c->hs_shift.ensure(R)); HIPCHK(c, c->pn_noise.ensure(R)); HIPCHK(c, c->dropout.ensure(R));
+    HIPCHK(c, c->rs_luma.ensure(31 * Rpad)); HIPCHK(c, c->n0_luma.ensure(Rpad));
+    HIPCHK(c, c->rs_chroma.ensure(31 * Rpad)); HIPCHK(c, c->n0_u.ensure(Rpad)); HIPCHK(c, c->n0_v.ensure(Rpad));
+    HIPCHK(c, c->tails.ensure((size_t)32 * 64 * dec_max));
+    // (an early setup kernel of the synchronous calls may still be writing these tables on its own stream: launch_setup)
+    if (c->spec.armed) (void)hipStreamWaitEvent(st, c->ev_spec, 0);
+    c->spec.armed = c->spec.dry = false;
+    c->spec.have_last = false;
+
+    // profiling as in ntscsim_fields_device: start | setup done | encode done | decode done | end
+    ntscsim_ctx::EvSet evs;
+    const bool prof = c->profiling;
+    if (prof) {
+        rc = take_events(c, evs);
+        if (rc != NTSCSIM_OK) return rc;
+        HIPCHK(c, hipEventRecord(evs.e[0], st));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->mixed_recs.p, host, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->mixed_stage_ev[si], st));
+    c->mixed_stage_used[si] = true;
+    const FieldDev *fields_dev = reinterpret_cast<const FieldDev *>(c->mixed_recs.p);
+    const MixedGroup *groups_dev = reinterpret_cast<const MixedGroup *>(c->mixed_recs.p + off_groups);
+    const int32_t *gof_dev = reinterpret_cast<const int32_t *>(c->mixed_recs.p + off_gof);
+    const MixedBlock *enc_dev = reinterpret_cast<const MixedBlock *>(c->mixed_recs.p + off_enc);
+
+    c->kernels.clear();
+    c->dec_lds = 0;
+    const bool fast = c->mode != NTSCSIM_MODE_EXACT;      // FAST32, and FLOAT's fallback: float filter states
+    const int nfs = 3 * n, nrs = (int)plan.enc_tab.size();
+    note_kernel(c, "k_mixed_setup");
+    hipLaunchKernelGGL(k_mixed_setup, dim3((unsigned)(nfs + 2 * nrs)), dim3(64), 0, st, groups_dev, gof_dev, enc_dev, fields_dev,
+                       c->hs_shift.p, c->pn_noise.p, c->dropout.p, c->rs_luma.p, c->n0_luma.p, c->rs_chroma.p, c->n0_u.p,
+                       c->n0_v.p, nfs, nrs);
+    if (prof) HIPCHK(c, hipEventRecord(evs.e[1], st));
+    // (the names carry the filter-state type, as the single-set kernels' do: the float forms run the arithmetic of
+    //  k_encode<1u,float> / k_decode<...,1u,float>, whose bytes tests/test_mixed_fields_gpu.py holds them to)
+    const std::string rt = fast ? "float" : "double";
+    note_kernel(c, ("k_mixed_encode<" + rt + ">").c_str());
+    if (fast) hipLaunchKernelGGL((k_mixed_encode<float>), dim3((unsigned)nrs), dim3(64), 0, st, groups_dev, enc_dev, fields_dev,
+                                 c->rs_luma.p, c->n0_luma.p, c->comp.p);
+    else hipLaunchKernelGGL((k_mixed_encode<double>), dim3((unsigned)nrs), dim3(64), 0, st, groups_dev, enc_dev, fields_dev,
+                            c->rs_luma.p, c->n0_luma.p, c->comp.p);
+    if (prof) HIPCHK(c, hipEventRecord(evs.e[2], st));
+#define NTSC_LAUNCH_MIXED_DECODE(CLS, VHS, CO, RT)                                                                      \
+    do { note_kernel(c, ("k_mixed_decode<" #VHS "," #CO "," + rt + ">").c_str());                                        \
+    hipLaunchKernelGGL((k_mixed_decode<VHS, CO, RT>), dim3((unsigned)plan.dec_tab[CLS].size()), dim3(64), 0, st, groups_dev, \
+                       reinterpret_cast<const MixedBlock *>(c->mixed_recs.p + off_dec[CLS]), fields_dev, c->comp.p,       \
+                       c->rs_chroma.p, c->n0_u.p, c->n0_v.p, c->hs_shift.p, c->pn_noise.p, c->dropout.p, c->tails.p); } while (0)
+    if (any_cls[mixed::CLS_TV]) { if (fast) NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_TV, false, false, float); else NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_TV, false, false, double); }
+    if (any_cls[mixed::CLS_VCR_COMP]) { if (fast) NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_COMP, true, true, float); else NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_COMP, true, true, double); }
+    if (any_cls[mixed::CLS_VCR_SVIDEO]) { if (fast) NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_SVIDEO, true, false, float); else NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_SVIDEO, true, false, double); }
+#undef NTSC_LAUNCH_MIXED_DECODE
+    if (prof) HIPCHK(c, hipEventRecord(evs.e[3], st));
+    if (any_bob) {
+        note_kernel(c, "k_mixed_bob");
+        hipLaunchKernelGGL(k_mixed_bob, dim3((H + 1) / 2, n), dim3(256), 0, st, groups_dev, fields_dev);
+    }
+    if (prof) HIPCHK(c, hipEventRecord(evs.e[4], st));
+    HIPCHK(c, hipGetLastError());
+    if (prof) c->ev_live.push_back(evs);
+    c->last_n = 0;                  // (ntscsim_debug_read_composite reads a single-set plane)
+    c->rng_pos = plan.rng_end;
+    return NTSCSIM_OK;
+}
+
+extern "C" int ntscsim_mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n_sets,
+                                           const ntscsim_mixed_field_desc *descs, int n, int W, int H, void *hip_stream)
+{
+    // (the plan and the call's host tables are std::vectors of the call's size: no exception crosses the C ABI)
+    try {
+        return mixed_fields_device(c, sets, n_sets, descs, n, W, H, hip_stream);
+    } catch (const std::bad_alloc &) {
+        return NTSCSIM_E_NOMEM;
+    }
+}
+
+extern "C" void ntscsim_debug_mixed_tables(const ntscsim_ctx *c, uint64_t out[3])
+{
+    if (!out) return;
+    out[0] = c ? c->mixed_geoms.size() : 0;
+    out[1] = c ? c->mixed_ptabs.size() : 0;
+    out[2] = c ? c->mixed_table_flushes : 0;
 }
 
 // ---- prepared batches: validate + derive + upload once, launch many times ------------------

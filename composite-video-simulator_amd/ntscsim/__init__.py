@@ -12,7 +12,7 @@ except ImportError:
     pass
 
 from . import _capi
-from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc, FieldDesc,
+from ._capi import (DESC_BOB, DESC_INTERLACED, DESC_TFF, RNG_AUTO, Field422Desc, FieldDesc, MixedFieldDesc,
                     NtscsimError, Out422Desc, YuvDesc, ScaleDesc, HostSource, Params, lib, make_params,
                     make_params_to_composite)
 
@@ -264,6 +264,49 @@ class FieldSimulator:
         self.run_descs(descs, src.shape[2], src.shape[1])
         return descs
 
+    # ---- the same with parameters per field (ntscsim_mixed_fields_device) -------------------
+    @staticmethod
+    def build_sets(sets):
+        """sets: list of Params or flag lists -> ntscsim_params array (None for an empty list)."""
+        if not sets:
+            return None
+        arr = (Params * len(sets))()
+        for i, s in enumerate(sets):
+            arr[i] = s if isinstance(s, Params) else make_params(s)
+        return arr
+
+    def build_mixed_descs(self, set_of, src, dst, jobs, bob=False, interlaced=0, tff=0, rng_pos=None):
+        """As build_descs(); set_of[i] is the set of job i (-1: this simulator's own parameters).  bob, interlaced and
+        tff may be one value for the call or a list with one value per job."""
+        jobs = list(jobs)
+        assert len(set_of) == len(jobs)
+
+        def per_job(v, i):
+            return v[i] if isinstance(v, (list, tuple)) else v
+        arr = (MixedFieldDesc * len(jobs))()
+        for i, job in enumerate(jobs):
+            one = self.build_descs(src, dst, [job], bob=per_job(bob, i), interlaced=per_job(interlaced, i),
+                                   tff=per_job(tff, i), rng_pos=None if rng_pos is None else [rng_pos[i]])
+            arr[i].d = one[0]
+            arr[i].set = int(set_of[i])
+        return arr
+
+    def run_mixed_descs(self, sets, descs, width, height, stream=None):
+        """Enqueue; does not synchronise.  sets: what build_sets() returns (or a list it accepts)."""
+        if isinstance(sets, (list, tuple)):
+            sets = self.build_sets(sets)
+        if stream is None:
+            stream = self._torch_stream()
+        rc = self._lib.ntscsim_mixed_fields_device(self._h, sets, 0 if sets is None else len(sets), descs, len(descs),
+                                                   int(width), int(height), C.c_void_p(stream))
+        self._chk(rc, "ntscsim_mixed_fields_device")
+
+    def mixed_fields(self, sets, set_of, src, dst, jobs, **kw):
+        """fields() with the parameters of sets[set_of[i]] for job i: one launch of each kernel for all of them."""
+        descs = self.build_mixed_descs(set_of, src, dst, jobs, **kw)
+        self.run_mixed_descs(sets, descs, src.shape[2], src.shape[1])
+        return descs
+
     # ---- 8-bit YUV422P sibling (ffmpeg_to_composite) ---------------------------------------
     def build_descs422(self, jobs):
         """jobs: list of dicts with keys dst (3 CUDA uint8 tensors [H, ls]), optional src (3
@@ -364,6 +407,12 @@ class FieldSimulator:
                   "ntscsim_get_timings_ms")
         return {"setup": out[0], "encode": out[1], "decode": out[2], "total": out[3],
                 "calls": n.value}
+
+    def debug_mixed_tables(self):
+        """[jump-table sets cached, cos/sin tables cached, times the caches were dropped] of mixed_fields()"""
+        a = (C.c_uint64 * 3)()
+        self._lib.ntscsim_debug_mixed_tables(self._h, a)
+        return [int(x) for x in a]
 
     def debug_force_generic(self, on=True):
         self._lib.ntscsim_debug_force_generic(self._h, 1 if on else 0)

@@ -25,11 +25,11 @@ EXPORTS = (
     "ntscsim_params_validate", "ntscsim_rng_calls_per_field", "ntscsim_rng_draw",
     "ntscsim_create", "ntscsim_destroy", "ntscsim_strerror", "ntscsim_last_error",
     "ntscsim_set_mode", "ntscsim_get_rng_pos", "ntscsim_set_rng_pos", "ntscsim_field", "ntscsim_frames_host",
-    "ntscsim_fields_device",
+    "ntscsim_fields_device", "ntscsim_mixed_fields_device",
     "ntscsim_batch_create", "ntscsim_batch_run", "ntscsim_batch_destroy",
     "ntscsim_sync", "ntscsim_set_profiling", "ntscsim_get_timings_ms", "ntscsim_set_launch_form",
     "ntscsim_debug_read_composite", "ntscsim_debug_set_warmup",
-    "ntscsim_debug_force_generic", "ntscsim_debug_no_fast_decode", "ntscsim_debug_last_kernels", "ntscsim_debug_last_decoder_lds", "ntscsim_debug_fast_plane_ok", "ntscsim_debug_field_stats",
+    "ntscsim_debug_force_generic", "ntscsim_debug_no_fast_decode", "ntscsim_debug_last_kernels", "ntscsim_debug_last_decoder_lds", "ntscsim_debug_fast_plane_ok", "ntscsim_debug_field_stats", "ntscsim_debug_mixed_tables",
     "ntscsim_params_init_to_composite", "ntscsim_params_parse_argv_to_composite",
     "ntscsim_fields422_device", "ntscsim_output422_device", "ntscsim_bgra_to_yuv_device", "ntscsim_rng_calls_per_field_422",
     "ntscsim_scale_to_bgra_device", "ntscsim_frames_host_scaled",
@@ -166,6 +166,15 @@ class FieldDesc(C.Structure):
         ("flags", C.c_uint32),
         ("fieldno", C.c_uint64),
         ("rng_pos", C.c_uint64),
+    ]
+
+
+class MixedFieldDesc(C.Structure):
+    """struct ntscsim_mixed_field_desc"""
+    _fields_ = [
+        ("d", FieldDesc),
+        ("set", C.c_int32),
+        ("_pad", C.c_int32),
     ]
 
 
@@ -561,6 +570,9 @@ def lib():
     L.ntscsim_fields_device.argtypes = [C.c_void_p, C.POINTER(FieldDesc), C.c_int, C.c_int,
                                         C.c_int, C.c_void_p]
     L.ntscsim_fields_device.restype = C.c_int
+    L.ntscsim_mixed_fields_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(MixedFieldDesc), C.c_int,
+                                              C.c_int, C.c_int, C.c_void_p]
+    L.ntscsim_mixed_fields_device.restype = C.c_int
     L.ntscsim_batch_create.argtypes = [C.c_void_p, C.POINTER(FieldDesc), C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]
     L.ntscsim_batch_create.restype = C.c_int
@@ -615,6 +627,8 @@ def lib():
     L.ntscsim_debug_fast_plane_ok.restype = C.c_int
     L.ntscsim_debug_field_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.ntscsim_debug_field_stats.restype = None
+    L.ntscsim_debug_mixed_tables.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.ntscsim_debug_mixed_tables.restype = None
     L.ntscsim_batch422_create.argtypes = [C.c_void_p, C.POINTER(Field422Desc), C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_void_p)]
     L.ntscsim_batch422_create.restype = C.c_int

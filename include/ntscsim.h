@@ -459,6 +459,47 @@ int ntscsim_fields_device(ntscsim_ctx *ctx, const ntscsim_field_desc *descs, int
                           int width, int height, void *hip_stream);
 
 /*
+ * Fields of one geometry, EACH WITH ITS OWN PARAMETERS: a fields call whose descriptors name a set of `sets` (a library
+ * of stills, an augmentation run that gives every clip its own noise levels, tape speed, sharpening, head-switch point,
+ * S-Video or composite out, pre-emphasis).  The call equals, in destination bytes and in the ctx's rand() position
+ * afterwards, this sequence for i = 0 .. n-1 in order: a ctx made with ntscsim_create(&sets[descs[i].set]) has its
+ * rand() position set to where descriptor i starts and runs ntscsim_fields_device(&descs[i].d, 1, width, height) -- but
+ * the fields run side by side in ONE launch of each kernel however many sets there are (the decoder: one launch per
+ * decoder class present -- no VCR, VCR with composite out, VCR with S-Video out), nothing waits for the device, and the
+ * ctx's own parameters are neither read (except through set == -1) nor written.
+ * rand() positions: NTSCSIM_RNG_AUTO continues after the previous descriptor in the call's order, which advanced by
+ * ntscsim_rng_calls_per_field() of ITS set; descs[0] continues from the ctx's position; the position moves only when the
+ * call succeeds, to the end of the last descriptor.
+ * Destinations: shared across the whole call exactly as in ntscsim_fields_device() -- two descriptors may share a frame
+ * only as its two fields, neither with NTSCSIM_DESC_BOB; the two may name different sets.
+ * Modes: NTSCSIM_MODE_EXACT is bit-identical to the reference; NTSCSIM_MODE_FAST32 runs the same kernels with float
+ * filter states; NTSCSIM_MODE_FLOAT runs the FAST32 forms here.  The call runs the generic kernels (every switch read at
+ * run time), not the hand-tuned ones of the presets: a long run of fields on ONE preset is faster through
+ * ntscsim_fields_device().  ntscsim_debug_set_warmup is honoured; ntscsim_debug_last_kernels names what
+ * ran: k_mixed_setup, k_mixed_encode<RT>, k_mixed_decode<VHS,COMPOUT,RT> per class, k_mixed_bob.
+ * ntscsim_set_profiling / ntscsim_get_timings_ms cover the call as they cover ntscsim_fields_device() (setup | encode |
+ * decode, the decoder launches of all classes together).  The first call that names a draw layout (which of the noise
+ * stages draw) or a chroma phase-noise level the ctx has not seen builds and uploads that table, synchronously; later
+ * calls reuse it (ntscsim_debug_mixed_tables).
+ * Refused before anything is enqueued or the position moves -- NTSCSIM_E_ARG / NTSCSIM_E_SIZE: everything
+ * ntscsim_fields_device() refuses, its size limits taken for the call's scanline space (every set's fields start at a
+ * multiple of 64 rows); a `set` outside -1 .. n_sets-1; n_sets < 0; a NULL `sets` that should hold something; a set some
+ * descriptor names with a wrong struct_size.  NTSCSIM_E_PARAM: a set some descriptor names that
+ * ntscsim_params_validate() refuses, or one with ghost_taps > 0 -- the ghosting extension is a pass over the whole
+ * composite plane with call-wide taps and stays with the single-set calls.  Sets that no descriptor names are not looked
+ * at.  n == 0 succeeds and does nothing.  `sets` and `descs` are host memory, consumed by the call.
+ */
+typedef struct ntscsim_mixed_field_desc {
+    ntscsim_field_desc d;      /* as in ntscsim_fields_device                                     */
+    int32_t            set;    /* index into `sets`; -1: the parameters the ctx was created with  */
+    int32_t            _pad;
+} ntscsim_mixed_field_desc;
+
+int ntscsim_mixed_fields_device(ntscsim_ctx *ctx, const ntscsim_params *sets, int n_sets,
+                                const ntscsim_mixed_field_desc *descs, int n,
+                                int width, int height, void *hip_stream);
+
+/*
  * Prepared batch: the same work as ntscsim_fields_device(), split into "validate the descriptors,
  * derive each field's rand() window, upload the records" (once) and "enqueue the kernel chain"
  * (any number of times, e.g. a clip that is re-rendered, or a ring of frame buffers that is
@@ -733,6 +774,12 @@ int ntscsim_debug_fast_plane_ok(int n_fields, int width, int height, int head_sw
  * DESTINATION frame was written where it is (no download), [3] calls (of either tool's synchronous entry point) that
  * found their setup kernel already run, launched ahead of time by the call before. */
 void ntscsim_debug_field_stats(const ntscsim_ctx *ctx, uint64_t out[4]);
+
+/* Test hook: the table caches of ntscsim_mixed_fields_device() -- [0] jump-table sets cached (one per geometry and draw
+ * layout), [1] cos/sin tables cached (one per video_chroma_phase_noise level), [2] times both caches were dropped, which
+ * waits for the device: only a call that MISSES more entries than a cache has room for (256 each) does that.  A call whose
+ * tables are all cached touches neither.  Touches no device. */
+void ntscsim_debug_mixed_tables(const ntscsim_ctx *ctx, uint64_t out[3]);
 
 /* ---- the raw-composite decoder: ffmpeg_raw28ntsc.cpp ---------------
  * The tool reads 8-bit composite video sampled at 8 x fsc (28.636 MHz, e.g. a cxadc capture) and

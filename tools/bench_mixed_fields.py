@@ -1,0 +1,234 @@
+#!/usr/bin/env python3
+"""Speed of video fields WITH PARAMETERS PER FIELD in one call (ntscsim_mixed_fields_device), 720x486, resident in HBM.
+
+In the same run:
+  (a)  the case the call exists for: --sets sets (noise levels, tape speed, sharpening, head-switch point, S-Video or
+       composite out, pre-emphasis drawn from a fixed seed), one frame = two fields each, through ONE mixed call (device
+       events, median of --reps after --warmup) -- against the same fields as one ntscsim_fields_device call per set on
+       one context per set, each on its context's own stream, which is what a caller had to do before (wall clock from
+       the first call to the device's last kernel; the contexts are made and warmed outside the clock)
+  (b)  the price of the generic kernels: 2 * --sets fields all on ONE set (-vhs) through the mixed call, through
+       ntscsim_fields_device with the generic kernels forced (ntscsim_debug_force_generic), and through
+       ntscsim_fields_device as it runs by itself (the hand-tuned kernels); device events, medians
+
+  (c), (d)  --compare-tree PARENT: what the change did to code it touched or sits beside, against a built tree of the
+       parent commit, each figure taken in a fresh process, the two trees alternating, --rounds times: (d)
+       ntscsim_fields_device with the generic kernels forced on the 2 * --sets -vhs fields of (b) -- the kernels whose
+       bodies the mixed call shares (this tool with --generic-only --tree T, device events, median of --reps) -- and (c)
+       the headline, `python bench.py --gpus 1 --steps 20 --warmup 5` run in each tree.  Written under
+       "parent_against_this" of the --out file.
+
+Every descriptor carries an explicit rand() position, so all forms compute the same fields.  Verified before a number is
+printed: (a)'s two forms and (b)'s three forms wrote the same bytes.
+
+    python tools/bench_mixed_fields.py [--sets 300] [--reps 5] [--warmup 2] [--compare-tree PARENT [--rounds 2]]
+                                       [--out profiles/mixed_fields.json]"""
+import argparse
+import json
+import os
+import random
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _tree_arg():
+    """--tree T (with --generic-only): import the package of that tree instead of this one"""
+    if "--tree" in sys.argv[:-1]:
+        return os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
+    return ROOT
+
+
+sys.path.insert(0, os.path.join(_tree_arg(), "composite-video-simulator_amd"))
+
+W, H = 720, 486
+
+
+def make_sets(n, make_params):
+    rnd = random.Random(300)
+    sets = []
+    for i in range(n):
+        flags = []
+        if i % 4:
+            flags += ["-vhs", "-vhs-speed", ("sp", "lp", "ep")[rnd.randrange(3)]]
+            if i % 4 == 3:
+                flags += ["-vhs-svideo", "1"]
+        if i % 5 == 0:
+            flags += [("-comp-catv", "-comp-catv2", "-comp-catv3")[rnd.randrange(3)]]
+        flags += ["-noise", str(rnd.randrange(0, 12)), "-chroma-noise", str(rnd.randrange(0, 24)),
+                  "-chroma-phase-noise", str(rnd.randrange(0, 8))]
+        sets.append(make_params(flags, vhs_out_sharpen=0.25 * rnd.randrange(0, 12),
+                                vhs_head_switching_point=1.0 - (4.0 + rnd.random()) / 262.5))
+    return sets
+
+
+def compare_trees(a, parent):
+    """(c) and (d): fresh processes, parent and this tree alternating"""
+    def last_json(cmd, cwd):
+        out = subprocess.run(cmd, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, check=True, timeout=600).stdout
+        return json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+
+    trees = (("parent", parent), ("this", ROOT))
+    r = {"rounds": a.rounds, "d_generic_single_set_ms": {"parent": [], "this": []}, "c_bench_py_fields_per_s": {"parent": [], "this": []}}
+    for _ in range(a.rounds):
+        for name, tree in trees:
+            j = last_json([sys.executable, os.path.abspath(__file__), "--generic-only", "--sets", str(a.sets), "--reps", str(a.reps),
+                           "--warmup", str(a.warmup), "--tree", tree], ROOT)
+            r["d_generic_single_set_ms"][name].append(j["ms"])
+    for _ in range(a.rounds):
+        for name, tree in trees:
+            j = last_json([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], tree)
+            r["c_bench_py_fields_per_s"][name].append(j["value"])
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", type=int, default=300)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--generic-only", action="store_true", help="(d) alone: one JSON line, old interface only")
+    ap.add_argument("--tree", default=None, help="with --generic-only: the built tree whose package is measured")
+    ap.add_argument("--compare-tree", default=None, help="a built tree of the parent commit: adds (c) and (d)")
+    ap.add_argument("--rounds", type=int, default=2)
+    a = ap.parse_args()
+
+    import torch
+    import ntscsim
+    if not torch.cuda.is_available():
+        sys.exit("bench_mixed_fields.py needs a GPU")
+    stream = torch.cuda.Stream()
+    n_sets, n = a.sets, 2 * a.sets
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(20)
+    src = torch.randint(0, 256, (8, H, W, 4), dtype=torch.uint8, device="cuda", generator=gen)
+    dst = [torch.zeros((n_sets, H, W, 4), dtype=torch.uint8, device="cuda") for _ in range(3)]
+    # field k: frame k // 2 of the destination, parity (k & 1) ^ 1, fieldno k, rand() position k * 2^21 (past any field's draws)
+    jobs = [(k // 2 % 8, k // 2, (k & 1) ^ 1, k) for k in range(n)]
+    pos = [k << 21 for k in range(n)]
+    result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": a.warmup, "width": W, "height": H,
+              "fields": n, "sets": n_sets}
+
+    def events(fn):
+        ms = []
+        for i in range(a.warmup + a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            if i >= a.warmup:
+                ms.append(e0.elapsed_time(e1))
+        return {"ms": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+    def wall(fn):
+        ms = []
+        for i in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i >= a.warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        return {"ms": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+    vhs = ntscsim.make_params(["-vhs"])
+    one = ntscsim.FieldSimulator(params=vhs)
+    one_descs = one.build_descs(src, dst[1], jobs, rng_pos=pos)
+
+    def run_generic():
+        one.debug_force_generic(True)
+        one.run_descs(one_descs, W, H, stream=stream.cuda_stream)
+        one.debug_force_generic(False)
+
+    if a.generic_only:
+        r = events(run_generic)
+        r["kernels"] = one.last_kernels()
+        one.close()
+        print(json.dumps(r))
+        return
+
+    # ---- (a)
+    sets = make_sets(n_sets, ntscsim.make_params)
+    sim = ntscsim.FieldSimulator()
+    set_arr = sim.build_sets(sets)
+    set_of = [k // 2 for k in range(n)]
+    mixed_descs = sim.build_mixed_descs(set_of, src, dst[0], jobs, rng_pos=pos)
+
+    def run_mixed():
+        sim.run_mixed_descs(set_arr, mixed_descs, W, H, stream=stream.cuda_stream)
+
+    case = events(run_mixed)
+    case["kernels"] = sim.last_kernels()
+    t0 = time.perf_counter()
+    run_mixed()
+    case["host_ms_of_the_call"] = (time.perf_counter() - t0) * 1e3
+    stream.synchronize()
+    result["a_mixed_call"] = case
+    per = [ntscsim.FieldSimulator(params=p) for p in sets]
+    per_descs = [c.build_descs(src, dst[1], jobs[2 * s:2 * s + 2], rng_pos=pos[2 * s:2 * s + 2]) for s, c in enumerate(per)]
+
+    def run_per_set():
+        for c, d in zip(per, per_descs):
+            c.run_descs(d, W, H, stream=0)              # (0: the context's own stream)
+
+    result["a_one_call_per_set"] = wall(run_per_set)
+    forms = {}
+    for c in per:
+        k = ";".join(c.last_kernels())
+        forms[k] = forms.get(k, 0) + 1
+    result["a_one_call_per_set"]["kernel_forms"] = forms
+    torch.cuda.synchronize()
+    if not torch.equal(dst[0], dst[1]):
+        sys.exit("(a): the mixed call differs from one call per set (%d bytes)" % int((dst[0] != dst[1]).sum()))
+    result["a_per_set_over_mixed"] = result["a_one_call_per_set"]["ms"] / case["ms"]
+    result["a_fields_per_s"] = n / (case["ms"] * 1e-3)
+    for c in per:
+        c.close()
+    print("a", json.dumps(result), flush=True)
+
+    # ---- (b)
+    for t in dst:
+        t.zero_()
+    uni_descs = sim.build_mixed_descs([0] * n, src, dst[0], jobs, rng_pos=pos)
+    uni_sets = sim.build_sets([vhs])
+
+    def run_uniform_mixed():
+        sim.run_mixed_descs(uni_sets, uni_descs, W, H, stream=stream.cuda_stream)
+
+    fast_descs = one.build_descs(src, dst[2], jobs, rng_pos=pos)
+
+    def run_fast():
+        one.run_descs(fast_descs, W, H, stream=stream.cuda_stream)
+
+    b = {"set": "-vhs"}
+    b["mixed_call"] = events(run_uniform_mixed)
+    b["mixed_call"]["kernels"] = sim.last_kernels()
+    b["generic_single_set"] = events(run_generic)
+    b["generic_single_set"]["kernels"] = one.last_kernels()
+    b["hand_tuned_single_set"] = events(run_fast)
+    b["hand_tuned_single_set"]["kernels"] = one.last_kernels()
+    torch.cuda.synchronize()
+    if not torch.equal(dst[0], dst[1]) or not torch.equal(dst[0], dst[2]):
+        sys.exit("(b): the three forms differ")
+    b["mixed_over_generic"] = b["mixed_call"]["ms"] / b["generic_single_set"]["ms"]
+    b["mixed_over_hand_tuned"] = b["mixed_call"]["ms"] / b["hand_tuned_single_set"]["ms"]
+    result["b_all_fields_on_one_set"] = b
+    result["verified"] = "(a) mixed call == one call per set; (b) mixed == generic == hand-tuned; whole destination buffers"
+    sim.close()
+    one.close()
+    if a.compare_tree:
+        result["parent_against_this"] = compare_trees(a, os.path.abspath(a.compare_tree))
+    print(json.dumps(result))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

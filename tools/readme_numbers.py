@@ -212,7 +212,25 @@ def cass_mixed_row(path="profiles/cass_mixed_tracks.json"):
             "`profiles/cass_mixed_tracks.json`, DESIGN.md §7m")
 
 
-for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row, cass_mixed_row):
+def mixed_fields_row(path="profiles/mixed_fields.json"):
+    """The row of fields with parameters per field, from tools/bench_mixed_fields.py's file ("unmeasured" without one)."""
+    what = ("fields with parameters per field in one call (`ntscsim_mixed_fields_device`), resident in HBM (`tools/bench_mixed_fields.py`); (a) one frame "
+            "per set, against the same fields as one `ntscsim_fields_device` call per set on one context per set, wall clock; (b) all fields on one set "
+            "(`-vhs`) through the mixed call, through `ntscsim_fields_device` with the generic kernels forced and with its hand-tuned kernels; all in the same run")
+    try:
+        j = json.load(open(path))
+    except OSError:
+        return (what, "**unmeasured**: no GPU run of `tools/bench_mixed_fields.py` was taken on this build", "DESIGN.md §3c")
+    a, p, b = j["a_mixed_call"], j["a_one_call_per_set"], j["b_all_fields_on_one_set"]
+    return (what,
+            "(a) %d fields over %d sets: **%.2f ms** (%.0f fields/s); one call per set %.1f ms, so the one call is worth **%.1f ×**; (b) %d fields on one set: mixed "
+            "call %.3f ms, generic single-set kernels %.3f ms (%.3f ×), hand-tuned %.3f ms (the mixed call takes %.2f × that).  Whole destination buffers equal "
+            "in (a) and in (b)" % (j["fields"], j["sets"], a["ms"], j["a_fields_per_s"], p["ms"], j["a_per_set_over_mixed"], j["fields"], b["mixed_call"]["ms"],
+                                 b["generic_single_set"]["ms"], b["mixed_over_generic"], b["hand_tuned_single_set"]["ms"], b["mixed_over_hand_tuned"]),
+            "`profiles/mixed_fields.json`, DESIGN.md §3c")
+
+
+for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row, cass_mixed_row, mixed_fields_row):
     try:
         rows.append(row())
     except Exception:
