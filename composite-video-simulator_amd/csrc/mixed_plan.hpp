@@ -13,7 +13,8 @@
 //               decoder has one table per decoder class (no VCR | VCR with composite out | VCR with S-Video out):
 //               a class is a template instantiation, hence a launch of its own over its groups' blocks only.
 //   4. rand()   every descriptor's start position in the CALLER's order: an explicit position stands, NTSCSIM_RNG_AUTO
-//               continues behind the previous descriptor, which advanced by the draws of ITS set and parity.
+//               continues behind the previous descriptor, which advanced by the draws of ITS set and parity -- or by
+//               nothing, if it is marked `nodraw` (ntscsim_mixed_fields422_device(): NTSCSIM_422_NOCOMP).
 //
 // All sizes are computed in 64 bits and checked against the limits of the single-set call (prepare_records(),
 // ntscsim_hip.hip) before anything is narrowed.
@@ -37,6 +38,7 @@ struct Field {
     int32_t set;          // -1 .. n_sets - 1
     uint32_t parity;      // 0 | 1
     uint64_t rng_pos;     // or RNG_AUTO
+    uint32_t nodraw = 0;  // 1: the field draws nothing, the position stays where it starts (default: it draws)
 };
 
 // what it needs to know of one set; entry 0 is set -1 (the ctx's own parameters), entry s + 1 is sets[s].  Entries of
@@ -73,9 +75,11 @@ struct Plan {
     int32_t Rpad = 0;
 };
 
-// (set, parity) are taken as validated: set in -1 .. n_sets - 1, parity 0 | 1.
+// (set, parity) are taken as validated: set in -1 .. n_sets - 1, parity 0 | 1.  any_bob: some kernel of the caller has
+// one grid plane per field.  plane_limit: the caller keeps a composite plane of Rpad * W elements (the YUV422P tool
+// has none, its call switches the limit off).
 inline int make_plan(const Field *f, int n, int n_sets, const SetInfo *info, int Lslot, int W, bool any_bob,
-                     uint64_t start_pos, Plan &p)
+                     uint64_t start_pos, Plan &p, bool plane_limit = true)
 {
     p = Plan();
     p.rng_end = start_pos;
@@ -128,7 +132,7 @@ inline int make_plan(const Field *f, int n, int n_sets, const SetInfo *info, int
         row = ((row + R + 63) / 64) * 64;
     }
     const long long Rpad = (((long long)p.R + 63) / 64) * 64 + 64;
-    if (Rpad * (long long)W > MAX_PLANE) return PLAN_E_SIZE;
+    if (plane_limit && Rpad * (long long)W > MAX_PLANE) return PLAN_E_SIZE;
     p.Rpad = (int32_t)Rpad;
 
     // ---- 3. block -> (group, block within the group)
@@ -146,7 +150,7 @@ inline int make_plan(const Field *f, int n, int n_sets, const SetInfo *info, int
     for (int i = 0; i < n; i++) {
         if (f[i].rng_pos != RNG_AUTO) pos = f[i].rng_pos;
         p.rng_start[(size_t)i] = pos;
-        pos += info[(size_t)(f[i].set + 1)].calls[f[i].parity & 1u];
+        if (!f[i].nodraw) pos += info[(size_t)(f[i].set + 1)].calls[f[i].parity & 1u];
     }
     p.rng_end = pos;
     return PLAN_OK;

@@ -19,6 +19,9 @@
 // filter's own pre-charge value.  The reference's three writes past its chroma scratch array
 // (:529-532) are dropped, as in the oracle.
 //
+// The bodies of k422_process, k422_halo, k422_render and k422_bkey are device functions that take their parameters, tables,
+// records, scratch and block indices from outside: ntsc422_mixed.hip runs the same bodies per parameter set.
+//
 // Included by ntscsim_hip.hip after ntsc_kernels.hip (shares OnePole/Lp3/LaneRand/helpers).
 #pragma clang fp contract(off)
 
@@ -53,12 +56,19 @@ struct Scratch422 {
 // differed from the same fields in launches of 8).  So the rows in question are copied aside by k422_halo BEFORE the
 // process kernel starts, and the halo lane reads the copy (64-byte aligned, as long as the frame's linesize + the two
 // bytes the separator reads past the row :496).
-DEV void halo_redirect(const Scratch422 &Sc, int lane, uint8_t *&fy, uint8_t *&fu, uint8_t *&fv)
+// (blk: the workgroup within its launch's row space -- its group, in a call over several parameter sets, whose first
+//  workgroup has no row above as workgroup 0 of a single-set launch has none; lblk: the workgroup of the LAUNCH, which
+//  owns the copy's slot as it owns the scratch slots)
+DEV void halo_redirect(const Scratch422 &Sc, int lane, unsigned blk, unsigned lblk, uint8_t *&fy, uint8_t *&fu, uint8_t *&fv)
 {
-    if (lane == 0 && blockIdx.x > 0 && Sc.halo) {
-        uint8_t *b = Sc.halo + (size_t)blockIdx.x * 3u * Sc.halo_pitch;
+    if (lane == 0 && blk > 0 && Sc.halo) {
+        uint8_t *b = Sc.halo + (size_t)lblk * 3u * Sc.halo_pitch;
         fy = b; fu = b + Sc.halo_pitch; fv = b + 2u * (size_t)Sc.halo_pitch;
     }
+}
+DEV void halo_redirect(const Scratch422 &Sc, int lane, uint8_t *&fy, uint8_t *&fu, uint8_t *&fv)
+{
+    halo_redirect(Sc, lane, blockIdx.x, blockIdx.x, fy, fu, fv);
 }
 
 // scanline phase of the 8-bit tool (:449-460 / :508-522): phase 0 ignores the offset, PAL differs
@@ -77,9 +87,9 @@ DEV unsigned scan_phase422(const DevParams &P, unsigned y, uint64_t fieldno)
 // ------------------------------------------------------------------------------ halo rows (see halo_redirect)
 // block b copies the input of the row above workgroup b + 1 (row rc = 63 (b + 1) - 1 of the batch's row space): linesize
 // bytes of each plane, + 2 of the luma plane (the separator's bytes past the row), never past the end of a plane
-__global__ __launch_bounds__(256) void k422_halo(DevParams P, const Field422Dev *__restrict__ fields, Scratch422 Sc)
+// (wg: the workgroup within the row space of P / fields, lwg: the workgroup of the launch, whose slot the copy takes)
+DEV void halo422_body(const DevParams &P, const Field422Dev *__restrict__ fields, const Scratch422 &Sc, int wg, unsigned lwg)
 {
-    const int wg = (int)blockIdx.x + 1;
     const int rc = wg * 63 - 1;
     if (rc >= P.R) return;
     const int f = rc / P.Lslot, k = rc - f * P.Lslot;
@@ -87,7 +97,7 @@ __global__ __launch_bounds__(256) void k422_halo(DevParams P, const Field422Dev 
     const unsigned field = fd.field & 1u;
     const bool rowok = (int)(field + 2u * k) < P.H;
     const unsigned y = rowok ? field + 2u * (unsigned)k : field;       // (the process kernels' row of that lane)
-    uint8_t *out = Sc.halo + (size_t)wg * 3u * Sc.halo_pitch;
+    uint8_t *out = Sc.halo + (size_t)lwg * 3u * Sc.halo_pitch;
     for (int pl = 0; pl < 3; pl++) {
         const size_t ls = (size_t)fd.dst_ls[pl];
         const uint8_t *src = fd.dst[pl] + ls * y;
@@ -99,14 +109,16 @@ __global__ __launch_bounds__(256) void k422_halo(DevParams P, const Field422Dev 
         for (size_t t = threadIdx.x; t < n; t += blockDim.x) dst[t] = src[t];
     }
 }
+__global__ __launch_bounds__(256) void k422_halo(DevParams P, const Field422Dev *__restrict__ fields, Scratch422 Sc)
+{
+    halo422_body(P, fields, Sc, (int)blockIdx.x + 1, blockIdx.x + 1u);
+}
 
 // ------------------------------------------------------------------------------ render_field
 // One thread per output byte of the field's rows (all three planes); pure integer lerp between
 // two source rows (:1076-1128).
-__global__ void k422_render(DevParams P, const Field422Dev *__restrict__ fields)
+DEV void render422_body(const DevParams &P, const Field422Dev &fd)
 {
-    const int f = blockIdx.z;
-    const Field422Dev &fd = fields[f];
     if (!fd.src[0]) return;
     const unsigned field = fd.field & 1u;
     const int k = blockIdx.y;
@@ -152,13 +164,15 @@ __global__ void k422_render(DevParams P, const Field422Dev *__restrict__ fields)
         }
     }
 }
+__global__ void k422_render(DevParams P, const Field422Dev *__restrict__ fields)
+{
+    render422_body(P, fields[blockIdx.z]);
+}
 
 // ------------------------------------------------------------------------------ black key
 // black_key_feedback :954-999: one thread per chroma sample (pixel pair).
-__global__ void k422_bkey(DevParams P, const Field422Dev *__restrict__ fields, int level)
+DEV void bkey422_body(const DevParams &P, const Field422Dev &fd, int level)
 {
-    const int f = blockIdx.z;
-    const Field422Dev &fd = fields[f];
     if (!fd.flt[0]) return;
     const unsigned y = (fd.field & 1u) + 2u * blockIdx.y;
     if ((int)y >= P.H) return;
@@ -187,6 +201,10 @@ __global__ void k422_bkey(DevParams P, const Field422Dev *__restrict__ fields, i
             dY[2 * c + 1] = (uint8_t)yy; fY[2 * c + 1] = (uint8_t)yy;
         }
     }
+}
+__global__ void k422_bkey(DevParams P, const Field422Dev *__restrict__ fields, int level)
+{
+    bkey422_body(P, fields[blockIdx.z], level);
 }
 
 // ------------------------------------------------------------------------------ output frame
@@ -356,9 +374,13 @@ struct LumaPost422 {
 };
 
 // composite_video_yuv_to_ntsc :434-477 (one chroma sample modulates two luma samples)
+// POST: the luma post-stages ride in this sweep; their state is copied into registers for the sweep, as demodulate422
+// copies its own (a struct reached through a pointer would live in scratch memory)
+template <bool POST>
 DEV void modulate422(const DevParams &P, const Row422 &R, int W, unsigned xi, int amp, bool nocolor,
-                     LumaPost422 *post = nullptr)
+                     const LumaPost422 &post_in)
 {
+    LumaPost422 post = post_in;
     const int W2 = W / 2;
     Reader422 ru, rv;
     ru.begin(R.U, W2); rv.begin(R.V, W2);
@@ -377,15 +399,15 @@ DEV void modulate422(const DevParams &P, const Row422 &R, int W, unsigned xi, in
         int chroma = ((s & 1u) ? cv : cu) * amp;
         if (s & 2u) chroma = -chroma;
         int yv = clampu8(in + chroma / 50);
-        if (post) {
-            if (post->pre_on) {
+        if (POST) {
+            if (post.pre_on) {
                 double sd = yv;
-                sd += post->pre.hp(sd, P.a_pre) * P.pre_gain;
+                sd += post.pre.hp(sd, P.a_pre) * P.pre_gain;
                 yv = clampu8((int)sd);
             }
-            if (post->noise_on) {
-                yv = clampu8(yv + post->noise);
-                post->noise = sdiv2(post->noise + (int)umod31(post->rng.next(post->ring, post->lane), P.m_noise) - P.noise_k);
+            if (post.noise_on) {
+                yv = clampu8(yv + post.noise);
+                post.noise = sdiv2(post.noise + (int)umod31(post.rng.next(post.ring, post.lane), P.m_noise) - P.noise_k);
             }
         }
         oy.put(x, yv);
@@ -477,24 +499,18 @@ DEV void demodulate422(const DevParams &P, const Row422 &R, int W, unsigned xi, 
     oy.finish(W); ou.finish(W2); ov.finish(W2);
 }
 
-__global__ __launch_bounds__(64) void k422_process(DevParams P, GeomDev G,
-                                                   const Field422Dev *__restrict__ fields,
-                                                   Scratch422 Sc,
-                                                   const uint32_t *__restrict__ rs_luma,
-                                                   const int *__restrict__ n0_luma,
-                                                   const uint32_t *__restrict__ rs_chroma,
-                                                   const int *__restrict__ n0_u,
-                                                   const int *__restrict__ n0_v,
-                                                   const int *__restrict__ hs_shift,
-                                                   const int *__restrict__ pn_noise,
-                                                   const int *__restrict__ dropout,
-                                                   double a_hp_i, double a_hp_q, double a_sh_c,
-                                                   double sharpen_c, int yc_recombine,
-                                                   int after_yc_sep)
+// The twelve-sweep body of one workgroup.  P, G, fields and the row-indexed tables are those of the workgroup's row space
+// (a whole single-set launch, or one group of ntscsim_mixed_fields422_device(), ntsc422_mixed.hip); blk is the workgroup
+// within that space, lblk the workgroup of the launch, which owns the scratch slots and the halo copy.
+DEV void process422_body(const DevParams &P, const GeomDev &G, const Field422Dev *__restrict__ fields, const Scratch422 &Sc,
+                         const uint32_t *__restrict__ rs_luma, const int *__restrict__ n0_luma,
+                         const uint32_t *__restrict__ rs_chroma, const int *__restrict__ n0_u, const int *__restrict__ n0_v,
+                         const int *__restrict__ hs_shift, const int *__restrict__ pn_noise, const int *__restrict__ dropout,
+                         const double a_hp_i, const double a_hp_q, const double a_sh_c, const double sharpen_c,
+                         const int yc_recombine, const int after_yc_sep, uint32_t *ring, const unsigned blk, const unsigned lblk)
 {
-    __shared__ uint32_t ring[31 * 64];
     const int lane = threadIdx.x;
-    const int gidx = blockIdx.x * 63 + lane - 1;          // lane 0 = halo (row above)
+    const int gidx = (int)blk * 63 + lane - 1;            // lane 0 = halo (row above)
     const int rc = gidx < 0 ? 0 : (gidx < P.R ? gidx : P.R - 1);
     const int f = rc / P.Lslot, k = rc - f * P.Lslot;
     const Field422Dev &fd = fields[f];
@@ -504,14 +520,14 @@ __global__ __launch_bounds__(64) void k422_process(DevParams P, GeomDev G,
     const unsigned y = rowok ? field + 2u * (unsigned)k : field;
     const unsigned xi = scan_phase422(P, y, fd.fieldno);
     const int W = P.W, W2 = P.W / 2;
-    const size_t slot = (size_t)blockIdx.x * 64 + lane;
+    const size_t slot = (size_t)lblk * 64 + lane;
     Row422 R;
     R.Y.p = Sc.Y + slot; R.T.p = Sc.T + slot; R.U.p = Sc.U + slot; R.V.p = Sc.V + slot;
     R.Y.S = R.T.S = R.U.S = R.V.S = Sc.S;
     uint8_t *fy = fd.dst[0] + (size_t)fd.dst_ls[0] * y;
     uint8_t *fu = fd.dst[1] + (size_t)fd.dst_ls[1] * y;
     uint8_t *fv = fd.dst[2] + (size_t)fd.dst_ls[2] * y;
-    halo_redirect(Sc, lane, fy, fu, fv);
+    halo_redirect(Sc, lane, blk, lblk, fy, fu, fv);
     // the two bytes the reference's Y/C separator reads past the row (:496): inside the luma plane
     // they are the caller's own bytes, outside it (last row, linesize < W + 2) the defined value 16
     int oob0 = 16, oob1 = 16;
@@ -559,7 +575,7 @@ __global__ __launch_bounds__(64) void k422_process(DevParams P, GeomDev G,
         lp_.pre_on = P.pre_on != 0; lp_.noise_on = P.noise_k != 0;
         lp_.pre.p = 16; lp_.noise = 0; lp_.ring = ring; lp_.lane = lane;
         if (lp_.noise_on) { lp_.rng.init(ring, rs_luma + rc, P.Rpad, lane); lp_.noise = n0_luma[rc]; }
-        modulate422(P, R, W, xi, P.amp, P.nocolor != 0, &lp_);
+        modulate422<true>(P, R, W, xi, P.amp, P.nocolor != 0, lp_);
     }
     // ---- head switching :669-732 (displaced copy, fill value 16)
     if (P.hs) {
@@ -672,7 +688,7 @@ __global__ __launch_bounds__(64) void k422_process(DevParams P, GeomDev G,
             ou.finish(W2); ov.finish(W2);
         }
         if (!P.svideo) {                                     // :926-929
-            modulate422(P, R, W, xi, P.amp, P.nocolor != 0);
+            modulate422<false>(P, R, W, xi, P.amp, P.nocolor != 0, LumaPost422());
             demodulate422<false>(P, R, W, xi, P.m_amp, after_yc_sep != 0, oob0, oob1, ChromaPost422());
         }
     }
@@ -683,7 +699,7 @@ __global__ __launch_bounds__(64) void k422_process(DevParams P, GeomDev G,
     }
     // ---- extra Y/C recombine passes :943-946
     for (int i = 0; i < yc_recombine; i++) {
-        modulate422(P, R, W, xi, P.amp, P.nocolor != 0);
+        modulate422<false>(P, R, W, xi, P.amp, P.nocolor != 0, LumaPost422());
         demodulate422<false>(P, R, W, xi, P.m_amp, after_yc_sep != 0, oob0, oob1, ChromaPost422());
     }
     // ---- output chroma low-pass :948-951 (full if "out", else lite if "lite")
@@ -733,6 +749,26 @@ __global__ __launch_bounds__(64) void k422_process(DevParams P, GeomDev G,
         }
         for (; c0 < W2; c0++) { fu[c0] = (uint8_t)R.U.byte_at(c0); fv[c0] = (uint8_t)R.V.byte_at(c0); }
     }
+}
+
+__global__ __launch_bounds__(64) void k422_process(DevParams P, GeomDev G,
+                                                   const Field422Dev *__restrict__ fields,
+                                                   Scratch422 Sc,
+                                                   const uint32_t *__restrict__ rs_luma,
+                                                   const int *__restrict__ n0_luma,
+                                                   const uint32_t *__restrict__ rs_chroma,
+                                                   const int *__restrict__ n0_u,
+                                                   const int *__restrict__ n0_v,
+                                                   const int *__restrict__ hs_shift,
+                                                   const int *__restrict__ pn_noise,
+                                                   const int *__restrict__ dropout,
+                                                   double a_hp_i, double a_hp_q, double a_sh_c,
+                                                   double sharpen_c, int yc_recombine,
+                                                   int after_yc_sep)
+{
+    __shared__ uint32_t ring[31 * 64];
+    process422_body(P, G, fields, Sc, rs_luma, n0_luma, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, a_hp_i, a_hp_q,
+                    a_sh_c, sharpen_c, yc_recombine, after_yc_sep, ring, blockIdx.x, blockIdx.x);
 }
 
 } // namespace ntscsim

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ntscsim.h"
@@ -25,6 +26,7 @@
 #include "ntsc_encode_fast.hip"
 #include "ntsc_pipe.hip"
 #include "ntsc422_kernels.hip"
+#include "ntsc422_mixed.hip"   // the twelve-sweep YUV422P chain over fields of different parameter sets (ntscsim_mixed_fields422_device)
 #include "ntsc422_fused.hip"
 #include "ntsc_scale.hip"
 #include "ntsc_float.hpp"       // NTSCSIM_MODE_FLOAT: its kernels are a translation unit of their own
@@ -95,7 +97,7 @@ struct Geometry {
 // ntscsim_mixed_fields_device(): the same tables per DRAW LAYOUT (which of the four stages draw: geometry_tables), and a
 // cos/sin table per phase-noise level -- a call holds sets that differ in both
 struct MixedGeom {
-    int W = 0, H = 0;
+    int W = 0, H = 0, variant = 0;       // variant: 0 the BGRA tool, 1 the YUV422P tool (chroma draws per row differ)
     unsigned layout = 0;
     DevBuf<uint32_t> lskip, pskip, jrow;
     uint64_t calls[2] = {0, 0};
@@ -1329,10 +1331,10 @@ static unsigned mixed_draw_layout(const ntscsim_params &p)
            (p.video_chroma_noise != 0 ? 4u : 0u) | (p.video_chroma_phase_noise != 0 ? 8u : 0u);
 }
 
-static MixedGeom *mixed_geometry_cached(const ntscsim_ctx *c, unsigned layout, int W, int H)
+static MixedGeom *mixed_geometry_cached(const ntscsim_ctx *c, unsigned layout, int W, int H, int variant)
 {
     for (MixedGeom *e : c->mixed_geoms)
-        if (e->W == W && e->H == H && e->layout == layout) return e;
+        if (e->W == W && e->H == H && e->layout == layout && e->variant == variant) return e;
     return nullptr;
 }
 
@@ -1343,14 +1345,14 @@ static const MixedPtab *mixed_ptab_cached(const ntscsim_ctx *c, int K)
     return nullptr;
 }
 
-static int mixed_geometry(ntscsim_ctx *c, const ntscsim_params &prm, int W, int H, MixedGeom *&out)
+static int mixed_geometry(ntscsim_ctx *c, const ntscsim_params &prm, int W, int H, int variant, MixedGeom *&out)
 {
     const unsigned layout = mixed_draw_layout(prm);
-    if ((out = mixed_geometry_cached(c, layout, W, H)) != nullptr) return NTSCSIM_OK;
+    if ((out = mixed_geometry_cached(c, layout, W, H, variant)) != nullptr) return NTSCSIM_OK;
     std::vector<uint32_t> lskip, pskip, jrow;
     MixedGeom *g = new (std::nothrow) MixedGeom();
     if (!g) return NTSCSIM_E_NOMEM;
-    geometry_tables(prm, W, H, 0, lskip, pskip, jrow, g->calls);
+    geometry_tables(prm, W, H, variant, lskip, pskip, jrow, g->calls);
     if (g->lskip.ensure(lskip.size()) != hipSuccess || g->pskip.ensure(pskip.size()) != hipSuccess ||
         g->jrow.ensure(jrow.size()) != hipSuccess ||
         upload_table(g->lskip.p, lskip.data(), lskip.size() * 4) != hipSuccess ||
@@ -1358,10 +1360,11 @@ static int mixed_geometry(ntscsim_ctx *c, const ntscsim_params &prm, int W, int 
         upload_table(g->jrow.p, jrow.data(), jrow.size() * 4) != hipSuccess) {
         g->lskip.release(); g->pskip.release(); g->jrow.release();
         delete g;
-        c->err = "ntscsim_mixed_fields_device: jump tables: device allocation / upload failed";
+        c->err = std::string(variant ? "ntscsim_mixed_fields422_device" : "ntscsim_mixed_fields_device") +
+                 ": jump tables: device allocation / upload failed";
         return NTSCSIM_E_HIP;
     }
-    g->W = W; g->H = H; g->layout = layout;
+    g->W = W; g->H = H; g->variant = variant; g->layout = layout;
     c->mixed_geoms.push_back(g);
     out = g;
     return NTSCSIM_OK;
@@ -1381,7 +1384,7 @@ static int mixed_ptab(ntscsim_ctx *c, int K, const double *&out)
     if (e->t.ensure(t.size()) != hipSuccess || upload_table(e->t.p, t.data(), t.size() * sizeof(double)) != hipSuccess) {
         e->t.release();
         delete e;
-        c->err = "ntscsim_mixed_fields_device: phase-noise table: device allocation / upload failed";
+        c->err = "mixed fields call: phase-noise table: device allocation / upload failed";
         return NTSCSIM_E_HIP;
     }
     e->K = K;
@@ -1393,6 +1396,33 @@ static int mixed_ptab(ntscsim_ctx *c, int K, const double *&out)
 #ifndef NTSC_MIXED_TABLES_MAX
 #define NTSC_MIXED_TABLES_MAX 256     /* cached table sets of either kind before the cache starts over */
 #endif
+
+// The flush rule of the two table caches, for the groups of one call (either tool's: `variant`).
+template <class ParamsOf>
+static int mixed_tables_make_room(ntscsim_ctx *c, const mixed::Plan &plan, ParamsOf params_of, int W, int H, int variant)
+{
+    unsigned new_layouts = 0;                    // bit per draw layout (16 of them) this geometry lacks
+    std::vector<int> new_levels;
+    for (size_t g = 0; g < plan.groups.size(); g++) {
+        const ntscsim_params &prm = params_of(plan.groups[g].set);
+        const unsigned layout = mixed_draw_layout(prm);
+        if (!mixed_geometry_cached(c, layout, W, H, variant)) new_layouts |= 1u << layout;
+        const int K = prm.video_chroma_phase_noise;
+        if (K != 0 && !mixed_ptab_cached(c, K)) new_levels.push_back(K);
+    }
+    std::sort(new_levels.begin(), new_levels.end());
+    new_levels.erase(std::unique(new_levels.begin(), new_levels.end()), new_levels.end());
+    const size_t add_geoms = (size_t)__builtin_popcount(new_layouts), add_ptabs = new_levels.size();
+    if ((add_geoms && c->mixed_geoms.size() + add_geoms > NTSC_MIXED_TABLES_MAX) ||
+        (add_ptabs && c->mixed_ptabs.size() + add_ptabs > NTSC_MIXED_TABLES_MAX)) {
+        HIPCHK(c, hipDeviceSynchronize());
+        for (MixedGeom *e : c->mixed_geoms) { e->lskip.release(); e->pskip.release(); e->jrow.release(); delete e; }
+        for (MixedPtab *e : c->mixed_ptabs) { e->t.release(); delete e; }
+        c->mixed_geoms.clear(); c->mixed_ptabs.clear();
+        c->mixed_table_flushes++;
+    }
+    return NTSCSIM_OK;
+}
 
 static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n_sets,
                                const ntscsim_mixed_field_desc *descs, int n, int W, int H, void *hip_stream)
@@ -1460,28 +1490,8 @@ static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n
     // ---- tables: one set per draw layout, one cos/sin table per phase-noise level.  A call whose tables are all cached
     // touches neither cache nor device; one that would take a cache past its bound with the entries it MISSES drains the
     // device and starts both over before it takes any (entries are immutable while anything queued may read them).
-    {
-        unsigned new_layouts = 0;                    // bit per draw layout (16 of them) this geometry lacks
-        std::vector<int> new_levels;
-        for (size_t g = 0; g < ng; g++) {
-            const ntscsim_params &prm = params_of(plan.groups[g].set);
-            const unsigned layout = mixed_draw_layout(prm);
-            if (!mixed_geometry_cached(c, layout, W, H)) new_layouts |= 1u << layout;
-            const int K = prm.video_chroma_phase_noise;
-            if (K != 0 && !mixed_ptab_cached(c, K)) new_levels.push_back(K);
-        }
-        std::sort(new_levels.begin(), new_levels.end());
-        new_levels.erase(std::unique(new_levels.begin(), new_levels.end()), new_levels.end());
-        const size_t add_geoms = (size_t)__builtin_popcount(new_layouts), add_ptabs = new_levels.size();
-        if ((add_geoms && c->mixed_geoms.size() + add_geoms > NTSC_MIXED_TABLES_MAX) ||
-            (add_ptabs && c->mixed_ptabs.size() + add_ptabs > NTSC_MIXED_TABLES_MAX)) {
-            HIPCHK(c, hipDeviceSynchronize());
-            for (MixedGeom *e : c->mixed_geoms) { e->lskip.release(); e->pskip.release(); e->jrow.release(); delete e; }
-            for (MixedPtab *e : c->mixed_ptabs) { e->t.release(); delete e; }
-            c->mixed_geoms.clear(); c->mixed_ptabs.clear();
-            c->mixed_table_flushes++;
-        }
-    }
+    rc = mixed_tables_make_room(c, plan, params_of, W, H, 0);
+    if (rc != NTSCSIM_OK) return rc;
     // ---- records: [n FieldDev, sorted by group][ng MixedGroup][n group of a field][encoder blocks][decoder blocks x 3]
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t off_groups = up16((size_t)n * sizeof(FieldDev));
@@ -1522,7 +1532,7 @@ static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n
         o.P.nfields = pg.nf; o.P.R = pg.R; o.P.Rpad = plan.Rpad;
         o.P.src_al16 = al_src; o.P.dst_al16 = al_dst;
         MixedGeom *mg = nullptr;
-        rc = mixed_geometry(c, prm, W, H, mg);
+        rc = mixed_geometry(c, prm, W, H, 0, mg);
         if (rc != NTSCSIM_OK) return rc;
         o.G.lskip = mg->lskip.p; o.G.pskip = mg->pskip.p; o.G.jrow = mg->jrow.p;
         o.G.ptab = nullptr;
@@ -1697,6 +1707,142 @@ static double alpha_rate(double rate, double hz)
     return timeInterval / (tau + timeInterval);
 }
 
+// What the YUV422P tool derives from one parameter set (both callers: prepare422() for the ctx's own set,
+// ntscsim_mixed_fields422_device() per named set): the switches as fill_dev_params() reads them, variant 1, and the
+// filter constants of the 8-bit tool, whose chroma runs at half the luma sample rate.
+struct Derived422 { double a_hp_i = 0, a_hp_q = 0, a_sh_c = 0; };
+static int derive422(const ntscsim_ctx *c, const ntscsim_params &p, DevParams &D, Derived422 &X)
+{
+    fill_dev_params(p, D);
+    if (c->warm_override[0] > 0) D.warm_luma = c->warm_override[0];
+    if (c->warm_override[1] > 0) D.warm_chroma = c->warm_override[1];
+    D.variant = 1;
+    const double rl = (315000000.00 * 4) / 88, rc2 = (315000000.00 * 4) / (88 * 2);
+    double luma_cut = 2400000, chroma_cut = 320000;                     // :793-808
+    D.cdelay = 4;
+    if (p.output_vhs_tape_speed == NTSCSIM_VHS_LP) { luma_cut = 1900000; chroma_cut = 300000; D.cdelay = 5; }
+    if (p.output_vhs_tape_speed == NTSCSIM_VHS_EP) { luma_cut = 1400000; chroma_cut = 280000; D.cdelay = 6; }
+    D.a_in_i = alpha_rate(rc2, 1300000);                                // :366-381
+    D.a_in_q = alpha_rate(rc2, 600000);
+    X.a_hp_i = alpha_rate(rc2, 1300000 / 2.0); X.a_hp_q = alpha_rate(rc2, 600000 / 2.0);
+    D.a_tv = alpha_rate(rc2, (315000000.00 * 4) / (88 * 2 * 4));        // lite :408
+    D.a_vl = alpha_rate(rl, luma_cut);
+    D.a_vc = alpha_rate(rc2, chroma_cut);
+    D.a_sh = alpha_rate(rl, luma_cut * 2);                              // :893
+    X.a_sh_c = alpha_rate(rc2, chroma_cut * 2);                          // :911
+    D.sharpen = p.vhs_out_sharpen;
+    D.out_lp = p.composite_out_chroma_lowpass ? 2 : (p.composite_out_chroma_lowpass_lite ? 1 : 0);  // :948-951
+    if (p.video_yc_recombine < 0 || p.video_yc_recombine > 64) return NTSCSIM_E_PARAM;
+    return NTSCSIM_OK;
+}
+
+// What is derived from one descriptor: its record, and what the call accumulates over all of them.  bkey: the
+// descriptor's parameter set has black-key feedback (a set without it gets no flt pointers).
+struct Acc422 {
+    bool any_render = false, any_flt = false;
+    bool al_y16 = true, al_c8 = true;      // vector copies between frame rows and scratch words
+    int max_ls = 0;                        // largest destination linesize (the pitch of the halo-row copies)
+};
+static int fill_field422_record(const ntscsim_field422_desc &d, int W, bool bkey, Field422Dev &o, Acc422 &A)
+{
+    if (d.field > 1) return NTSCSIM_E_ARG;
+    std::memset(&o, 0, sizeof(o));
+    for (int k = 0; k < 3; k++) {
+        if (!d.dst_dev[k]) return NTSCSIM_E_ARG;
+        const int need = k == 0 ? W : W / 2;
+        if (d.dst_linesize[k] < need) return NTSCSIM_E_SIZE;
+        o.dst[k] = (uint8_t *)d.dst_dev[k]; o.dst_ls[k] = d.dst_linesize[k];
+        if (d.dst_linesize[k] > A.max_ls) A.max_ls = d.dst_linesize[k];
+        if (d.src_dev[0]) {
+            if (!d.src_dev[k] || d.src_linesize[k] < need) return NTSCSIM_E_SIZE;
+            o.src[k] = (const uint8_t *)d.src_dev[k]; o.src_ls[k] = d.src_linesize[k];
+        }
+        if (d.flt_dev[0] && bkey) {
+            if (!d.flt_dev[k] || d.flt_linesize[k] < need) return NTSCSIM_E_SIZE;
+            o.flt[k] = (uint8_t *)d.flt_dev[k]; o.flt_ls[k] = d.flt_linesize[k];
+        }
+    }
+    if (d.src_dev[0]) {
+        const int minh = (d.flags & NTSCSIM_422_INTERLACED) ? 4 : 2;
+        if (d.src_height < minh) return NTSCSIM_E_SIZE;
+        A.any_render = true;
+    }
+    A.any_flt = A.any_flt || o.flt[0] != nullptr;
+    A.al_y16 = A.al_y16 && !(((uintptr_t)d.dst_dev[0] | (uintptr_t)d.dst_linesize[0]) & 15);
+    A.al_c8 = A.al_c8 && !(((uintptr_t)d.dst_dev[1] | (uintptr_t)d.dst_linesize[1] |
+                            (uintptr_t)d.dst_dev[2] | (uintptr_t)d.dst_linesize[2]) & 7);
+    o.src_height = d.src_height;
+    o.field = d.field; o.flags = d.flags; o.fieldno = d.fieldno;
+    return NTSCSIM_OK;
+}
+// ... and the record the setup kernels read: parity, field number, rand() state at `pos`
+static void fill_field422_rng(ntscsim_ctx *c, const ntscsim_field422_desc &d, uint64_t pos, FieldDev &fo)
+{
+    std::memset(&fo, 0, sizeof(fo));
+    fo.field = d.field; fo.fieldno = d.fieldno;
+    const RandState s = ctx_state_at(c, pos);
+    std::memcpy(fo.rng, s.w, sizeof(s.w));
+    for (int j = 31; j < 61; j++) fo.rng[j] = fo.rng[j - 31] + fo.rng[j - 3];
+}
+
+// Descriptors of one call run concurrently and in place.  Two of them on the same destination frame
+// are a write-write race when they have the same field parity, and a read-write race when the luma
+// rows are tighter than width + 2: the Y/C separator reads two bytes past its row (:496), i.e. the
+// first bytes of the OTHER field's row, which the tool has / has not processed yet depending on the
+// order of its sequential loop (:1783-1800).  Refuse both; separate calls are stream-ordered.
+// (frames are compared by the byte range of their luma plane, not by base pointer: sub-frame views of one
+// allocation and frames whose planes overlap partly race in the same way)
+template <class DescAt>
+static int check_destinations422(ntscsim_ctx *c, int n, int W, int H, DescAt desc_at)
+{
+    if (n <= 1) return NTSCSIM_OK;
+    struct Key { uintptr_t lo, hi; unsigned field; int ls; unsigned nocomp; };
+    std::vector<Key> keys((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const ntscsim_field422_desc &d = desc_at(i);
+        const uintptr_t lo = (uintptr_t)d.dst_dev[0];
+        keys[(size_t)i] = {lo, lo + (uintptr_t)d.dst_linesize[0] * (uintptr_t)(H - 1) + (uintptr_t)W,
+                           d.field & 1u, d.dst_linesize[0], (d.flags & NTSCSIM_422_NOCOMP) ? 1u : 0u};
+    }
+    std::sort(keys.begin(), keys.end(), [](const Key &a, const Key &b) {
+        return a.lo != b.lo ? a.lo < b.lo : a.field < b.field; });
+    // sweep: every descriptor against the ones whose range is still open
+    size_t open0 = 0;
+    for (size_t i = 1; i < keys.size(); i++) {
+        while (open0 < i && keys[open0].hi <= keys[i].lo) {
+            // (ranges sorted by start: one that ended before this start can still be followed by longer ones --
+            //  only skip a prefix of closed ranges, the inner loop tests the rest)
+            open0++;
+        }
+        for (size_t j = open0; j < i; j++) {
+            const Key &a = keys[j], &b = keys[i];
+            if (a.hi <= b.lo) continue;
+            if (a.lo != b.lo || a.ls != b.ls) {
+                // views of one allocation with the same linesize whose pixel columns (plus the separator's two bytes
+                // behind each row) never meet -- side-by-side tiles, row-interleaved frames with a doubled linesize --
+                // write disjoint bytes: no race
+                if (a.ls == b.ls && a.ls > 0) {
+                    const uintptr_t d = (b.lo - a.lo) % (uintptr_t)a.ls;       // b's first column inside a's rows
+                    const uintptr_t span = (uintptr_t)W + 2u;
+                    if (d >= span && d + span <= (uintptr_t)a.ls) continue;
+                }
+                c->err = "descriptors of one batch write overlapping destination frames that are not the same frame";
+                return NTSCSIM_E_ARG;
+            }
+            if (a.field == b.field) {
+                c->err = "descriptors of one batch share a destination frame and field";
+                return NTSCSIM_E_ARG;
+            }
+            if ((a.ls < W + 2 || b.ls < W + 2) && !(a.nocomp && b.nocomp)) {
+                c->err = "both fields of one destination frame in one batch need dst_linesize[0] >= width + 2 "
+                         "(the Y/C separator reads two bytes past each luma row); use separate calls";
+                return NTSCSIM_E_ARG;
+            }
+        }
+    }
+    return NTSCSIM_OK;
+}
+
 // One ntscsim_fields422_device() call in two halves, so that a prepared batch (ntscsim_batch422_*) can
 // repeat the second: everything derived from the descriptors ...
 struct Prep422 {
@@ -1716,137 +1862,38 @@ static int prepare422(ntscsim_ctx *c, const ntscsim_field422_desc *descs, int n,
     const ntscsim_params &p = c->prm;
 
     DevParams &D = P.D;
-    fill_dev_params(p, D);
-    if (c->warm_override[0] > 0) D.warm_luma = c->warm_override[0];
-    if (c->warm_override[1] > 0) D.warm_chroma = c->warm_override[1];
-    D.variant = 1;
-    D.W = W; D.H = H; D.Lslot = (H + 1) / 2; D.nfields = n;
-    const long long R = (long long)n * D.Lslot;
+    const long long R = (long long)n * ((H + 1) / 2);
     if (R > (1ll << 30)) return NTSCSIM_E_SIZE;
+    Derived422 X;
+    int rc = derive422(c, p, D, X);
+    D.W = W; D.H = H; D.Lslot = (H + 1) / 2; D.nfields = n;
     D.R = (int)R;
     D.Rpad = (int)(((R + 63) / 64) * 64 + 64);
-    // filter constants of the 8-bit tool: chroma runs at half the luma sample rate
-    const double rl = (315000000.00 * 4) / 88, rc2 = (315000000.00 * 4) / (88 * 2);
-    double luma_cut = 2400000, chroma_cut = 320000;                     // :793-808
-    D.cdelay = 4;
-    if (p.output_vhs_tape_speed == NTSCSIM_VHS_LP) { luma_cut = 1900000; chroma_cut = 300000; D.cdelay = 5; }
-    if (p.output_vhs_tape_speed == NTSCSIM_VHS_EP) { luma_cut = 1400000; chroma_cut = 280000; D.cdelay = 6; }
-    D.a_in_i = alpha_rate(rc2, 1300000);                                // :366-381
-    D.a_in_q = alpha_rate(rc2, 600000);
-    P.a_hp_i = alpha_rate(rc2, 1300000 / 2.0); P.a_hp_q = alpha_rate(rc2, 600000 / 2.0);
-    D.a_tv = alpha_rate(rc2, (315000000.00 * 4) / (88 * 2 * 4));        // lite :408
-    D.a_vl = alpha_rate(rl, luma_cut);
-    D.a_vc = alpha_rate(rc2, chroma_cut);
-    D.a_sh = alpha_rate(rl, luma_cut * 2);                              // :893
-    P.a_sh_c = alpha_rate(rc2, chroma_cut * 2);                          // :911
-    D.sharpen = p.vhs_out_sharpen;
-    D.out_lp = p.composite_out_chroma_lowpass ? 2 : (p.composite_out_chroma_lowpass_lite ? 1 : 0);  // :948-951
-    if (p.video_yc_recombine < 0 || p.video_yc_recombine > 64) return NTSCSIM_E_PARAM;
+    P.a_hp_i = X.a_hp_i; P.a_hp_q = X.a_hp_q; P.a_sh_c = X.a_sh_c;
+    if (rc != NTSCSIM_OK) return rc;
 
-    int rc = build_geometry(c, W, H, D);
+    rc = build_geometry(c, W, H, D);
     if (rc != NTSCSIM_OK) return rc;
     if (D.pnoise_k) { rc = build_ptab(c); if (rc != NTSCSIM_OK) return rc; }
 
     uint64_t pos = P.rng_end;
-    bool any_render = false, any_flt = false;
-    bool al_y16 = true, al_c8 = true;      // vector copies between frame rows and scratch words
+    Acc422 A;
+    A.max_ls = P.max_ls;
     for (int i = 0; i < n; i++) {
         const ntscsim_field422_desc &d = descs[i];
-        if (d.field > 1) return NTSCSIM_E_ARG;
-        Field422Dev &o = host_fields422[(size_t)i];
-        std::memset(&o, 0, sizeof(o));
-        for (int k = 0; k < 3; k++) {
-            if (!d.dst_dev[k]) return NTSCSIM_E_ARG;
-            const int need = k == 0 ? W : W / 2;
-            if (d.dst_linesize[k] < need) return NTSCSIM_E_SIZE;
-            o.dst[k] = (uint8_t *)d.dst_dev[k]; o.dst_ls[k] = d.dst_linesize[k];
-            if (d.dst_linesize[k] > P.max_ls) P.max_ls = d.dst_linesize[k];
-            if (d.src_dev[0]) {
-                if (!d.src_dev[k] || d.src_linesize[k] < need) return NTSCSIM_E_SIZE;
-                o.src[k] = (const uint8_t *)d.src_dev[k]; o.src_ls[k] = d.src_linesize[k];
-            }
-            if (d.flt_dev[0] && p.black_key_level_feedback >= 0) {
-                if (!d.flt_dev[k] || d.flt_linesize[k] < need) return NTSCSIM_E_SIZE;
-                o.flt[k] = (uint8_t *)d.flt_dev[k]; o.flt_ls[k] = d.flt_linesize[k];
-            }
-        }
-        if (d.src_dev[0]) {
-            const int minh = (d.flags & NTSCSIM_422_INTERLACED) ? 4 : 2;
-            if (d.src_height < minh) return NTSCSIM_E_SIZE;
-            any_render = true;
-        }
-        any_flt = any_flt || o.flt[0] != nullptr;
-        al_y16 = al_y16 && !(((uintptr_t)d.dst_dev[0] | (uintptr_t)d.dst_linesize[0]) & 15);
-        al_c8 = al_c8 && !(((uintptr_t)d.dst_dev[1] | (uintptr_t)d.dst_linesize[1] |
-                            (uintptr_t)d.dst_dev[2] | (uintptr_t)d.dst_linesize[2]) & 7);
-        o.src_height = d.src_height;
-        o.field = d.field; o.flags = d.flags; o.fieldno = d.fieldno;
+        rc = fill_field422_record(d, W, p.black_key_level_feedback >= 0, host_fields422[(size_t)i], A);
+        P.max_ls = A.max_ls;
+        if (rc != NTSCSIM_OK) return rc;
         if (d.rng_pos != NTSCSIM_RNG_AUTO) pos = d.rng_pos;
-        FieldDev &fo = host_fields[(size_t)i];
-        std::memset(&fo, 0, sizeof(fo));
-        fo.field = d.field; fo.fieldno = d.fieldno;
-        const RandState s = ctx_state_at(c, pos);
-        std::memcpy(fo.rng, s.w, sizeof(s.w));
-        for (int j = 31; j < 61; j++) fo.rng[j] = fo.rng[j - 31] + fo.rng[j - 3];
+        fill_field422_rng(c, d, pos, host_fields[(size_t)i]);
         if (!(d.flags & NTSCSIM_422_NOCOMP)) pos += c->geom_cur->calls[d.field & 1];
     }
-    // Descriptors of one call run concurrently and in place.  Two of them on the same destination frame
-    // are a write-write race when they have the same field parity, and a read-write race when the luma
-    // rows are tighter than width + 2: the Y/C separator reads two bytes past its row (:496), i.e. the
-    // first bytes of the OTHER field's row, which the tool has / has not processed yet depending on the
-    // order of its sequential loop (:1783-1800).  Refuse both; separate calls are stream-ordered.
-    // (frames are compared by the byte range of their luma plane, not by base pointer: sub-frame views of one
-    // allocation and frames whose planes overlap partly race in the same way)
-    if (n > 1) {
-        struct Key { uintptr_t lo, hi; unsigned field; int ls; unsigned nocomp; };
-        std::vector<Key> keys((size_t)n);
-        for (int i = 0; i < n; i++) {
-            const uintptr_t lo = (uintptr_t)descs[i].dst_dev[0];
-            keys[(size_t)i] = {lo, lo + (uintptr_t)descs[i].dst_linesize[0] * (uintptr_t)(H - 1) + (uintptr_t)W,
-                               descs[i].field & 1u, descs[i].dst_linesize[0],
-                               (descs[i].flags & NTSCSIM_422_NOCOMP) ? 1u : 0u};
-        }
-        std::sort(keys.begin(), keys.end(), [](const Key &a, const Key &b) {
-            return a.lo != b.lo ? a.lo < b.lo : a.field < b.field; });
-        // sweep: every descriptor against the ones whose range is still open
-        size_t open0 = 0;
-        for (size_t i = 1; i < keys.size(); i++) {
-            while (open0 < i && keys[open0].hi <= keys[i].lo) {
-                // (ranges sorted by start: one that ended before this start can still be followed by longer ones --
-                //  only skip a prefix of closed ranges, the inner loop tests the rest)
-                open0++;
-            }
-            for (size_t j = open0; j < i; j++) {
-                const Key &a = keys[j], &b = keys[i];
-                if (a.hi <= b.lo) continue;
-                if (a.lo != b.lo || a.ls != b.ls) {
-                    // views of one allocation with the same linesize whose pixel columns (plus the separator's two bytes
-                    // behind each row) never meet -- side-by-side tiles, row-interleaved frames with a doubled linesize --
-                    // write disjoint bytes: no race
-                    if (a.ls == b.ls && a.ls > 0) {
-                        const uintptr_t d = (b.lo - a.lo) % (uintptr_t)a.ls;       // b's first column inside a's rows
-                        const uintptr_t span = (uintptr_t)W + 2u;
-                        if (d >= span && d + span <= (uintptr_t)a.ls) continue;
-                    }
-                    c->err = "descriptors of one batch write overlapping destination frames that are not the same frame";
-                    return NTSCSIM_E_ARG;
-                }
-                if (a.field == b.field) {
-                    c->err = "descriptors of one batch share a destination frame and field";
-                    return NTSCSIM_E_ARG;
-                }
-                if ((a.ls < W + 2 || b.ls < W + 2) && !(a.nocomp && b.nocomp)) {
-                    c->err = "both fields of one destination frame in one batch need dst_linesize[0] >= width + 2 "
-                             "(the Y/C separator reads two bytes past each luma row); use separate calls";
-                    return NTSCSIM_E_ARG;
-                }
-            }
-        }
-    }
-    D.src_al16 = al_y16;      // (422 path: luma rows 16-byte aligned)
-    D.dst_al16 = al_c8;       // (422 path: chroma rows 8-byte aligned)
+    rc = check_destinations422(c, n, W, H, [&](int i) -> const ntscsim_field422_desc & { return descs[i]; });
+    if (rc != NTSCSIM_OK) return rc;
+    D.src_al16 = A.al_y16;    // (422 path: luma rows 16-byte aligned)
+    D.dst_al16 = A.al_c8;     // (422 path: chroma rows 8-byte aligned)
 
-    P.any_render = any_render; P.any_flt = any_flt;
+    P.any_render = A.any_render; P.any_flt = A.any_flt;
     P.rng_end = pos;
     return NTSCSIM_OK;
 }
@@ -2078,6 +2125,240 @@ extern "C" int ntscsim_fields422_device(ntscsim_ctx *c, const ntscsim_field422_d
     if (prof) c->ev_live.push_back(evs);
     c->rng_pos = P.rng_end;
     return NTSCSIM_OK;
+}
+
+// ---- YUV422P fields that name different parameter sets, one launch of each kernel (csrc/mixed_plan.hpp,
+// csrc/ntsc422_mixed.hip): mixed_fields_device() for the 8-bit tool.  All sets run the twelve-sweep body.
+static int mixed_fields422_device(ntscsim_ctx *c, const ntscsim_params *sets, int n_sets,
+                                  const ntscsim_mixed_field422_desc *descs, int n, int W, int H, void *hip_stream)
+{
+    if (!c || n < 0 || n_sets < 0) return NTSCSIM_E_ARG;
+    if (n == 0) return NTSCSIM_OK;
+    if (!descs) return NTSCSIM_E_ARG;
+    if (W < 16 || (W & 1) || H < 2 || W > 16384 || H > 16384) return NTSCSIM_E_SIZE;   // as prepare422
+    if (n > 65535) return NTSCSIM_E_SIZE;                 // render / black-key grids: one plane per field
+    const int Lslot = (H + 1) / 2;
+    if (c->pipe_fault && *c->pipe_fault) {      // raised by an earlier launch of this ctx, as in ntscsim_fields422_device
+        c->err = "k422_pipe: hand-off timed out in workgroup " + std::to_string(*c->pipe_fault - 1u);
+        *c->pipe_fault = 0u;
+        return NTSCSIM_E_HIP;
+    }
+
+    // ---- which sets the descriptors name.  The plan sees the NAMED sets only, numbered 0 .. in ascending order (`used`)
+    std::vector<int32_t> used((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int32_t set = descs[i].set;
+        if (set < -1 || set >= n_sets || (set >= 0 && !sets)) return NTSCSIM_E_ARG;
+        used[(size_t)i] = set;
+    }
+    std::sort(used.begin(), used.end());
+    used.erase(std::unique(used.begin(), used.end()), used.end());
+    const int n_used = (int)used.size();
+    auto params_of = [&](int32_t id) -> const ntscsim_params & { return used[(size_t)id] < 0 ? c->prm : sets[used[(size_t)id]]; };
+    // ---- the named sets: refused as ntscsim_create() and prepare422() refuse them; sets nobody names are not looked at
+    struct Set422 { DevParams D; Derived422 X; };
+    std::vector<Set422> derived((size_t)n_used);
+    std::vector<mixed::SetInfo> info((size_t)n_used + 1);
+    for (int s = 0; s < n_used; s++) {
+        const ntscsim_params &prm = params_of(s);
+        if (prm.struct_size != sizeof(ntscsim_params)) return NTSCSIM_E_ARG;
+        int vrc = ntscsim_params_validate(&prm);
+        if (vrc != NTSCSIM_OK) return vrc;
+        vrc = derive422(c, prm, derived[(size_t)s].D, derived[(size_t)s].X);
+        if (vrc != NTSCSIM_OK) return vrc;
+        mixed::SetInfo &si = info[(size_t)(s + 1)];
+        for (unsigned par = 0; par < 2; par++) si.calls[par] = ntscsim_rng_calls_per_field_422(&prm, W, H, par);
+        si.cls = 0;                               // one decoder class: every set runs the twelve-sweep body
+    }
+    // ---- the descriptors (records in the caller's order; the plan sorts them)
+    std::vector<Field422Dev> recs((size_t)n);
+    std::vector<mixed::Field> pf((size_t)n);
+    Acc422 A;
+    for (int i = 0; i < n; i++) {
+        const ntscsim_field422_desc &d = descs[i].d;
+        const int32_t id = (int32_t)(std::lower_bound(used.begin(), used.end(), descs[i].set) - used.begin());
+        const int drc = fill_field422_record(d, W, params_of(id).black_key_level_feedback >= 0, recs[(size_t)i], A);
+        if (drc != NTSCSIM_OK) return drc;
+        pf[(size_t)i] = mixed::Field{id, d.field, d.rng_pos, (d.flags & NTSCSIM_422_NOCOMP) ? 1u : 0u};
+    }
+    // (across the whole call, whatever sets the descriptors name)
+    int rc = check_destinations422(c, n, W, H, [&](int i) -> const ntscsim_field422_desc & { return descs[i].d; });
+    if (rc != NTSCSIM_OK) return rc;
+    mixed::Plan plan;
+    // (one grid plane per field: the 65535-field limit; no composite plane: no limit on Rpad * W)
+    rc = mixed::make_plan(pf.data(), n, n_used, info.data(), Lslot, W, true, c->rng_pos, plan, false);
+    if (rc != mixed::PLAN_OK) return rc == mixed::PLAN_E_SIZE ? NTSCSIM_E_SIZE : NTSCSIM_E_ARG;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const size_t ng = plan.groups.size();
+    rc = mixed_tables_make_room(c, plan, params_of, W, H, 1);
+    if (rc != NTSCSIM_OK) return rc;
+    // ---- records: [n FieldDev, sorted by group][n Field422Dev, likewise][ng Mixed422Group][ng MixedGroup: what
+    //               k_mixed_setup reads of a group][n group of a field][row-state blocks of 64 rows][process blocks of 63]
+    const std::vector<mixed::BlockRef> &ptab = plan.dec_tab[0];
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t off_f422 = up16((size_t)n * sizeof(FieldDev));
+    const size_t off_groups = up16(off_f422 + (size_t)n * sizeof(Field422Dev));
+    const size_t off_sgroups = up16(off_groups + ng * sizeof(Mixed422Group));
+    const size_t off_gof = up16(off_sgroups + ng * sizeof(MixedGroup));
+    const size_t off_enc = up16(off_gof + (size_t)n * sizeof(int32_t));
+    const size_t off_proc = up16(off_enc + plan.enc_tab.size() * sizeof(MixedBlock));
+    const size_t bytes = up16(off_proc + ptab.size() * sizeof(MixedBlock));
+
+    const int si = c->mixed_stage_idx;
+    c->mixed_stage_idx ^= 1;
+    if (!c->mixed_stage_ev[si]) HIPCHK(c, hipEventCreateWithFlags(&c->mixed_stage_ev[si], hipEventDisableTiming));
+    if (c->mixed_stage_used[si]) HIPCHK(c, hipEventSynchronize(c->mixed_stage_ev[si]));
+    if (c->mixed_stage_cap[si] < bytes) {
+        if (c->mixed_stage[si]) (void)hipHostFree(c->mixed_stage[si]);
+        c->mixed_stage[si] = nullptr; c->mixed_stage_cap[si] = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        HIPCHK(c, hipHostMalloc((void **)&c->mixed_stage[si], want, hipHostMallocDefault));
+        c->mixed_stage_cap[si] = want;
+    }
+    unsigned char *host = c->mixed_stage[si];
+    std::memset(host, 0, bytes);
+    FieldDev *fh = reinterpret_cast<FieldDev *>(host);
+    Field422Dev *f422h = reinterpret_cast<Field422Dev *>(host + off_f422);
+    for (int i = 0; i < n; i++) {
+        const size_t at = (size_t)plan.slot[(size_t)i];
+        fill_field422_rng(c, descs[i].d, plan.rng_start[(size_t)i], fh[at]);
+        f422h[at] = recs[(size_t)i];
+    }
+    Mixed422Group *gh = reinterpret_cast<Mixed422Group *>(host + off_groups);
+    MixedGroup *sgh = reinterpret_cast<MixedGroup *>(host + off_sgroups);
+    bool any_halo = false;
+    for (size_t g = 0; g < ng; g++) {
+        const mixed::Group &pg = plan.groups[g];
+        const ntscsim_params &prm = params_of(pg.set);
+        Mixed422Group &o = gh[g];
+        o.P = derived[(size_t)pg.set].D;
+        o.P.W = W; o.P.H = H; o.P.Lslot = Lslot;
+        o.P.nfields = pg.nf; o.P.R = pg.R; o.P.Rpad = plan.Rpad;
+        o.P.src_al16 = A.al_y16; o.P.dst_al16 = A.al_c8;
+        MixedGeom *mg = nullptr;
+        rc = mixed_geometry(c, prm, W, H, 1, mg);
+        if (rc != NTSCSIM_OK) return rc;
+        o.G.lskip = mg->lskip.p; o.G.pskip = mg->pskip.p; o.G.jrow = mg->jrow.p;
+        o.G.ptab = nullptr;
+        if (o.P.pnoise_k) { rc = mixed_ptab(c, o.P.pnoise_k, o.G.ptab); if (rc != NTSCSIM_OK) return rc; }
+        const Derived422 &X = derived[(size_t)pg.set].X;
+        o.a_hp_i = X.a_hp_i; o.a_hp_q = X.a_hp_q; o.a_sh_c = X.a_sh_c;
+        o.sharpen_c = prm.vhs_out_sharpen_chroma;
+        o.yc_recombine = prm.video_yc_recombine;
+        o.after_yc_sep = prm.nocolor_subcarrier_after_yc_sep;
+        o.bkey_level = prm.black_key_level_feedback;
+        o.base = pg.base; o.field0 = pg.field0;
+        // k_mixed_setup keeps its signature, so it reads its own array of MixedGroup records: sgh[g] MUST mirror gh[g] in
+        // every member the two records share -- filled here, from the finished record, and nowhere else
+        static_assert(std::is_same<decltype(MixedGroup::P), decltype(Mixed422Group::P)>::value &&
+                      std::is_same<decltype(MixedGroup::G), decltype(Mixed422Group::G)>::value &&
+                      std::is_same<decltype(MixedGroup::base), decltype(Mixed422Group::base)>::value &&
+                      std::is_same<decltype(MixedGroup::field0), decltype(Mixed422Group::field0)>::value &&
+                      sizeof(MixedGroup) == sizeof(DevParams) + sizeof(GeomDev) + 2 * sizeof(int32_t),
+                      "MixedGroup is exactly the members mirrored here");
+        sgh[g].P = o.P; sgh[g].G = o.G; sgh[g].base = o.base; sgh[g].field0 = o.field0;
+        any_halo = any_halo || pg.dec_blocks > 1;
+    }
+    std::memcpy(host + off_gof, plan.group_of.data(), (size_t)n * sizeof(int32_t));
+    std::memcpy(host + off_enc, plan.enc_tab.data(), plan.enc_tab.size() * sizeof(MixedBlock));
+    std::memcpy(host + off_proc, ptab.data(), ptab.size() * sizeof(MixedBlock));
+    // ---- scratch: row tables for the padded scanline space, plane scratch and halo rows per process block of the LAUNCH
+    const size_t R = (size_t)plan.R, Rpad = (size_t)plan.Rpad;
+    const size_t nblk = ptab.size(), S = nblk * 64;
+    const size_t W2 = (size_t)W / 2;
+    const size_t Wq = ((size_t)W + 3) / 4 + 2, W2q = (W2 + 3) / 4 + 2;   // words per row (+slack), as launch422
+    HIPCHK(c, c->mixed_recs.ensure(bytes));
+    HIPCHK(c, c->scratch422.ensure(S * (2 * Wq + 2 * W2q) + 256));
+    HIPCHK(c, c->hs_shift.ensure(R)); HIPCHK(c, c->pn_noise.ensure(R)); HIPCHK(c, c->dropout.ensure(R));
+    HIPCHK(c, c->rs_luma.ensure(31 * Rpad)); HIPCHK(c, c->n0_luma.ensure(Rpad));
+    HIPCHK(c, c->rs_chroma.ensure(31 * Rpad)); HIPCHK(c, c->n0_u.ensure(Rpad)); HIPCHK(c, c->n0_v.ensure(Rpad));
+    Scratch422 Sc;
+    Sc.S = S;
+    Sc.Y = c->scratch422.p;
+    Sc.T = Sc.Y + S * Wq;
+    Sc.U = Sc.T + S * Wq;
+    Sc.V = Sc.U + S * W2q;
+    Sc.halo_pitch = (uint32_t)((((size_t)A.max_ls + 2 + 63) / 64) * 64);
+    Sc.halo = nullptr;
+    if (any_halo) {
+        HIPCHK(c, c->halo422.ensure(nblk * 3 * Sc.halo_pitch + 256));
+        Sc.halo = c->halo422.p;
+    }
+    // (an early setup kernel of the synchronous calls may still be writing the row tables on its own stream: launch_setup)
+    if (c->spec.armed) (void)hipStreamWaitEvent(st, c->ev_spec, 0);
+    c->spec.armed = c->spec.dry = false;
+    c->spec.have_last = false;
+
+    // profiling as in ntscsim_fields422_device: start | setup done | (empty) | process done | end
+    ntscsim_ctx::EvSet evs;
+    const bool prof = c->profiling;
+    if (prof) {
+        rc = take_events(c, evs);
+        if (rc != NTSCSIM_OK) return rc;
+        HIPCHK(c, hipEventRecord(evs.e[0], st));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->mixed_recs.p, host, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->mixed_stage_ev[si], st));
+    c->mixed_stage_used[si] = true;
+    const FieldDev *fields_dev = reinterpret_cast<const FieldDev *>(c->mixed_recs.p);
+    const Field422Dev *fields422_dev = reinterpret_cast<const Field422Dev *>(c->mixed_recs.p + off_f422);
+    const Mixed422Group *groups_dev = reinterpret_cast<const Mixed422Group *>(c->mixed_recs.p + off_groups);
+    const MixedGroup *sgroups_dev = reinterpret_cast<const MixedGroup *>(c->mixed_recs.p + off_sgroups);
+    const int32_t *gof_dev = reinterpret_cast<const int32_t *>(c->mixed_recs.p + off_gof);
+    const MixedBlock *enc_dev = reinterpret_cast<const MixedBlock *>(c->mixed_recs.p + off_enc);
+    const MixedBlock *proc_dev = reinterpret_cast<const MixedBlock *>(c->mixed_recs.p + off_proc);
+
+    c->kernels.clear();
+    const int nfs = 3 * n, nrs = (int)plan.enc_tab.size();
+    // the draws read no pixels: they go first, beside the host-frame engine's upload of the source (as launch422)
+    note_kernel(c, "k_mixed_setup");
+    hipLaunchKernelGGL(k_mixed_setup, dim3((unsigned)(nfs + 2 * nrs)), dim3(64), 0, st, sgroups_dev, gof_dev, enc_dev, fields_dev,
+                       c->hs_shift.p, c->pn_noise.p, c->dropout.p, c->rs_luma.p, c->n0_luma.p, c->rs_chroma.p, c->n0_u.p,
+                       c->n0_v.p, nfs, nrs);
+    if (c->wait422_ev) {
+        HIPCHK(c, hipStreamWaitEvent(st, c->wait422_ev, 0));
+        c->wait422_ev = nullptr;
+    }
+    if (A.any_render) {
+        note_kernel(c, "k422_mixed_render");
+        hipLaunchKernelGGL(k422_mixed_render, dim3((unsigned)((2 * W + 255) / 256), (unsigned)Lslot, (unsigned)n), dim3(256), 0, st,
+                           groups_dev, gof_dev, fields422_dev);
+    }
+    if (A.any_flt) {
+        note_kernel(c, "k422_mixed_bkey");
+        hipLaunchKernelGGL(k422_mixed_bkey, dim3((unsigned)((W2 + 255) / 256), (unsigned)Lslot, (unsigned)n), dim3(256), 0, st,
+                           groups_dev, gof_dev, fields422_dev);
+    }
+    if (Sc.halo) {
+        note_kernel(c, "k422_mixed_halo");
+        hipLaunchKernelGGL(k422_mixed_halo, dim3((unsigned)nblk), dim3(256), 0, st, groups_dev, proc_dev, fields422_dev, Sc);
+    }
+    if (prof) { HIPCHK(c, hipEventRecord(evs.e[1], st)); HIPCHK(c, hipEventRecord(evs.e[2], st)); }
+    note_kernel(c, "k422_mixed_process");
+    hipLaunchKernelGGL(k422_mixed_process, dim3((unsigned)nblk), dim3(64), 0, st, groups_dev, proc_dev, fields422_dev, Sc,
+                       c->rs_luma.p, c->n0_luma.p, c->rs_chroma.p, c->n0_u.p, c->n0_v.p, c->hs_shift.p, c->pn_noise.p,
+                       c->dropout.p);
+    HIPCHK(c, hipGetLastError());
+    if (prof) {
+        HIPCHK(c, hipEventRecord(evs.e[3], st));
+        HIPCHK(c, hipEventRecord(evs.e[4], st));
+        c->ev_live.push_back(evs);
+    }
+    c->rng_pos = plan.rng_end;
+    return NTSCSIM_OK;
+}
+
+extern "C" int ntscsim_mixed_fields422_device(ntscsim_ctx *c, const ntscsim_params *sets, int n_sets,
+                                              const ntscsim_mixed_field422_desc *descs, int n, int W, int H, void *hip_stream)
+{
+    // (the plan and the call's host tables are std::vectors of the call's size: no exception crosses the C ABI)
+    try {
+        return mixed_fields422_device(c, sets, n_sets, descs, n, W, H, hip_stream);
+    } catch (const std::bad_alloc &) {
+        return NTSCSIM_E_NOMEM;
+    }
 }
 
 // ---- prepared batch of the YUV422P tool: validate + derive + upload once, launch many times

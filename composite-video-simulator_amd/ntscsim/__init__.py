@@ -356,6 +356,43 @@ class FieldSimulator:
         """build_descs422 + run_descs422."""
         self.run_descs422(self.build_descs422(jobs), width, height, stream)
 
+    # ---- the same with parameters per field (ntscsim_mixed_fields422_device) ----------------
+    def build_mixed_descs422(self, sets_idx, jobs, rng_pos=None):
+        """As build_descs422(); sets_idx[i] is the set of job i (-1: this simulator's own parameters).  rng_pos: None
+        (every job's own "rng_pos" key, as in build_descs422) or a list with one absolute position or None per job."""
+        jobs = list(jobs)
+        assert len(sets_idx) == len(jobs)
+        if rng_pos is not None:
+            assert len(rng_pos) == len(jobs)
+            jobs = [dict(j, rng_pos=rp) for j, rp in zip(jobs, rng_pos)]
+        plain = self.build_descs422(jobs)
+        arr = (_capi.MixedField422Desc * len(jobs))()
+        for i in range(len(jobs)):
+            arr[i].d = plain[i]
+            arr[i].set = int(sets_idx[i])
+        return arr
+
+    @staticmethod
+    def build_sets422(sets):
+        """sets: list of Params or ffmpeg_to_composite flag lists -> ntscsim_params array (None for an empty list)."""
+        if not sets:
+            return None
+        arr = (Params * len(sets))()
+        for i, s in enumerate(sets):
+            arr[i] = s if isinstance(s, Params) else make_params_to_composite(s)
+        return arr
+
+    def run_mixed_descs422(self, sets, arr, width, height, stream=None):
+        """Enqueue; does not synchronise.  sets: what build_sets422() returns, or a list it accepts (Params or
+        ffmpeg_to_composite flag lists)."""
+        if isinstance(sets, (list, tuple)):
+            sets = self.build_sets422(sets)
+        if stream is None:
+            stream = self._torch_stream()
+        rc = self._lib.ntscsim_mixed_fields422_device(self._h, sets, 0 if sets is None else len(sets), arr, len(arr),
+                                                      int(width), int(height), C.c_void_p(stream))
+        self._chk(rc, "ntscsim_mixed_fields422_device")
+
     def output422(self, jobs, width, height, stream=None):
         """jobs: list of dicts {frame: 3 CUDA uint8 tensors, bob: 3 tensors, field, mode}."""
         arr = (Out422Desc * len(jobs))()

@@ -25,7 +25,7 @@ EXPORTS = (
     "ntscsim_params_validate", "ntscsim_rng_calls_per_field", "ntscsim_rng_draw",
     "ntscsim_create", "ntscsim_destroy", "ntscsim_strerror", "ntscsim_last_error",
     "ntscsim_set_mode", "ntscsim_get_rng_pos", "ntscsim_set_rng_pos", "ntscsim_field", "ntscsim_frames_host",
-    "ntscsim_fields_device", "ntscsim_mixed_fields_device",
+    "ntscsim_fields_device", "ntscsim_mixed_fields_device", "ntscsim_mixed_fields422_device",
     "ntscsim_batch_create", "ntscsim_batch_run", "ntscsim_batch_destroy",
     "ntscsim_sync", "ntscsim_set_profiling", "ntscsim_get_timings_ms", "ntscsim_set_launch_form",
     "ntscsim_debug_read_composite", "ntscsim_debug_set_warmup",
@@ -193,6 +193,15 @@ class Field422Desc(C.Structure):
         ("_pad", C.c_uint32),
         ("fieldno", C.c_uint64),
         ("rng_pos", C.c_uint64),
+    ]
+
+
+class MixedField422Desc(C.Structure):
+    """struct ntscsim_mixed_field422_desc"""
+    _fields_ = [
+        ("d", Field422Desc),
+        ("set", C.c_int32),
+        ("_pad", C.c_int32),
     ]
 
 
@@ -573,6 +582,9 @@ def lib():
     L.ntscsim_mixed_fields_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(MixedFieldDesc), C.c_int,
                                               C.c_int, C.c_int, C.c_void_p]
     L.ntscsim_mixed_fields_device.restype = C.c_int
+    L.ntscsim_mixed_fields422_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(MixedField422Desc),
+                                                 C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.ntscsim_mixed_fields422_device.restype = C.c_int
     L.ntscsim_batch_create.argtypes = [C.c_void_p, C.POINTER(FieldDesc), C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]
     L.ntscsim_batch_create.restype = C.c_int

@@ -556,6 +556,50 @@ typedef struct ntscsim_field422_desc {
 int ntscsim_fields422_device(ntscsim_ctx *ctx, const ntscsim_field422_desc *descs, int n,
                              int width, int height, void *hip_stream);
 
+/*
+ * YUV422P fields of one geometry, EACH WITH ITS OWN PARAMETERS: ntscsim_mixed_fields_device() for the 8-bit tool -- a
+ * fields422 call whose descriptors name a set of `sets` (a library of stills, an augmentation run that gives every clip
+ * its own deck).  The call equals, in every byte of every destination and feedback plane and in the ctx's rand()
+ * position afterwards, this sequence for i = 0 .. n-1 in order: a ctx made with ntscsim_create(&sets[descs[i].set]) has
+ * its rand() position set to where descriptor i starts and runs ntscsim_fields422_device(&descs[i].d, 1, width, height)
+ * -- render_field, black_key_feedback, composite_video_process, each with THAT set's switches
+ * (black_key_level_feedback, video_yc_recombine, nocolor_subcarrier_after_yc_sep, tape speed, vhs_out_sharpen_chroma,
+ * S-Video or composite out and everything else the 8-bit tool derives from a set) -- but the fields run side by side in
+ * ONE launch of each kernel however many sets there are, nothing waits for the device, and the ctx's own parameters are
+ * neither read (except through set == -1) nor written.
+ * rand() positions: NTSCSIM_RNG_AUTO continues after the previous descriptor in the call's order, which advanced by
+ * ntscsim_rng_calls_per_field_422() of ITS set and parity -- by nothing if it carries NTSCSIM_422_NOCOMP; descs[0]
+ * continues from the ctx's position; the position moves only when the call succeeds, to the end of the last descriptor.
+ * Destinations and the separator's two bytes past each luma row: the rules of ntscsim_fields422_device() hold across
+ * the whole call, whatever sets the descriptors name -- the same frame and field twice is refused, both fields of one
+ * frame with dst_linesize[0] < width + 2 are refused, overlapping frames that are not side-by-side views are refused.
+ * Fields that share a FEEDBACK frame remain the caller's business, as there.
+ * Modes and ghosting: the YUV422P path has no float forms (ntscsim_set_mode changes nothing here) and ignores
+ * ghost_taps; so does this call.  All sets run the twelve-sweep kernel (every switch read at run time), not the
+ * streamed forms of the presets: a long run of fields on ONE preset is faster through ntscsim_fields422_device()
+ * (INTEGRATION.md).  ntscsim_debug_set_warmup is honoured; ntscsim_debug_last_kernels names what ran: k_mixed_setup,
+ * k422_mixed_render when some descriptor has a source, k422_mixed_bkey when some descriptor keys, k422_mixed_halo when
+ * some set's fields fill more than one workgroup of 63 rows, k422_mixed_process.  ntscsim_set_profiling /
+ * ntscsim_get_timings_ms cover the call as they cover ntscsim_fields422_device() (setup | (empty) | process).  Tables
+ * are cached as for ntscsim_mixed_fields_device(), per tool (ntscsim_debug_mixed_tables counts both tools' entries).
+ * Refused before anything is enqueued or the position moves -- NTSCSIM_E_ARG / NTSCSIM_E_SIZE: everything
+ * ntscsim_fields422_device() refuses (odd or out-of-range size, field > 1, NULL planes, short linesizes, a short
+ * src_height, n > 65535, more than 2^30 rows -- taken for the call's padded scanline space: every set's fields start at
+ * a multiple of 64 rows); a `set` outside -1 .. n_sets-1; n_sets < 0; a NULL `sets` that should hold something; a set
+ * some descriptor names with a wrong struct_size.  NTSCSIM_E_PARAM: a set some descriptor names that
+ * ntscsim_params_validate() refuses, or one with video_yc_recombine outside 0 .. 64.  Sets that no descriptor names are
+ * not looked at.  n == 0 succeeds and does nothing.  `sets` and `descs` are host memory, consumed by the call.
+ */
+typedef struct ntscsim_mixed_field422_desc {
+    ntscsim_field422_desc d;   /* as in ntscsim_fields422_device                                  */
+    int32_t               set; /* index into `sets`; -1: the parameters the ctx was created with  */
+    int32_t               _pad;
+} ntscsim_mixed_field422_desc;
+
+int ntscsim_mixed_fields422_device(ntscsim_ctx *ctx, const ntscsim_params *sets, int n_sets,
+                                   const ntscsim_mixed_field422_desc *descs, int n,
+                                   int width, int height, void *hip_stream);
+
 /* Prepared batch of the same call (like ntscsim_batch_create/run/destroy above): descriptors are
  * validated, their rand() windows derived and everything uploaded once; every ntscsim_batch422_run()
  * is then only the kernel launches.  The descriptors' frame pointers must stay valid; runs on one ctx

@@ -230,7 +230,32 @@ def mixed_fields_row(path="profiles/mixed_fields.json"):
             "`profiles/mixed_fields.json`, DESIGN.md §3c")
 
 
-for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row, cass_mixed_row, mixed_fields_row):
+def mixed_fields422_row(path="profiles/mixed_fields422.json"):
+    """The row of YUV422P fields with parameters per field, from tools/bench_mixed_fields422.py's file ("unmeasured" without one)."""
+    what = ("YUV422P fields with parameters per field in one call (`ntscsim_mixed_fields422_device`), 720×480, resident in HBM "
+            "(`tools/bench_mixed_fields422.py`); (a) one frame per set, against the same fields as one `ntscsim_fields422_device` call per set on one context "
+            "per set, wall clock; (b) all fields on one set (`-vhs`) through the mixed call, through `ntscsim_fields422_device` on `k422_process` and on its "
+            "streamed kernel; (c) the single-set `k422_process` of the parent commit and of this one, fresh processes; all in the same run")
+    try:
+        j = json.load(open(path))
+    except OSError:
+        return (what, "**unmeasured**: no GPU run of `tools/bench_mixed_fields422.py` was taken on this build", "DESIGN.md §7a")
+    a, p, b, c = j["a_mixed_call"], j["a_one_call_per_set"], j["b_all_fields_on_one_set"], j.get("parent_against_this")
+    host = ""
+    if "wall" in a:
+        host = (" (device events; %.2f ms on the wall clock, of which the host side of the call takes %.2f ms: %.1f × on the same clock)"
+                % (a["wall"]["ms"], a["host_ms_of_the_call"], j["a_per_set_over_mixed_wall"]))
+    txt = ("(a) %d fields over %d sets: **%.2f ms** (%.0f fields/s); one call per set %.1f ms, so the one call is worth **%.1f ×**%s; (b) %d fields on one set: "
+           "mixed call %.3f ms, `k422_process` %.3f ms (%.3f ×), streamed kernel %.3f ms (the mixed call takes %.2f × that).  Whole destination buffers equal "
+           "in (a) and in (b)" % (j["fields"], j["sets"], a["ms"], j["a_fields_per_s"], p["ms"], j["a_per_set_over_mixed"], host, j["fields"], b["mixed_call"]["ms"],
+                                b["k422_process_single_set"]["ms"], b["mixed_over_k422_process"], b["streamed_single_set"]["ms"], b["mixed_over_streamed"]))
+    if c:
+        txt += ("; (c) `k422_process`, %d rounds: parent %.3f-%.3f ms, this commit %.3f-%.3f ms"
+                % (c["rounds"], c["parent_range_ms"][0], c["parent_range_ms"][1], c["this_range_ms"][0], c["this_range_ms"][1]))
+    return (what, txt, "`profiles/mixed_fields422.json`, DESIGN.md §7a")
+
+
+for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row, cass_mixed_row, mixed_fields_row, mixed_fields422_row):
     try:
         rows.append(row())
     except Exception:
