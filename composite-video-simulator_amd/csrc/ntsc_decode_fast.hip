@@ -1103,8 +1103,13 @@ template <> struct FastWaves<float> { static constexpr int n = NTSC_FAST_WAVES_F
 // WR (VHS form only): head-switch displacements beyond W/10 samples, e.g. PAL's 312.5-line field with
 // the default switching point (see cs_load).  BK: subcarrier_amplitude_back other than 50 (the pre-emphasis
 // presets -comp-catv* raise it), see scale_back50.
+// `blk`: the workgroup's block of 63 rows among the rows of `fields` (P.R of them); `base`: their first row in the composite
+// plane.  A single-set launch passes blockIdx.x and 0.  A mixed call (ntsc_mixed.hip) passes the block within the group and the
+// group's first row, with every row-indexed scratch pointer advanced by `base` -- EXCEPT `comp`, which stays the whole plane:
+// cs_load relies on the descriptor's bounds check (num_records = W * Rpad * 4 from the plane's first byte) to read 0 outside
+// the row, so the group's first row goes into the lane's byte offset (C.vbase).  The `tails` column and stride stay launch-wide.
 template <bool VHS, class RT, bool WR, bool BK, bool SV = false, bool XA = false, bool FO = false>
-DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *__restrict__ fields,
+DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const unsigned blk, const int base, const FieldDev *__restrict__ fields,
                           const int *__restrict__ comp, const uint32_t *__restrict__ rs_chroma,
                           const int *__restrict__ n0_u, const int *__restrict__ n0_v,
                           const int *__restrict__ hs_shift, const int *__restrict__ pn_noise,
@@ -1120,7 +1125,7 @@ DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *
     extern __shared__ uint32_t yring[];
 
     const int lane = threadIdx.x;
-    const int gidx = blockIdx.x * 63 + lane - 1;          // lane 0 = halo (row above)
+    const int gidx = blk * 63 + lane - 1;                 // lane 0 = halo (row above)
     const int rc = gidx < 0 ? 0 : (gidx < P.R ? gidx : P.R - 1);
     const int f = rc / P.Lslot, k = rc - f * P.Lslot;
     const FieldDev &fd = fields[f];
@@ -1177,7 +1182,7 @@ DEV void decode_fast_body(const DevParams &P, const GeomDev &G, const FieldDev *
     C.rowbytes = P.Rpad * 4;
     // head switching :1687-1697: a per-lane byte offset plus the buffer bounds check (cs_load)
     const int hs = P.hs ? hs_shift[rc] : 0;
-    C.vbase = (int)((unsigned)rc * 4u + (unsigned)hs * (unsigned)C.rowbytes);
+    C.vbase = (int)((unsigned)(base + rc) * 4u + (unsigned)hs * (unsigned)C.rowbytes);
     {
         // shift > 0: wrap iff x >= tw - shift, i.e. (tw - shift - 1 - x) < 0; shift < 0: wrap iff x < -shift,
         // i.e. ~(-shift - 1 - x) < 0; shift == 0: never (A = INT_MAX / 2, no sign flip)
@@ -1292,7 +1297,7 @@ __global__ __launch_bounds__(64, VHS ? FastWaves<RT>::n : 4) void k_decode_fast(
                                                      const int *__restrict__ dropout,
                                                      int *__restrict__ tails)
 {
-    decode_fast_body<VHS, RT, WR, false>(P, G, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
+    decode_fast_body<VHS, RT, WR, false>(P, G, blockIdx.x, 0, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
 }
 
 // the same for a subcarrier_amplitude_back other than 50 (one form per preset: the VHS one takes the wrap-around loads)
@@ -1308,7 +1313,7 @@ __global__ __launch_bounds__(64, VHS ? FastWaves<RT>::n : 4) void k_decode_fast_
                                                      const int *__restrict__ dropout,
                                                      int *__restrict__ tails)
 {
-    decode_fast_body<VHS, RT, VHS, true>(P, G, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
+    decode_fast_body<VHS, RT, VHS, true>(P, G, blockIdx.x, 0, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
 }
 
 // the -vhs family with scanline phases of either parity (-comp-phase 90 / 270, or an odd -comp-phase-offset): the picks
@@ -1325,7 +1330,7 @@ __global__ __launch_bounds__(64, FastWaves<RT>::n) void k_decode_fast_xi(DevPara
                                                      const int *__restrict__ dropout,
                                                      int *__restrict__ tails)
 {
-    decode_fast_body<true, RT, true, false, false, true>(P, G, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
+    decode_fast_body<true, RT, true, false, false, true>(P, G, blockIdx.x, 0, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
 }
 
 // the -vhs family with the FULL output chroma low-pass (-out-composite-lowpass-lite 0; wrap-around loads)
@@ -1341,7 +1346,7 @@ __global__ __launch_bounds__(64, FastWaves<RT>::n) void k_decode_fast_fo(DevPara
                                                      const int *__restrict__ dropout,
                                                      int *__restrict__ tails)
 {
-    decode_fast_body<true, RT, true, false, false, false, true>(P, G, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
+    decode_fast_body<true, RT, true, false, false, false, true>(P, G, blockIdx.x, 0, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
 }
 
 // the -vhs preset with S-Video out (-vhs-svideo 1): the VCR's components go to the TV stages directly, no
@@ -1358,7 +1363,7 @@ __global__ __launch_bounds__(64, FastWaves<RT>::n) void k_decode_fast_sv(DevPara
                                                      const int *__restrict__ dropout,
                                                      int *__restrict__ tails)
 {
-    decode_fast_body<true, RT, true, false, true>(P, G, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
+    decode_fast_body<true, RT, true, false, true>(P, G, blockIdx.x, 0, fields, comp, rs_chroma, n0_u, n0_v, hs_shift, pn_noise, dropout, tails);
 }
 
 // =============================================================================== k_vcr_front

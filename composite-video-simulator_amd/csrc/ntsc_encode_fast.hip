@@ -248,9 +248,13 @@ struct CoopLoader {
 
 } // namespace fastenc
 
+// `blk`: the workgroup's block of 64 rows among the rows of `fields` (P.R of them); `base`: their first row in the composite
+// plane.  A single-set launch passes blockIdx.x and 0.  A mixed call (ntsc_mixed.hip) passes the block within the group and the
+// group's first row, with `rs_luma` / `n0_luma` advanced by `base` -- but `comp` is the WHOLE plane: the buffer descriptor's
+// num_records counts from its base address, so the group's first row goes into the lane's byte offset (C.vcol) instead.
 template <class RT, bool PRE, bool XA = false, int GH = 0>
-DEV void encode_fast_body(const DevParams &P, const FieldDev *__restrict__ fields, const uint32_t *__restrict__ rs_luma,
-                          const int *__restrict__ n0_luma, int *__restrict__ comp)
+DEV void encode_fast_body(const DevParams &P, const unsigned blk, const int base, const FieldDev *__restrict__ fields,
+                          const uint32_t *__restrict__ rs_luma, const int *__restrict__ n0_luma, int *__restrict__ comp)
 {
     using namespace fastenc;
     __shared__ uint32_t ring[33 * 64];            // LaneRand32
@@ -259,7 +263,7 @@ DEV void encode_fast_body(const DevParams &P, const FieldDev *__restrict__ field
 #endif
     __shared__ uint32_t gring[GH ? NTSC_GHOST_RING * 64 : 1];
     const int lane = threadIdx.x;
-    const int rho = blockIdx.x * 64 + lane;
+    const int rho = blk * 64 + lane;
     const int rc = rho < P.R ? rho : P.R - 1;
     const int f = rc / P.Lslot, k = rc - f * P.Lslot;
     const FieldDev &fd = fields[f];
@@ -285,7 +289,7 @@ DEV void encode_fast_body(const DevParams &P, const FieldDev *__restrict__ field
     C.a_i = (RT)P.a_in_i; C.a_q = (RT)P.a_in_q;
     C.a_pre = (RT)P.a_pre; C.pre_gain = (RT)P.pre_gain;
     C.rowbytes = P.Rpad * 4;
-    C.vcol = rho * 4;                  // rho < Rpad: lanes past the last row own padding columns
+    C.vcol = (base + rho) * 4;         // base + rho < Rpad: lanes past the last row own padding columns
     C.comp = __builtin_amdgcn_make_buffer_rsrc(comp, 0, (int)((unsigned)W * (unsigned)C.rowbytes), 0x00020000);
 
     EState<RT> S;
@@ -388,7 +392,7 @@ __global__ __launch_bounds__(64) void k_encode_fast(DevParams P, const FieldDev 
                                                     const int *__restrict__ n0_luma,
                                                     int *__restrict__ comp)
 {
-    encode_fast_body<RT, false>(P, fields, rs_luma, n0_luma, comp);
+    encode_fast_body<RT, false>(P, blockIdx.x, 0, fields, rs_luma, n0_luma, comp);
 }
 
 // the same with the ghosting extension folded in (GT = 2 or 4 taps, delays <= 63): stores the ghosted plane, no k_ghost pass
@@ -398,7 +402,7 @@ __global__ __launch_bounds__(64) void k_encode_fast_gh(DevParams P, const FieldD
                                                        const int *__restrict__ n0_luma,
                                                        int *__restrict__ comp)
 {
-    encode_fast_body<RT, false, false, GT>(P, fields, rs_luma, n0_luma, comp);
+    encode_fast_body<RT, false, false, GT>(P, blockIdx.x, 0, fields, rs_luma, n0_luma, comp);
 }
 
 // the same for scanline phases of either parity (-comp-phase 90 / 270, odd -comp-phase-offset)
@@ -408,7 +412,7 @@ __global__ __launch_bounds__(64) void k_encode_fast_xi(DevParams P, const FieldD
                                                        const int *__restrict__ n0_luma,
                                                        int *__restrict__ comp)
 {
-    encode_fast_body<RT, false, true>(P, fields, rs_luma, n0_luma, comp);
+    encode_fast_body<RT, false, true>(P, blockIdx.x, 0, fields, rs_luma, n0_luma, comp);
 }
 
 // the same with composite pre-emphasis (ffmpeg_ntsc.cpp:1614-1629; the -comp-catv* presets)
@@ -418,7 +422,7 @@ __global__ __launch_bounds__(64) void k_encode_fast_pre(DevParams P, const Field
                                                         const int *__restrict__ n0_luma,
                                                         int *__restrict__ comp)
 {
-    encode_fast_body<RT, true>(P, fields, rs_luma, n0_luma, comp);
+    encode_fast_body<RT, true>(P, blockIdx.x, 0, fields, rs_luma, n0_luma, comp);
 }
 
 } // namespace ntscsim

@@ -17,6 +17,7 @@
 #include "ntscsim.h"
 #include "ntsc_device.hpp"
 #include "mixed_plan.hpp"      // ntscsim_mixed_fields_device(): groups, rows, block tables and rand() positions of a call (no HIP in it)
+#include "mixed_forms.hpp"     // ... and which kernel form each group runs under ntscsim_set_mixed_forms(), with the forms' block tables (no HIP either)
 #include "engine_host.hpp"     // what the host-frame engines decide without the GPU: row maps, copy lists, copy threads, pinned ranges
 
 // single translation unit: the kernels are compiled together with their launcher
@@ -24,6 +25,7 @@
 #include "ntsc_mixed.hip"      // the generic chain over fields of different parameter sets (ntscsim_mixed_fields_device)
 #include "ntsc_decode_fast.hip"
 #include "ntsc_encode_fast.hip"
+#include "ntsc_mixed_fast.hip" // the hand-tuned kernels over fields of different parameter sets (ntscsim_set_mixed_forms)
 #include "ntsc_pipe.hip"
 #include "ntsc422_kernels.hip"
 #include "ntsc422_mixed.hip"   // the twelve-sweep YUV422P chain over fields of different parameter sets (ntscsim_mixed_fields422_device)
@@ -141,6 +143,7 @@ struct ntscsim_ctx {
     std::vector<MixedGeom *> mixed_geoms;
     std::vector<MixedPtab *> mixed_ptabs;
     uint64_t mixed_table_flushes = 0;    // times the two caches started over (ntscsim_debug_mixed_tables)
+    bool mixed_tuned = false;            // ntscsim_set_mixed_forms(): groups of the preset families take the hand-tuned kernels
     DevBuf<uint8_t> mixed_recs;
     unsigned char *mixed_stage[2] = {nullptr, nullptr};
     size_t mixed_stage_cap[2] = {0, 0};
@@ -587,6 +590,13 @@ extern "C" int ntscsim_set_launch_form(ntscsim_ctx *c, int form)
     return NTSCSIM_OK;
 }
 
+extern "C" int ntscsim_set_mixed_forms(ntscsim_ctx *c, int forms)
+{
+    if (!c || (forms != NTSCSIM_MIXED_GENERIC && forms != NTSCSIM_MIXED_TUNED)) return NTSCSIM_E_ARG;
+    c->mixed_tuned = forms == NTSCSIM_MIXED_TUNED;
+    return NTSCSIM_OK;
+}
+
 extern "C" int ntscsim_sync(ntscsim_ctx *c)
 {
     if (!c) return NTSCSIM_E_ARG;
@@ -887,22 +897,10 @@ static bool head_switch_is_small(const DevParams &D, int W)
     return m <= (int)(tw - (unsigned)W);
 }
 
-// The hand-tuned kernels address the transposed composite plane through a raw buffer descriptor with a
-// 32-bit byte offset: offset = row*4 + (x + head-switch displacement) * Rpad*4, compared (unsigned)
-// with num_records = W * Rpad*4, and out-of-range reads return the reference's fill value 0.  That only
-// works while the displaced offset cannot wrap around 2^32 back INTO the plane: the displacement lies in
-// [-W/10, +W/10] (head_switch_is_small), so both x + shift >= W and x + shift < 0 stay outside iff
-// (W + W/10 + 1) * Rpad*4 fits in 32 bits.  When the displacement can wrap around the tw = 1.1 W window
-// (|shift| up to tw/2: k_decode_fast's WR form) the offset is first formed for x + shift, which reaches
-// from -tw/2 to W - 1 + tw/2, and then moved by -+ tw samples: (W + tw + 1) * Rpad*4 is required to fit,
-// a margin that covers every intermediate value.  Larger planes take the generic kernels (64-bit
-// addressing).  hs_mode: 0 no head switching, 1 displacement <= W/10, 2 any displacement.
-static bool fast_plane_ok(size_t Rpad, int W, int hs_mode)
-{
-    const size_t tw = (size_t)W + (size_t)W / 10u;
-    const size_t span = (size_t)W + (hs_mode == 0 ? 0u : (hs_mode == 1 ? (size_t)W / 10u + 1u : tw + 1u));
-    return span * Rpad * 4u < 0xFFF00000ull;
-}
+// Whether the hand-tuned kernels' 32-bit byte offsets into the composite plane are safe for a plane of Rpad rows
+// (mixed_forms.hpp states the rule; the mixed call applies it to its call-wide Rpad).
+// hs_mode: 0 no head switching, 1 displacement <= W/10, 2 any displacement.
+static bool fast_plane_ok(size_t Rpad, int W, int hs_mode) { return mixed::fast_plane_ok(Rpad, W, hs_mode); }
 
 extern "C" int ntscsim_debug_fast_plane_ok(int n_fields, int W, int H, int head_switching)
 {
@@ -910,6 +908,43 @@ extern "C" int ntscsim_debug_fast_plane_ok(int n_fields, int W, int H, int head_
     const long long R = (long long)n_fields * ((H + 1) / 2);
     const size_t Rpad = (size_t)(((R + 63) / 64) * 64 + 64);         // as prepare_records
     return fast_plane_ok(Rpad, W, head_switching) ? 1 : 0;
+}
+
+// What mixed::form_of() needs to know of one parameter set, read off its DevParams as launch_records() reads them.
+static mixed::SetFacts mixed_set_facts(const DevParams &D, int W)
+{
+    mixed::SetFacts s;
+    s.in_lp = D.in_lp != 0; s.pre_on = D.pre_on != 0;
+    s.noise = D.noise_k != 0; s.cnoise = D.cnoise_k != 0; s.pnoise = D.pnoise_k != 0;
+    s.nocolor = D.nocolor != 0;
+    s.even_phase = (D.phase_mode == 180 || (D.phase_mode != 90 && D.phase_mode != 270)) && !(D.phase_off & 1);
+    s.vhs = D.vhs != 0; s.svideo = D.svideo != 0;
+    s.hs = D.hs != 0; s.hs_small = head_switch_is_small(D, W);
+    s.amp = D.amp; s.amp_back = D.amp_back; s.out_lp = D.out_lp;
+    return s;
+}
+
+extern "C" int ntscsim_debug_mixed_form_of(const ntscsim_params *set, int W, int H, int n_fields_total, int aligned, int mode,
+                                           int *enc_form, int *dec_form)
+{
+    if (!set || !enc_form || !dec_form || n_fields_total <= 0 || W < 16 || H < 2 || W > 16384 || H > 16384) return NTSCSIM_E_ARG;
+    // (FLOAT runs the FAST32 forms in a mixed call, and the forms of EXACT and FAST32 differ in the filter-state type only)
+    if (mode != NTSCSIM_MODE_EXACT && mode != NTSCSIM_MODE_FAST32 && mode != NTSCSIM_MODE_FLOAT) return NTSCSIM_E_ARG;
+    if (set->struct_size != sizeof(ntscsim_params)) return NTSCSIM_E_ARG;
+    const int vrc = ntscsim_params_validate(set);
+    if (vrc != NTSCSIM_OK) return vrc;
+    if (set->ghost_taps > 0) return NTSCSIM_E_PARAM;              // (the mixed call refuses such a set)
+    DevParams D;
+    fill_dev_params(*set, D);
+    const long long R = (long long)n_fields_total * ((H + 1) / 2);
+    mixed::CallFacts cf;
+    cf.Rpad = (size_t)(((R + 63) / 64) * 64 + 64);                // one group: as mixed::make_plan
+    cf.W = W;
+    cf.src_al16 = cf.dst_al16 = aligned != 0;
+    cf.force_generic = cf.no_fast = false;
+    const mixed::Forms f = mixed::form_of(mixed_set_facts(D, W), cf);
+    *enc_form = f.enc; *dec_form = f.dec;
+    return NTSCSIM_OK;
 }
 
 // ---- step 2: scratch + the kernel chain over device-resident records
@@ -1492,15 +1527,53 @@ static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n
     // device and starts both over before it takes any (entries are immutable while anything queued may read them).
     rc = mixed_tables_make_room(c, plan, params_of, W, H, 0);
     if (rc != NTSCSIM_OK) return rc;
-    // ---- records: [n FieldDev, sorted by group][ng MixedGroup][n group of a field][encoder blocks][decoder blocks x 3]
+    // ---- the kernel form of every group (csrc/mixed_forms.hpp).  Switch off (the default): the generic form of the group's
+    // decoder class, over the plan's own tables.  NTSCSIM_MIXED_TUNED: the hand-tuned form launch_records() picks for the
+    // set, under that form's preconditions taken for the call, and one block table per form.
+    const bool tuned = c->mixed_tuned && !c->force_generic && !c->no_fast_decode;
+    mixed::FormTables ft;
+    const std::vector<mixed::BlockRef> no_blocks;
+    const std::vector<mixed::BlockRef> *enc_t[mixed::N_ENC], *dec_t[mixed::N_DEC];
+    for (int e = 0; e < mixed::N_ENC; e++) enc_t[e] = e == mixed::ENC_GENERIC ? &plan.enc_tab : &no_blocks;
+    for (int d = 0; d < mixed::N_DEC; d++) dec_t[d] = d < mixed::N_CLS ? &plan.dec_tab[d] : &no_blocks;
+    unsigned lring_lds[mixed::N_DEC] = {0};       // dynamic LDS of a tuned decoder launch: the luma delay ring, if any of its groups runs it
+    if (tuned) {
+        mixed::CallFacts cf;
+        cf.Rpad = (size_t)plan.Rpad; cf.W = W; cf.src_al16 = al_src; cf.dst_al16 = al_dst;
+        cf.force_generic = c->force_generic; cf.no_fast = c->no_fast_decode;
+        std::vector<int> enc_form(ng), dec_form(ng);
+        for (size_t g = 0; g < ng; g++) {
+            DevParams D;
+            fill_dev_params(params_of(plan.groups[g].set), D);
+            const mixed::Forms f = mixed::form_of(mixed_set_facts(D, W), cf);
+            enc_form[g] = f.enc; dec_form[g] = f.dec;
+            if ((f.dec == mixed::DEC_FAST_VHS || f.dec == mixed::DEC_FAST_VHS_WR || f.dec == mixed::DEC_FAST_BK_VHS) &&
+                rowend::luma_ring(rowend::make_plan(W, D.cdelay, true, false, false)))
+                lring_lds[f.dec] = (unsigned)rowend::LUMA_RING_BYTES;
+        }
+        if (!mixed::make_form_tables(plan, enc_form.data(), dec_form.data(), ft)) {
+            c->err = "ntscsim_mixed_fields_device: internal error: a group's kernel form does not fit its decoder class";
+            return NTSCSIM_E_ARG;
+        }
+        for (int e = 0; e < mixed::N_ENC; e++) enc_t[e] = &ft.enc[e];
+        for (int d = 0; d < mixed::N_DEC; d++) dec_t[d] = &ft.dec[d];
+    }
+    // ---- records: [n FieldDev, sorted by group][ng MixedGroup][n group of a field][encoder blocks of all groups: k_mixed_setup]
+    //               [encoder blocks per form, where they are not all one form's][decoder blocks per form]
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t off_groups = up16((size_t)n * sizeof(FieldDev));
     const size_t off_gof = up16(off_groups + ng * sizeof(MixedGroup));
     const size_t off_enc = up16(off_gof + (size_t)n * sizeof(int32_t));
-    size_t off_dec[mixed::N_CLS + 1];
-    off_dec[0] = up16(off_enc + plan.enc_tab.size() * sizeof(MixedBlock));
-    for (int k = 0; k < mixed::N_CLS; k++) off_dec[k + 1] = up16(off_dec[k] + plan.dec_tab[k].size() * sizeof(MixedBlock));
-    const size_t bytes = off_dec[mixed::N_CLS];
+    size_t off_encf[mixed::N_ENC], off_dec[mixed::N_DEC];
+    size_t at = up16(off_enc + plan.enc_tab.size() * sizeof(MixedBlock));
+    for (int e = 0; e < mixed::N_ENC; e++) {
+        // (a form that holds every group's blocks IS the setup kernel's table)
+        if (enc_t[e]->size() == plan.enc_tab.size()) { off_encf[e] = off_enc; continue; }
+        off_encf[e] = at;
+        at = up16(at + enc_t[e]->size() * sizeof(MixedBlock));
+    }
+    for (int d = 0; d < mixed::N_DEC; d++) { off_dec[d] = at; at = up16(at + dec_t[d]->size() * sizeof(MixedBlock)); }
+    const size_t bytes = at;
     static_assert(sizeof(MixedBlock) == sizeof(mixed::BlockRef), "block table layout");
 
     const int si = c->mixed_stage_idx;
@@ -1520,7 +1593,6 @@ static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n
     for (int i = 0; i < n; i++)
         fill_field_record(c, descs[i].d, plan.rng_start[(size_t)i], fh[plan.slot[(size_t)i]]);
     MixedGroup *gh = reinterpret_cast<MixedGroup *>(host + off_groups);
-    bool any_cls[mixed::N_CLS] = {false, false, false};
     for (size_t g = 0; g < ng; g++) {
         const mixed::Group &pg = plan.groups[g];
         const ntscsim_params &prm = params_of(pg.set);
@@ -1538,15 +1610,16 @@ static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n
         o.G.ptab = nullptr;
         if (o.P.pnoise_k) { rc = mixed_ptab(c, o.P.pnoise_k, o.G.ptab); if (rc != NTSCSIM_OK) return rc; }
         o.base = pg.base; o.field0 = pg.field0;
-        any_cls[pg.cls] = true;
     }
     std::memcpy(host + off_gof, plan.group_of.data(), (size_t)n * sizeof(int32_t));
     std::memcpy(host + off_enc, plan.enc_tab.data(), plan.enc_tab.size() * sizeof(MixedBlock));
-    size_t dec_max = 0;
-    for (int k = 0; k < mixed::N_CLS; k++) {
-        if (!plan.dec_tab[k].empty())
-            std::memcpy(host + off_dec[k], plan.dec_tab[k].data(), plan.dec_tab[k].size() * sizeof(MixedBlock));
-        dec_max = std::max(dec_max, plan.dec_tab[k].size());
+    for (int e = 0; e < mixed::N_ENC; e++)
+        if (off_encf[e] != off_enc && !enc_t[e]->empty())
+            std::memcpy(host + off_encf[e], enc_t[e]->data(), enc_t[e]->size() * sizeof(MixedBlock));
+    size_t dec_max = 0;           // (`tails` is sized for the largest decoder table of the call)
+    for (int d = 0; d < mixed::N_DEC; d++) {
+        if (!dec_t[d]->empty()) std::memcpy(host + off_dec[d], dec_t[d]->data(), dec_t[d]->size() * sizeof(MixedBlock));
+        dec_max = std::max(dec_max, dec_t[d]->size());
     }
     // ---- scratch for the padded scanline space (all of it: which tables a call reads is per group)
     const size_t R = (size_t)plan.R, Rpad = (size_t)plan.Rpad;
@@ -1589,21 +1662,46 @@ static int mixed_fields_device(ntscsim_ctx *c, const ntscsim_params *sets, int n
     // (the names carry the filter-state type, as the single-set kernels' do: the float forms run the arithmetic of
     //  k_encode<1u,float> / k_decode<...,1u,float>, whose bytes tests/test_mixed_fields_gpu.py holds them to)
     const std::string rt = fast ? "float" : "double";
-    note_kernel(c, ("k_mixed_encode<" + rt + ">").c_str());
-    if (fast) hipLaunchKernelGGL((k_mixed_encode<float>), dim3((unsigned)nrs), dim3(64), 0, st, groups_dev, enc_dev, fields_dev,
-                                 c->rs_luma.p, c->n0_luma.p, c->comp.p);
-    else hipLaunchKernelGGL((k_mixed_encode<double>), dim3((unsigned)nrs), dim3(64), 0, st, groups_dev, enc_dev, fields_dev,
-                            c->rs_luma.p, c->n0_luma.p, c->comp.p);
+    // every form is launched over ITS block table, and only if some group takes it; the order is fixed (generic, then the
+    // hand-tuned forms in the order of mixed_forms.hpp) and ntscsim_debug_last_kernels reports it
+#define NTSC_MIXED_ENC(FORM, NAME, ...)                                                                                  \
+    do { if (!enc_t[FORM]->empty()) { note_kernel(c, (NAME "<" + rt + ">").c_str());                                      \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)enc_t[FORM]->size()), dim3(64), 0, st, groups_dev,                   \
+                       reinterpret_cast<const MixedBlock *>(c->mixed_recs.p + off_encf[FORM]), fields_dev,                \
+                       c->rs_luma.p, c->n0_luma.p, c->comp.p); } } while (0)
+    if (fast) {
+        NTSC_MIXED_ENC(mixed::ENC_GENERIC, "k_mixed_encode", k_mixed_encode<float>);
+        NTSC_MIXED_ENC(mixed::ENC_FAST, "k_mixed_encode_fast", k_mixed_encode_fast<float, false>);
+        NTSC_MIXED_ENC(mixed::ENC_FAST_PRE, "k_mixed_encode_fast_pre", k_mixed_encode_fast<float, true>);
+    } else {
+        NTSC_MIXED_ENC(mixed::ENC_GENERIC, "k_mixed_encode", k_mixed_encode<double>);
+        NTSC_MIXED_ENC(mixed::ENC_FAST, "k_mixed_encode_fast", k_mixed_encode_fast<double, false>);
+        NTSC_MIXED_ENC(mixed::ENC_FAST_PRE, "k_mixed_encode_fast_pre", k_mixed_encode_fast<double, true>);
+    }
+#undef NTSC_MIXED_ENC
     if (prof) HIPCHK(c, hipEventRecord(evs.e[2], st));
-#define NTSC_LAUNCH_MIXED_DECODE(CLS, VHS, CO, RT)                                                                      \
-    do { note_kernel(c, ("k_mixed_decode<" #VHS "," #CO "," + rt + ">").c_str());                                        \
-    hipLaunchKernelGGL((k_mixed_decode<VHS, CO, RT>), dim3((unsigned)plan.dec_tab[CLS].size()), dim3(64), 0, st, groups_dev, \
-                       reinterpret_cast<const MixedBlock *>(c->mixed_recs.p + off_dec[CLS]), fields_dev, c->comp.p,       \
-                       c->rs_chroma.p, c->n0_u.p, c->n0_v.p, c->hs_shift.p, c->pn_noise.p, c->dropout.p, c->tails.p); } while (0)
-    if (any_cls[mixed::CLS_TV]) { if (fast) NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_TV, false, false, float); else NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_TV, false, false, double); }
-    if (any_cls[mixed::CLS_VCR_COMP]) { if (fast) NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_COMP, true, true, float); else NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_COMP, true, true, double); }
-    if (any_cls[mixed::CLS_VCR_SVIDEO]) { if (fast) NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_SVIDEO, true, false, float); else NTSC_LAUNCH_MIXED_DECODE(mixed::CLS_VCR_SVIDEO, true, false, double); }
-#undef NTSC_LAUNCH_MIXED_DECODE
+    // (NAME: the kernel's name up to the filter-state type, TAIL: what follows it)
+#define NTSC_MIXED_DEC(FORM, NAME, TAIL, ...)                                                                            \
+    do { if (!dec_t[FORM]->empty()) { note_kernel(c, (NAME + rt + TAIL).c_str());                                         \
+    c->dec_lds = std::max(c->dec_lds, lring_lds[FORM]);                                                                   \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)dec_t[FORM]->size()), dim3(64), lring_lds[FORM], st, groups_dev,     \
+                       reinterpret_cast<const MixedBlock *>(c->mixed_recs.p + off_dec[FORM]), fields_dev, c->comp.p,      \
+                       c->rs_chroma.p, c->n0_u.p, c->n0_v.p, c->hs_shift.p, c->pn_noise.p, c->dropout.p, c->tails.p); } } while (0)
+#define NTSC_MIXED_DECODERS(RT)                                                                                          \
+    do {                                                                                                                 \
+        NTSC_MIXED_DEC(mixed::DEC_GENERIC_TV, std::string("k_mixed_decode<false,false,"), ">", k_mixed_decode<false, false, RT>);       \
+        NTSC_MIXED_DEC(mixed::DEC_GENERIC_VCR_COMP, std::string("k_mixed_decode<true,true,"), ">", k_mixed_decode<true, true, RT>);     \
+        NTSC_MIXED_DEC(mixed::DEC_GENERIC_VCR_SVIDEO, std::string("k_mixed_decode<true,false,"), ">", k_mixed_decode<true, false, RT>); \
+        NTSC_MIXED_DEC(mixed::DEC_FAST_TV, std::string("k_mixed_decode_fast<false,"), ">", k_mixed_decode_fast<false, RT>);             \
+        NTSC_MIXED_DEC(mixed::DEC_FAST_VHS, std::string("k_mixed_decode_fast<true,"), ">", k_mixed_decode_fast<true, RT>);              \
+        NTSC_MIXED_DEC(mixed::DEC_FAST_VHS_WR, std::string("k_mixed_decode_fast<true,"), ",true>", k_mixed_decode_fast<true, RT, true>); \
+        NTSC_MIXED_DEC(mixed::DEC_FAST_SV, std::string("k_mixed_decode_fast_sv<"), ">", k_mixed_decode_fast_sv<RT>);                    \
+        NTSC_MIXED_DEC(mixed::DEC_FAST_BK_TV, std::string("k_mixed_decode_fast_bk<false,"), ">", k_mixed_decode_fast_bk<false, RT>);    \
+        NTSC_MIXED_DEC(mixed::DEC_FAST_BK_VHS, std::string("k_mixed_decode_fast_bk<true,"), ">", k_mixed_decode_fast_bk<true, RT>);     \
+    } while (0)
+    if (fast) NTSC_MIXED_DECODERS(float); else NTSC_MIXED_DECODERS(double);
+#undef NTSC_MIXED_DECODERS
+#undef NTSC_MIXED_DEC
     if (prof) HIPCHK(c, hipEventRecord(evs.e[3], st));
     if (any_bob) {
         note_kernel(c, "k_mixed_bob");

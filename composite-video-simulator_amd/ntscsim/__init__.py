@@ -433,6 +433,11 @@ class FieldSimulator:
         """Device-resident launches of up to 64 fields as wavefront roles (ntscsim_set_launch_form: NTSCSIM_FORM_LATENCY)."""
         self._chk(self._lib.ntscsim_set_launch_form(self._h, 1 if latency else 0), "ntscsim_set_launch_form")
 
+    def set_mixed_forms(self, tuned=True):
+        """Later mixed_fields() calls run sets of the default / -vhs preset families on the hand-tuned kernels
+        (ntscsim_set_mixed_forms: NTSCSIM_MIXED_TUNED); every other set keeps the generic mixed kernels.  Same bytes."""
+        self._chk(self._lib.ntscsim_set_mixed_forms(self._h, 1 if tuned else 0), "ntscsim_set_mixed_forms")
+
     def set_profiling(self, on=True):
         self._lib.ntscsim_set_profiling(self._h, 1 if on else 0)
 

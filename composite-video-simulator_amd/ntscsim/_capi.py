@@ -28,6 +28,7 @@ EXPORTS = (
     "ntscsim_fields_device", "ntscsim_mixed_fields_device", "ntscsim_mixed_fields422_device",
     "ntscsim_batch_create", "ntscsim_batch_run", "ntscsim_batch_destroy",
     "ntscsim_sync", "ntscsim_set_profiling", "ntscsim_get_timings_ms", "ntscsim_set_launch_form",
+    "ntscsim_set_mixed_forms", "ntscsim_debug_mixed_form_of",
     "ntscsim_debug_read_composite", "ntscsim_debug_set_warmup",
     "ntscsim_debug_force_generic", "ntscsim_debug_no_fast_decode", "ntscsim_debug_last_kernels", "ntscsim_debug_last_decoder_lds", "ntscsim_debug_fast_plane_ok", "ntscsim_debug_field_stats", "ntscsim_debug_mixed_tables",
     "ntscsim_params_init_to_composite", "ntscsim_params_parse_argv_to_composite",
@@ -598,6 +599,10 @@ def lib():
     L.ntscsim_set_profiling.restype = None
     L.ntscsim_set_launch_form.argtypes = [C.c_void_p, C.c_int]
     L.ntscsim_set_launch_form.restype = C.c_int
+    L.ntscsim_set_mixed_forms.argtypes = [C.c_void_p, C.c_int]
+    L.ntscsim_set_mixed_forms.restype = C.c_int
+    L.ntscsim_debug_mixed_form_of.argtypes = [C.POINTER(Params)] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2
+    L.ntscsim_debug_mixed_form_of.restype = C.c_int
     L.ntscsim_get_timings_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     L.ntscsim_get_timings_ms.restype = C.c_int
     L.ntscsim_debug_read_composite.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t]

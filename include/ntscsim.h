@@ -759,6 +759,25 @@ int ntscsim_sync(ntscsim_ctx *ctx);
 enum { NTSCSIM_FORM_THROUGHPUT = 0, NTSCSIM_FORM_LATENCY = 1 };
 int ntscsim_set_launch_form(ntscsim_ctx *ctx, int form);
 
+/* Which kernels the groups of a later ntscsim_mixed_fields_device() call on this ctx run (nothing else is affected: the
+ * single-set calls, the YUV422P mixed call and the batches pick their kernels as before):
+ *   NTSCSIM_MIXED_GENERIC (default)  every group runs the generic mixed kernel of its decoder class (k_mixed_encode,
+ *                                    k_mixed_decode<..>): options read at run time;
+ *   NTSCSIM_MIXED_TUNED              a named set of the default or -vhs preset families -- noise levels, tape speed,
+ *                                    sharpening, head-switch point, S-Video out, PAL, the -comp-catv* presets -- runs the
+ *                                    hand-tuned kernel form ntscsim_fields_device() picks for it on a throughput-form ctx
+ *                                    (k_mixed_encode_fast*, k_mixed_decode_fast*: csrc/ntsc_mixed_fast.hip), when that form's
+ *                                    preconditions hold for the CALL: 16-byte aligned rows in every descriptor, and a
+ *                                    composite plane of the whole call small enough for 32-bit offsets
+ *                                    (ntscsim_debug_fast_plane_ok).  Every other set -- odd scanline phases, the full output
+ *                                    low-pass, nocolor, a subcarrier amplitude other than 50, no luma noise, no input
+ *                                    low-pass ... -- keeps the generic kernel, in the same call.  Still one launch per kernel
+ *                                    form present, in a fixed order (csrc/mixed_forms.hpp).  Same bytes, same refusals and
+ *                                    same rand() position either way.
+ * NTSCSIM_OK, NTSCSIM_E_ARG. */
+enum { NTSCSIM_MIXED_GENERIC = 0, NTSCSIM_MIXED_TUNED = 1 };
+int ntscsim_set_mixed_forms(ntscsim_ctx *ctx, int forms);
+
 /* Kernel timing from hipEvents recorded on the launch stream around each stage of every
  * ntscsim_fields_device() call made while profiling is on.  ntscsim_get_timings_ms() waits for
  * those calls, returns the SUMS since the previous query (index 0 setup kernels, 1 encode
@@ -812,6 +831,17 @@ int ntscsim_debug_last_decoder_lds(const ntscsim_ctx *ctx);
  * 2 = any displacement (the wrap-around form: a margin of a whole 1.1-width window either way).
  * 0 = the generic kernels run. */
 int ntscsim_debug_fast_plane_ok(int n_fields, int width, int height, int head_switching);
+
+/* Test hook (pure host arithmetic, no ctx): the kernel forms a NTSCSIM_MIXED_TUNED call gives the groups of `set` when
+ * the call holds n_fields_total fields of width x height in all (its composite plane is sized for all of them), every
+ * descriptor has 16-byte aligned rows (aligned != 0) or some have not, and the ctx is in `mode` (NTSCSIM_MODE_*: the forms
+ * of the three modes differ in the filter-state type only).  *enc_form: 0 generic, 1 k_mixed_encode_fast, 2 its
+ * pre-emphasis form.  *dec_form: 0 | 1 | 2 the generic kernel of the set's decoder class (no VCR | VCR with composite out |
+ * VCR with S-Video out), 3 k_mixed_decode_fast<false>, 4 k_mixed_decode_fast<true>, 5 its wrap-around form, 6
+ * k_mixed_decode_fast_sv, 7 k_mixed_decode_fast_bk<false>, 8 k_mixed_decode_fast_bk<true> (csrc/mixed_forms.hpp).
+ * NTSCSIM_OK, NTSCSIM_E_ARG, or what the mixed call returns for such a set (NTSCSIM_E_PARAM). */
+int ntscsim_debug_mixed_form_of(const ntscsim_params *set, int width, int height, int n_fields_total, int aligned, int mode,
+                                int *enc_form, int *dec_form);
 
 /* Test hook: what the synchronous call ntscsim_field() did since the ctx was created -- [0] calls, [1] calls whose SOURCE
  * frame was read where it is (pinned memory the GPU can address, 16-byte aligned rows: no upload), [2] calls whose

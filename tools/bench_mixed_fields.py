@@ -11,6 +11,13 @@ In the same run:
        ntscsim_fields_device with the generic kernels forced (ntscsim_debug_force_generic), and through
        ntscsim_fields_device as it runs by itself (the hand-tuned kernels); device events, medians
 
+  Each mixed call of (a) and (b) is measured twice in the same run: with the generic kernels (the default) and with
+  ntscsim_set_mixed_forms(NTSCSIM_MIXED_TUNED), where sets of the preset families take the hand-tuned kernels.  The
+  yardsticks are the generic mixed call (what the switch gains) and, in (b), the single-set hand-tuned call (what a
+  mixed call still loses).
+  (b')  the fields of (b) split over four sets of ONE kernel form (SP at four noise levels) and over SP / LP / EP /
+        S-Video (two decoder forms, three delay classes in one launch), tuned against generic
+
   (c), (d)  --compare-tree PARENT: what the change did to code it touched or sits beside, against a built tree of the
        parent commit, each figure taken in a fresh process, the two trees alternating, --rounds times: (d)
        ntscsim_fields_device with the generic kernels forced on the 2 * --sets -vhs fields of (b) -- the kernels whose
@@ -19,7 +26,7 @@ In the same run:
        "parent_against_this" of the --out file.
 
 Every descriptor carries an explicit rand() position, so all forms compute the same fields.  Verified before a number is
-printed: (a)'s two forms and (b)'s three forms wrote the same bytes.
+printed: (a)'s two forms and (b)'s four forms wrote the same bytes, and every tuned call the bytes of its generic twin.
 
     python tools/bench_mixed_fields.py [--sets 300] [--reps 5] [--warmup 2] [--compare-tree PARENT [--rounds 2]]
                                        [--out profiles/mixed_fields.json]"""
@@ -106,7 +113,7 @@ def main():
     gen = torch.Generator(device="cuda")
     gen.manual_seed(20)
     src = torch.randint(0, 256, (8, H, W, 4), dtype=torch.uint8, device="cuda", generator=gen)
-    dst = [torch.zeros((n_sets, H, W, 4), dtype=torch.uint8, device="cuda") for _ in range(3)]
+    dst = [torch.zeros((n_sets, H, W, 4), dtype=torch.uint8, device="cuda") for _ in range(4)]
     # field k: frame k // 2 of the destination, parity (k & 1) ^ 1, fieldno k, rand() position k * 2^21 (past any field's draws)
     jobs = [(k // 2 % 8, k // 2, (k & 1) ^ 1, k) for k in range(n)]
     pos = [k << 21 for k in range(n)]
@@ -169,6 +176,21 @@ def main():
     case["host_ms_of_the_call"] = (time.perf_counter() - t0) * 1e3
     stream.synchronize()
     result["a_mixed_call"] = case
+    # ... and with the hand-tuned kernels behind it (another context: the switch is the context's)
+    tuned = ntscsim.FieldSimulator()
+    tuned.set_mixed_forms(True)
+    tuned_descs = tuned.build_mixed_descs(set_of, src, dst[3], jobs, rng_pos=pos)
+
+    def run_tuned():
+        tuned.run_mixed_descs(set_arr, tuned_descs, W, H, stream=stream.cuda_stream)
+
+    tcase = events(run_tuned)
+    tcase["kernels"] = tuned.last_kernels()
+    result["a_tuned_mixed_call"] = tcase
+    torch.cuda.synchronize()
+    if not torch.equal(dst[0], dst[3]):
+        sys.exit("(a): the tuned mixed call differs from the generic one (%d bytes)" % int((dst[0] != dst[3]).sum()))
+    result["a_generic_over_tuned"] = case["ms"] / tcase["ms"]
     per = [ntscsim.FieldSimulator(params=p) for p in sets]
     per_descs = [c.build_descs(src, dst[1], jobs[2 * s:2 * s + 2], rng_pos=pos[2 * s:2 * s + 2]) for s, c in enumerate(per)]
 
@@ -205,21 +227,54 @@ def main():
     def run_fast():
         one.run_descs(fast_descs, W, H, stream=stream.cuda_stream)
 
+    tuned_uni_descs = tuned.build_mixed_descs([0] * n, src, dst[3], jobs, rng_pos=pos)
+
+    def run_uniform_tuned():
+        tuned.run_mixed_descs(uni_sets, tuned_uni_descs, W, H, stream=stream.cuda_stream)
+
     b = {"set": "-vhs"}
     b["mixed_call"] = events(run_uniform_mixed)
     b["mixed_call"]["kernels"] = sim.last_kernels()
+    b["tuned_mixed_call"] = events(run_uniform_tuned)
+    b["tuned_mixed_call"]["kernels"] = tuned.last_kernels()
     b["generic_single_set"] = events(run_generic)
     b["generic_single_set"]["kernels"] = one.last_kernels()
     b["hand_tuned_single_set"] = events(run_fast)
     b["hand_tuned_single_set"]["kernels"] = one.last_kernels()
     torch.cuda.synchronize()
-    if not torch.equal(dst[0], dst[1]) or not torch.equal(dst[0], dst[2]):
-        sys.exit("(b): the three forms differ")
+    if not torch.equal(dst[0], dst[1]) or not torch.equal(dst[0], dst[2]) or not torch.equal(dst[0], dst[3]):
+        sys.exit("(b): the four forms differ")
+    b["generic_over_tuned"] = b["mixed_call"]["ms"] / b["tuned_mixed_call"]["ms"]
+    b["tuned_over_hand_tuned"] = b["tuned_mixed_call"]["ms"] / b["hand_tuned_single_set"]["ms"]
     b["mixed_over_generic"] = b["mixed_call"]["ms"] / b["generic_single_set"]["ms"]
     b["mixed_over_hand_tuned"] = b["mixed_call"]["ms"] / b["hand_tuned_single_set"]["ms"]
     result["b_all_fields_on_one_set"] = b
-    result["verified"] = "(a) mixed call == one call per set; (b) mixed == generic == hand-tuned; whole destination buffers"
+    # ---- (b')
+    splits = {
+        "four_noise_levels_sp": [ntscsim.make_params(["-vhs", "-noise", str(k)]) for k in (1, 2, 4, 8)],
+        "sp_lp_ep_svideo": [ntscsim.make_params(f) for f in (["-vhs"], ["-vhs", "-vhs-speed", "lp"], ["-vhs", "-vhs-speed", "ep"],
+                                                             ["-vhs", "-vhs-svideo", "1"])],
+    }
+    result["b_split_over_four_sets"] = {}
+    for name, four in splits.items():
+        four_arr = sim.build_sets(four)
+        four_of = [(k // 2) % 4 for k in range(n)]
+        g_descs = sim.build_mixed_descs(four_of, src, dst[0], jobs, rng_pos=pos)
+        t_descs = tuned.build_mixed_descs(four_of, src, dst[3], jobs, rng_pos=pos)
+        r = {"mixed_call": events(lambda: sim.run_mixed_descs(four_arr, g_descs, W, H, stream=stream.cuda_stream))}
+        r["mixed_call"]["kernels"] = sim.last_kernels()
+        r["tuned_mixed_call"] = events(lambda: tuned.run_mixed_descs(four_arr, t_descs, W, H, stream=stream.cuda_stream))
+        r["tuned_mixed_call"]["kernels"] = tuned.last_kernels()
+        torch.cuda.synchronize()
+        if not torch.equal(dst[0], dst[3]):
+            sys.exit("(b'), %s: the tuned mixed call differs from the generic one" % name)
+        r["generic_over_tuned"] = r["mixed_call"]["ms"] / r["tuned_mixed_call"]["ms"]
+        r["tuned_over_hand_tuned_one_set"] = r["tuned_mixed_call"]["ms"] / b["hand_tuned_single_set"]["ms"]
+        result["b_split_over_four_sets"][name] = r
+    result["verified"] = ("(a) mixed call == one call per set == tuned mixed call; (b) mixed == tuned mixed == generic == hand-tuned; "
+                          "(b') tuned mixed == mixed; whole destination buffers")
     sim.close()
+    tuned.close()
     one.close()
     if a.compare_tree:
         result["parent_against_this"] = compare_trees(a, os.path.abspath(a.compare_tree))

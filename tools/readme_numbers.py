@@ -230,6 +230,30 @@ def mixed_fields_row(path="profiles/mixed_fields.json"):
             "`profiles/mixed_fields.json`, DESIGN.md §3c")
 
 
+def mixed_fields_tuned_row(path="profiles/mixed_fields_tuned.json"):
+    """The row of the mixed call on the hand-tuned kernels (ntscsim_set_mixed_forms), from the same tool's file."""
+    what = ("the same call with `ntscsim_set_mixed_forms(NTSCSIM_MIXED_TUNED)` (off by default): sets of the default / `-vhs` preset families on the "
+            "hand-tuned kernels, every other set on the generic ones, in the one call; against the generic mixed call and, in (b), against the single-set "
+            "hand-tuned call; (b′) the fields of (b) over four sets; all in the same run")
+    try:
+        j = json.load(open(path))
+    except OSError:
+        return (what, "**unmeasured**: no GPU run of `tools/bench_mixed_fields.py` was taken on this build", "DESIGN.md §3c")
+    a, at, b, s = j["a_mixed_call"], j["a_tuned_mixed_call"], j["b_all_fields_on_one_set"], j["b_split_over_four_sets"]
+    s1, s2 = s["four_noise_levels_sp"], s["sp_lp_ep_svideo"]
+    txt = ("(a) %d fields over %d sets: tuned **%.2f ms**, generic %.2f ms (**%.2f ×**); (b) %d fields on one set: tuned %.3f ms, generic mixed %.3f ms "
+           "(**%.2f ×**), single-set hand-tuned %.3f ms (the tuned call takes %.2f × that); (b′) SP at four noise levels: tuned %.3f ms, generic %.3f ms "
+           "(%.2f ×); SP / LP / EP / S-Video: tuned %.3f ms, generic %.3f ms (%.2f ×).  Every tuned call wrote the bytes of its generic twin"
+           % (j["fields"], j["sets"], at["ms"], a["ms"], j["a_generic_over_tuned"], j["fields"], b["tuned_mixed_call"]["ms"], b["mixed_call"]["ms"],
+              b["generic_over_tuned"], b["hand_tuned_single_set"]["ms"], b["tuned_over_hand_tuned"], s1["tuned_mixed_call"]["ms"], s1["mixed_call"]["ms"],
+              s1["generic_over_tuned"], s2["tuned_mixed_call"]["ms"], s2["mixed_call"]["ms"], s2["generic_over_tuned"]))
+    c = j.get("parent_against_this")
+    if c:
+        cp, ct = c["c_bench_py_fields_per_s"]["parent"], c["c_bench_py_fields_per_s"]["this"]
+        txt += ("; `bench.py`, %d rounds of fresh processes: parent %.0f-%.0f, this commit %.0f-%.0f fields/s" % (c["rounds"], min(cp), max(cp), min(ct), max(ct)))
+    return (what, txt, "`profiles/mixed_fields_tuned.json`, DESIGN.md §3c")
+
+
 def mixed_fields422_row(path="profiles/mixed_fields422.json"):
     """The row of YUV422P fields with parameters per field, from tools/bench_mixed_fields422.py's file ("unmeasured" without one)."""
     what = ("YUV422P fields with parameters per field in one call (`ntscsim_mixed_fields422_device`), 720×480, resident in HBM "
@@ -255,7 +279,7 @@ def mixed_fields422_row(path="profiles/mixed_fields422.json"):
     return (what, txt, "`profiles/mixed_fields422.json`, DESIGN.md §7a")
 
 
-for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row, cass_mixed_row, mixed_fields_row, mixed_fields422_row):
+for row in (led_row, filmac_row, audio_tracks_row, audio_mixed_row, cass_tracks_row, cass_mixed_row, mixed_fields_row, mixed_fields_tuned_row, mixed_fields422_row):
     try:
         rows.append(row())
     except Exception:
