@@ -9,7 +9,10 @@ A row: (id, flags, w, h, n, layout, source, kernel, fallback, share, hs)
   layout    "padded"     luma rows 16-byte and chroma rows 8-byte aligned, luma linesize >= W + 2 (nothing is excluded)
             "tight"      linesize == W (a multiple of 16): the two bytes behind a luma row are the next row's
             "odd"        luma linesize W + 3: the streamed forms' precondition fails
-            "odd-chroma" luma rows aligned, chroma linesize W/2 + 4 at W/2 = 0 mod 8: the precondition fails in chroma alone
+            "odd-chroma" luma rows aligned, chroma linesize W/2 + 4 (+ 1 where that is a multiple of 8): the precondition fails
+                         in chroma alone
+            "odd-luma"   luma linesize W + 3, chroma rows 8-byte aligned (the planes start at multiples of 16): it fails in
+                         luma alone (tests/_sweep422_forms.py)
   source    "inplace"  the frames hold the pictures; "src" / "src420" / "src-il": through k422_render from progressive 4:2:2,
             progressive 4:2:0 and interlaced (top field first, second field) 4:2:2 sources
   kernel    the ONE role-kernel name ntscsim_debug_last_kernels() must report, or None
@@ -351,7 +354,10 @@ def linesizes(w, layout):
     if layout == "odd":
         return [w + 3, w // 2 + 3, w // 2 + 3]
     if layout == "odd-chroma":
-        return [up(w + 2, 16), w // 2 + 4, w // 2 + 4]
+        c = w // 2 + 4 + (1 if (w // 2 + 4) % 8 == 0 else 0)
+        return [up(w + 2, 16), c, c]
+    if layout == "odd-luma":
+        return [w + 3, up(w // 2 + 2, 8), up(w // 2 + 2, 8)]
     return [up(w + 2, 16), up(w // 2 + 2, 8), up(w // 2 + 2, 8)]
 
 
@@ -363,9 +369,19 @@ def aligned(w, layout):
 GUARD = 64          # bytes between two frames of a launch's buffer (and behind the last one)
 
 
+def plane_offsets(w, h, layout):
+    """where the three planes start in a frame's bytes: back to back -- behind an unaligned luma plane ("odd-luma") at the
+    next multiple of 16, so that the chroma rows are aligned on their own"""
+    ls = linesizes(w, layout)
+    o1 = ls[0] * h
+    if layout == "odd-luma":
+        o1 = (o1 + 15) // 16 * 16
+    return [0, o1, o1 + ls[1] * h]
+
+
 def frame_bytes(w, h, layout):
     ls = linesizes(w, layout)
-    return (sum(ls) * h + GUARD + 63) // 64 * 64
+    return (plane_offsets(w, h, layout)[2] + ls[2] * h + GUARD + 63) // 64 * 64
 
 
 def frame_at(buf, k, w, h, layout):
@@ -374,7 +390,7 @@ def frame_at(buf, k, w, h, layout):
     nb = frame_bytes(w, h, layout)
     f = L.Yuv422.__new__(L.Yuv422)
     f.w, f.h, f.ls = w, h, linesizes(w, layout)
-    f.off = [0, f.ls[0] * h, f.ls[0] * h + f.ls[1] * h]
+    f.off = plane_offsets(w, h, layout)
     f.buf = buf[k * nb:(k + 1) * nb]
     return f
 
